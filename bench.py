@@ -30,6 +30,18 @@ Beside it, at N = 1 and outside the timed region:
 N > 1 (driver: torch.distributed.run, one rank per GPU): the SAME job sharded N ways by fragment lineage (strong
 scaling); per-pass primer-stock all-reduce and the allocation partials over RCCL; every rank writes its own FASTQ shard
 (its own part files, its own PCIe link and writer threads).
+--dump-outputs DIR (N = 1) writes what the last timed step computed, once the timed region is over, as DIR/<name>.npy:
+  job_counts                    float64: pairs, reads, FASTQ bytes of mate 1 and of mate 2, fragments, semi-amplicons, full
+                                amplicons, primers left, reads requested (scs_stats of the job)
+  read<m>_bases, read<m>_quals  float32 [8192, L + 64]: base codes (A C G T N = 0..4) and Phred qualities of a sample of mate m's
+                                records, -1 past a read's end; the records are those holding the bytes at 8192 offsets drawn with a
+                                fixed seed over the whole text of the mate (the concatenation of its part files), in text order
+  read<m>_length, read<m>_amplicon, read<m>_attempt
+                                float32 / float64 / float32 [8192]: the read's length and the two numbers of its name
+                                @<amplicon>#<attempt>/<m>
+The sample is a function of the text alone (not of the number of part files). To sample it, the last timed step keeps its
+part files until the timed region is over, and so its sink starts when no older text is left (one step's text is the most
+tmpfs holds). With --hbm-only the text stays in HBM and only job_counts is written.
 """
 import argparse
 import glob
@@ -233,6 +245,65 @@ def cpu_baseline(td, prof, names, seqs, sample_desc, coverage):
                 os.remove(fa + suf)
     os.remove(fa)
     return out or None
+
+
+DUMP_RECORDS = 8192                 # records sampled per mate by --dump-outputs (2 x 8192 x 2 x 214 float32 at PE150: 28 MB)
+
+
+def sample_fastq(paths, n, L, rng):
+    """n records of one mate's FASTQ text, the text being the concatenation of `paths`: the records holding the bytes at n offsets
+    that `rng` draws uniformly over the text, in text order.  Returns float arrays (see --dump-outputs in the module's docstring)."""
+    import numpy as np
+    W = L + 64                                                       # the longest read (indels)
+    span = 2 * W + 64                                                # the longest record: name, read, "+", qualities
+    sizes = [os.path.getsize(p) for p in paths]
+    starts = np.cumsum([0] + sizes)
+    codes = np.full(256, -1, np.float32)
+    codes[np.frombuffer(b"ACGTN", np.uint8)] = np.arange(5)
+    out = {"bases": np.full((n, W), -1, np.float32), "quals": np.full((n, W), -1, np.float32), "length": np.zeros(n, np.float32),
+           "amplicon": np.zeros(n, np.float64), "attempt": np.zeros(n, np.float32)}
+    offs = np.sort(rng.integers(0, int(starts[-1]), n))
+    for k, o in enumerate(offs):
+        p = int(np.searchsorted(starts, o, side="right")) - 1        # parts end on record boundaries
+        lo = int(o - starts[p])
+        w0 = max(0, lo - span)
+        with open(paths[p], "rb") as f:
+            f.seek(w0)
+            buf = f.read(min(sizes[p], lo + span) - w0)
+        # the separator line "+" is the one line of a record that can be told apart from the window alone (qualities are >= 50 long)
+        q = buf.find(b"\n+\n")
+        while q >= 0:
+            s = buf.rfind(b"\n", 0, q) + 1                           # the read's line
+            h = buf.rfind(b"\n", 0, s - 1) + 1 if s else -1          # the name's line (at 0: whole only at the part's start)
+            e = buf.find(b"\n", q + 3)
+            if (h > 0 or (h == 0 and w0 == 0)) and e >= 0 and h <= lo - w0 <= e:
+                break
+            q = buf.find(b"\n+\n", q + 1)
+        if q < 0:
+            raise ValueError("%s: no FASTQ record holds byte %d" % (paths[p], lo))
+        name, seq, qual = buf[h:s - 1], buf[s:q], buf[q + 3:e]
+        if name[:1] != b"@" or len(seq) != len(qual) or len(seq) > W:
+            raise ValueError("%s: malformed FASTQ record at byte %d" % (paths[p], w0 + h))
+        amp, att = name[1:].split(b"/")[0].split(b"#")
+        m = len(seq)
+        out["bases"][k, :m] = codes[np.frombuffer(seq, np.uint8)]
+        out["quals"][k, :m] = np.frombuffer(qual, np.uint8).astype(np.float32) - 33
+        out["length"][k], out["amplicon"][k], out["attempt"][k] = m, int(amp), int(att)
+    return out
+
+
+def dump_outputs(d, st, parts, L):
+    """--dump-outputs: the job's counts and, when the step wrote files (`parts`: per mate, its part files in record order), a seeded
+    sample of every mate's records, as d/<name>.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    counts = [st["pairs_written"], st["reads_written"], st["fastq_bytes"][0], st["fastq_bytes"][1], st["fragments"], st["semi_amplicons"],
+              st["full_amplicons"], st["primers_left"], st["reads_requested"]]
+    np.save(os.path.join(d, "job_counts.npy"), np.array(counts, np.float64))
+    rng = np.random.default_rng(20240607)
+    for m, paths in enumerate(parts or []):
+        for k, v in sample_fastq(paths, DUMP_RECORDS, L, rng).items():
+            np.save(os.path.join(d, "read%d_%s.npy" % (m + 1, k)), v)
 
 
 def summary_rows(path):
@@ -581,7 +652,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the generation-only, D2H-only, small-configuration and CLI legs")
     ap.add_argument("--cpu-sample-mb", type=float, default=4.0)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (see the module's docstring)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.gpus != 1 or a.steps < 1):
+        ap.error("--dump-outputs needs --gpus 1 and at least one timed step")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus))                               # (this process never touches the GPU)
@@ -693,8 +767,9 @@ def main():
             for f in ("launches", "ms", "units"):
                 d[f] += kt[k][f]
 
-    def step(i, ktimes, stage, mode):
-        """one whole job with a fresh seed; mode: 'files' (K part files per mate), 'null' (text stays in HBM), or a sink callable"""
+    def step(i, ktimes, stage, mode, keep=None):
+        """one whole job with a fresh seed; mode: 'files' (K part files per mate), 'null' (text stays in HBM), or a sink callable.
+        keep: a list that takes the step's part files (per mate, in record order) and the files beside them instead of the cleaners"""
         g.set_seed(1000 + i)
         if mode in ("files", "bgzf"):
             cleaner.boost()                                          # (the step before's files: every core may free them until this step's sink starts)
@@ -705,11 +780,14 @@ def main():
         t3 = time.perf_counter()
         waited = 0.0
         if mode in ("files", "bgzf", "files_alone"):
-            waited = cleaner.gate(0 if mode == "files_alone" else GATE_BYTES)
+            waited = cleaner.gate(0 if mode == "files_alone" or keep is not None else GATE_BYTES)
             base = os.path.join(out_dir, "step%d" % i)
             lbase = base + (".r%d" % rank if world > 1 else "")
             pp = scssim_amd.part_paths(lbase, writers * generations, True, ".fq.gz" if mode == "bgzf" else ".fq")
-            if mode == "files_alone":                                # one job on an EMPTY tmpfs, nothing unlinked while it runs: what a single run sees
+            if keep is not None:
+                def finish(extra):
+                    keep.extend([pp, list(extra)])
+            elif mode == "files_alone":                              # one job on an EMPTY tmpfs, nothing unlinked while it runs: what a single run sees
                 def finish(extra):
                     cleaner.add([f for p in range(writers * generations) for f in (pp[0][p], pp[1][p])] + list(extra))
             else:
@@ -731,8 +809,9 @@ def main():
             stage[k] = stage.get(k, 0.0) + v
         return g.stats()
 
-    def timed(n_warm, n_steps, mode, first):
-        """n_warm untimed + n_steps timed steps; returns (elapsed, pairs, fastq bytes, amplicons, kernel times, stage seconds)"""
+    def timed(n_warm, n_steps, mode, first, keep=None):
+        """n_warm untimed + n_steps timed steps; returns (elapsed, pairs, fastq bytes, amplicons, kernel times, stage seconds, the last
+        step's stats); keep: the last step's files go there (step)"""
         kt, stage = {}, {}
         for i in range(n_warm):                                      # the first step also maps the device buffers and pins the sink's
             step(first + i, kt, stage, mode)
@@ -741,10 +820,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        pairs = fqb = amps = 0; per_step = []
+        pairs = fqb = amps = 0; per_step = []; last = None
         for i in range(n_steps):
             ts = time.perf_counter()
-            last = step(first + n_warm + i, kt, stage, mode)
+            last = step(first + n_warm + i, kt, stage, mode, keep if i == n_steps - 1 else None)
             per_step.append(time.perf_counter() - ts)                   # (this rank's view; the timed region is the barrier-to-barrier total)
             pairs += last["pairs_written"]; fqb += sum(last["fastq_bytes"]); amps += last["semi_amplicons"] + last["full_amplicons"]
         torch.cuda.synchronize()
@@ -768,10 +847,18 @@ def main():
             pairs, fqb_all, amps = int(pt[0]), int(pt[1]), int(pt[2])
         else:
             fqb_all = fqb
-        return dict(elapsed=elapsed, pairs=pairs, fq_bytes_local=fqb, fq_bytes=fqb_all, amps=amps, ktimes=kt, stage={k: v / n_steps for k, v in stage.items()}, per_rank=per_rank, per_step=per_step)
+        return dict(elapsed=elapsed, pairs=pairs, fq_bytes_local=fqb, fq_bytes=fqb_all, amps=amps, ktimes=kt, stage={k: v / n_steps for k, v in stage.items()}, per_rank=per_rank, per_step=per_step,
+                    last=last)
 
     main_mode = "null" if a.hbm_only else "files"
-    R = timed(a.warmup, a.steps, main_mode, 0)
+    kept = [] if a.dump_outputs else None
+    R = timed(a.warmup, a.steps, main_mode, 0, kept)
+    if a.dump_outputs:
+        try:
+            dump_outputs(a.dump_outputs, R["last"], kept[0] if kept else None, g.read_length)
+        finally:
+            if kept:
+                cleaner.add([f for m in kept[0] for f in m] + kept[1])
     cleaner.gate(0)                                                  # (outside the timed region: the last step's files)
     # ---- generation only (every rank takes part: the steps hold the job's collectives): the same job with a NULL sink -- the text is
     # written into HBM batch buffers (8 M pairs per launch) and counted.  What the kernels do when nothing has to cross PCIe; the

@@ -278,6 +278,40 @@ def test_bench_starts_its_own_ranks_and_relays_their_failure(tmp_path):
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_bench_dump_sample_is_the_records_of_the_text_whatever_its_parts(tmp_path):
+    """bench.py --dump-outputs samples a mate's FASTQ text at seeded byte offsets: the records it returns are the ones holding those
+    bytes, parsed right (qualities that contain '@' and '+', reads of 50 .. L + 64 bases), and the same when the text is one file or
+    part files cut anywhere between records (empty parts, a one-record part)."""
+    import bench
+    rng = np.random.default_rng(5)
+    L = 150
+    recs = []
+    for i in range(3000):
+        m = int(rng.integers(50, L + 65))
+        recs.append((1000000000 + 3 * i, int(rng.integers(1, 9)), bytes(np.frombuffer(b"ACGTN", np.uint8)[rng.integers(0, 5, m)]),
+                     bytes(rng.integers(33, 127, m).astype(np.uint8))))
+    raw = [b"@%d#%d/1\n%s\n+\n%s\n" % r for r in recs]
+    starts = np.cumsum([0] + [len(r) for r in raw])
+
+    def parts(name, cuts):
+        bounds = [0] + cuts + [len(raw)]
+        paths = [str(tmp_path / ("%s.p%02d" % (name, k))) for k in range(len(bounds) - 1)]
+        for p, lo, hi in zip(paths, bounds, bounds[1:]):
+            open(p, "wb").write(b"".join(raw[lo:hi]))
+        return paths
+    one = bench.sample_fastq(parts("one", []), 2048, L, np.random.default_rng(1))
+    cut = bench.sample_fastq(parts("cut", [0, 1, 700, 701, 701, 2999, 3000]), 2048, L, np.random.default_rng(1))
+    assert all(np.array_equal(one[k], cut[k]) for k in one)
+    offs = np.sort(np.random.default_rng(1).integers(0, int(starts[-1]), 2048))
+    for k, r in enumerate(np.searchsorted(starts, offs, side="right") - 1):
+        amp, att, seq, qual = recs[r]
+        m = len(seq)
+        assert (one["amplicon"][k], one["attempt"][k], one["length"][k]) == (amp, att, m)
+        assert np.array_equal(one["bases"][k, :m], ["ACGTN".index(c) for c in seq.decode()])
+        assert np.array_equal(one["quals"][k, :m], np.frombuffer(qual, np.uint8) - 33.0)
+        assert (one["bases"][k, m:] == -1).all() and (one["quals"][k, m:] == -1).all()
+
+
 def test_bgzf_arithmetic_inflates_with_zlib():
     """The BGZF kernels' arithmetic run on the CPU (scs_bgzf_probe: the same functions "thread" by "thread" -- Huffman lengths with
     the 15-bit limit, the run-length coded header under a fixed code-length code, 256 chunks packed at prefix-sum bit offsets, 256
