@@ -216,6 +216,34 @@ int         scs_merge_fastq_shards(const char* prefix, int nranks, int paired, i
 /* host only: <prefix>.p*_1.fq ... -> <prefix>_1.fq ... (byte-range copies; parts removed unless keep_parts) */
 int         scs_merge_fastq_parts(const char* prefix, int paired, int keep_parts, char* errbuf, size_t errlen);
 
+/* ---- truth SAM: where every read came from --------------------------------------------------------------------------
+ * scs_set_truth_sam(ctx, path): the following yield calls also write each read's true alignment to `path` as plain-text SAM
+ * (NULL: off, the default).  Header: @HD VN:1.6 SO:unsorted, one @SQ per staged genome record (staging order), @PG ID:scssim.
+ * One record per FASTQ record, in FASTQ order (read 1 then its read 2): QNAME = the FASTQ name without '@' and /1 /2; FLAG
+ * 0x1|0x2|0x40/0x80 (+0x10 reverse, +0x20 mate reverse) for PE, 0 / 0x10 for SE; RNAME / POS in the staged (haplotype) records;
+ * MAPQ 255; CIGAR from the read's indel events (Profile::predict), genome-forward; RNEXT '=' / PNEXT / TLEN (+ on the leftmost
+ * read) for PE, '*' 0 0 for SE; SEQ / QUAL the FASTQ's, reverse-complemented / reversed for 0x10; NM:i and MD:Z against the
+ * staged record (amplification and sequencing errors alike).  The records are made on the GPU after each batch's reads and
+ * written by the sink's writer thread.  Applies to scs_yield_reads (any sink, NULL included), scs_yield_reads_files(_ex) with
+ * writers <= 1 and scs_run_genreads; a sharded ctx, writers > 1 and scs_yield_reads_device fail with SCS_EINVAL.
+ * scs_truth_bytes: SAM bytes of the last yield call (header included). */
+int         scs_set_truth_sam(scs_ctx* ctx, const char* path);
+int         scs_truth_bytes(const scs_ctx* ctx, uint64_t* bytes);
+/* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
+ * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
+int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);
+/* Host-only test seam of the truth kernels: one read's SAM record through their formatter.  n = window length (the model's read
+ * length); pos0 = 0-based record coordinate of window base 0 (the rightmost base when reverse); events = nev triples {window
+ * position, deletion?, length} in read orientation, as Profile::predict draws them (a deletion clipped to the window end); the
+ * mate (PE) likewise; seq / qual = the FASTQ record's len bases and qualities; genome = the record's bases from coordinate
+ * genome_start on (genome_len of them, covering the read).  out receives the line with its newline (out may be NULL to ask for
+ * its size *n_out); SCS_EINVAL: not a valid alignment, SCS_EOVERFLOW: cap too small. */
+int         scs_truth_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                                   int64_t pos0, int reverse, const int32_t* events, int nev,
+                                   int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                                   const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
+                                   char* out, size_t cap, size_t* n_out);
+
 /* ---- kernel-level entry points (unit parity tests; same kernels as the pipeline) ------------ */
 
 /* char* Profile::predict(char* refSeq, int isRead1)  (lib/profile/Profile.cpp:1582-1697) for a batch:
@@ -287,10 +315,10 @@ int         scs_fasta_write_index(const char* fasta_path, char* errbuf, size_t e
 /* Per-kernel timing (HIP events recorded on the ctx stream around every launch, accumulated over the
  * last scs_amplify / scs_yield_reads call): name, launches, total milliseconds, and the units the
  * launches processed (amplicons created for the errscan kernels, read pairs for k_reads/k_indels,
- * templates for the two k_attach instances).  which = 0..5: k_errs<semi->full>, k_errs<frag->semi>, k_reads,
- * k_attach<semi>, k_indels, k_attach<frag>. */
+ * templates for the two k_attach instances).  which = 0..6: k_errs<semi->full>, k_errs<frag->semi>, k_reads,
+ * k_attach<semi>, k_indels, k_attach<frag>, k_truth (the truth SAM's sizing + scan and emit passes, two event pairs per batch). */
 int         scs_kernel_time(const scs_ctx* ctx, int which, const char** name, uint64_t* launches, double* ms, uint64_t* units);
-/* Which of the six kernels get their HIP event pairs: bit `which` of mask (default: all), and on which calls: every
+/* Which of the seven kernels get their HIP event pairs: bit `which` of mask (default: all), and on which calls: every
  * `every`-th scs_amplify / scs_yield_reads call counted from this call (default 1 = all).  Every event record is a
  * packet on the stream (about 6 us each on the latency-bound 1 Mb configuration), so a measurement run times only the
  * kernel of interest, on a sample of the steps.  scs_kernel_time reports an untimed call as 0 launches / 0 units. */

@@ -225,6 +225,33 @@ def devbuf_probe(first_bytes, second_bytes, device=0):
     return caps[0], caps[1], bool(same.value)
 
 
+def truth_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, genome_start=0, rname="chr", amp=0, cnt=1,
+                       paired=False, is_read2=False, mate=None):
+    """Host-only: one read's truth SAM line (with its newline) through the formatter the truth kernels run.  n = window length;
+    pos0 = 0-based record coordinate of window base 0 (the rightmost base when reverse); events = [(window position, deletion?,
+    length), ...] in read orientation; seq / qual = the FASTQ record's; genome = the record's bases from genome_start on;
+    mate = (pos0, reverse, events) of the other read of a pair (paired=True)."""
+    L = load_library()
+    L.scs_truth_record_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int64, C.c_uint64,
+                                         C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    enc = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+    seq, qual, genome = enc(seq), enc(qual), enc(genome)
+    ev = lambda es: (C.c_int32 * max(1, 3 * len(es)))(*[int(v) for e in es for v in e])
+    m_pos, m_rev, m_ev = mate if mate is not None else (0, False, ())
+    args = [int(paired), int(is_read2), amp, cnt, enc(rname), n, pos0, int(reverse), ev(events), len(events),
+            m_pos, int(m_rev), ev(m_ev), len(m_ev), seq, qual, len(seq), genome, genome_start, len(genome)]
+    size = C.c_size_t()
+    rc = L.scs_truth_record_probe(*args, None, 0, C.byref(size))
+    if rc:
+        raise ScsError(rc, "scs_truth_record_probe: not a valid alignment")
+    out = C.create_string_buffer(size.value)
+    rc = L.scs_truth_record_probe(*args, out, size.value, C.byref(size))
+    if rc:
+        raise ScsError(rc, "scs_truth_record_probe")
+    return out.raw[:size.value].decode()
+
+
 def fasta_probe(path):
     """Host-only: (names, total bases, FNV-1a checksum of the upper-cased sequence) as the library stages the file."""
     L = load_library()
@@ -287,7 +314,7 @@ class GenReads:
     """One `scssim genreads` job on one MI355X.  Mirrors the reference's driver (src/scssim.cpp:46-67)."""
 
     def __init__(self, profile=None, input_fasta=None, primers=100000, gamma=1e-9, coverage=5.0, isize=260,
-                 layout="PE", seed=1, device=0, stream=None, shard_rank=0, shard_count=1, verbose=False):
+                 layout="PE", seed=1, device=0, stream=None, shard_rank=0, shard_count=1, verbose=False, ber=3.4e-4):
         import numpy as np
         self._np = np
         self._L = load_library()
@@ -296,6 +323,7 @@ class GenReads:
         self._L.scs_default_config(C.byref(cfg))
         cfg.device, cfg.stream, cfg.seed = device, stream, seed
         cfg.primers, cfg.gamma, cfg.coverage, cfg.isize = primers, gamma, coverage, isize
+        cfg.ber = ber                         # amplification error rate per base (Config "ber"); 0: no amplification errors
         if layout not in ("PE", "SE"):
             raise ValueError("Error: sequence layout incorrectly specified!")
         cfg.paired = 1 if layout == "PE" else 0
@@ -450,6 +478,28 @@ class GenReads:
         else:
             open(prefix + ".fq", "wb").write(fq1)
 
+    def set_truth_sam(self, path):
+        """The following yield calls also write each read's true alignment to `path` as SAM (None: off).  One GPU, one writer."""
+        self._L.scs_set_truth_sam.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_set_truth_sam(self._ctx, os.fsencode(path) if path is not None else None))
+
+    def truth_bytes(self):
+        """Bytes of the truth SAM the last yield call wrote (header included)."""
+        self._L.scs_truth_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        n = C.c_uint64()
+        self._ck(self._L.scs_truth_bytes(self._ctx, C.byref(n)))
+        return n.value
+
+    def download_frags(self):
+        """The fragments of create_frags: genome offset (records concatenated in staging order), length, strand (+1 / -1)."""
+        np = self._np
+        n = self.stats()["fragments"]
+        goff, ln, st = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.int8)
+        self._L.scs_download_frags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        ptr = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._ck(self._L.scs_download_frags(self._ctx, ptr(goff), ptr(ln), ptr(st)))
+        return dict(goff=goff, len=ln, strand=st)
+
     def set_batch_checksums(self, on=True):
         """Every batch of the following yield_reads* calls gets a 64-bit checksum per mate, computed on the device."""
         self._L.scs_set_batch_checksums.argtypes = [C.c_void_p, C.c_int]
@@ -482,10 +532,10 @@ class GenReads:
             out[name.value.decode()] = dict(launches=n.value, ms=ms.value, units=units.value)
         return out
 
-    KERNELS = ("k_errs<semi->full>", "k_errs<frag->semi>", "k_reads", "k_attach<semi>", "k_indels", "k_attach<frag>")
+    KERNELS = ("k_errs<semi->full>", "k_errs<frag->semi>", "k_reads", "k_attach<semi>", "k_indels", "k_attach<frag>", "k_truth")
 
     def set_kernel_timing(self, names=None, every=1):
-        """Keep HIP event pairs only around the named kernels (None = all six), on every `every`-th amplify / yield call.
+        """Keep HIP event pairs only around the named kernels (None = all seven), on every `every`-th amplify / yield call.
         Every event record is a packet on the stream (about 6 us each on the latency-bound 1 Mb job)."""
         mask = (1 << len(self.KERNELS)) - 1 if names is None else sum(1 << self.KERNELS.index(n) for n in names)
         self._ck(self._L.scs_set_kernel_timing(self._ctx, mask, every))

@@ -10,6 +10,7 @@
 #include "scs_tables.h"
 #include "scs_comm.h"
 #include "scs_bgzf.h"
+#include "scs_truth.h"
 
 #include <atomic>
 #include <fcntl.h>
@@ -192,6 +193,11 @@ struct scs_ctx {
     // blocks' total per batch reaches the host through a small pinned array (h_z) behind an event, one batch late (see do_yield)
     DevBuf z_plan[2], z_sizes[2], z_offs[2], z_out[2][2], z_crc; uint32_t* h_z = nullptr; hipEvent_t ev_z[2] = {nullptr, nullptr};
     bool want_cks = false; DevBuf d_cks; std::vector<uint64_t> cks;   // scs_set_batch_checksums: per batch and mate, computed where the text lies in HBM
+    // truth SAM (scs_set_truth_sam): the path (empty: off), per batch the pairs' SAM sizes and 64-bit offsets, two output buffers (the
+    // batch's text crosses PCIe on the copy stream while the next batch is made), the record table the kernels name records from,
+    // and the batch's total, read back through a pinned word behind ev_t
+    std::string truth_path; uint64_t truth_bytes = 0;
+    DevBuf t_sizes, t_offs, t_scan, t_out[2], t_recs; uint64_t* h_t = nullptr; hipEvent_t ev_t = nullptr;
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     hipStream_t pre_stream = nullptr; hipEvent_t ev_pre[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_plan = nullptr;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)
@@ -240,7 +246,7 @@ struct scs_ctx {
         HIP_OK(hipMemcpyAsync(d_recv, all.data(), all.size(), hipMemcpyHostToDevice, stream)); HIP_OK(hipStreamSynchronize(stream));
     }
     scs_stats st{};
-    KernelTimer tm_errscan{"k_errs<semi->full>"}, tm_errscan_f{"k_errs<frag->semi>"}, tm_reads{"k_reads"}, tm_attach{"k_attach<semi>"}, tm_indels{"k_indels"}, tm_attach_f{"k_attach<frag>"};
+    KernelTimer tm_errscan{"k_errs<semi->full>"}, tm_errscan_f{"k_errs<frag->semi>"}, tm_reads{"k_reads"}, tm_attach{"k_attach<semi>"}, tm_indels{"k_indels"}, tm_attach_f{"k_attach<frag>"}, tm_truth{"k_truth"};
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
@@ -280,10 +286,13 @@ struct CallbackSink : BatchSink {           // a caller's scs_sink_fn as a Batch
 };
 struct OutTarget { bool device; char* d1; char* d2; size_t cap1, cap2; BatchSink* sink;
                    std::vector<uint64_t>* seg_off1 = nullptr; std::vector<uint64_t>* seg_off2 = nullptr;
-                   bool bgzf = false; };                                          // bgzf: the sink gets BGZF blocks made on the device instead of the text   // seg_off: byte offset of each list segment's first record (shard index)
+                   bool bgzf = false;
+                   bool discard = false; };                                       // discard: the FASTQ text is not wanted on the host (a NULL sink with truth on)                                          // bgzf: the sink gets BGZF blocks made on the device instead of the text   // seg_off: byte offset of each list segment's first record (shard index)
 
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out);
 void sink_pipe_free(scs_ctx* c);            // releases and deletes c->pipe
+// truth SAM: refuses (SCS_EINVAL) the targets it does not apply to; device: scs_yield_reads_device, writers: the file sink's
+void truth_check(scs_ctx* c, bool device, int writers);
 std::vector<int> gpu_local_cpus(int device);
 
 template <class F>

@@ -104,8 +104,8 @@ struct AllocPlan {
 // local amplicon index -> index in the whole job's list (the number printed in the record name); n == 0: identity
 struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned long long go[ALLOC_SLOTS]; };
 
-// error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16 };
+// error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -233,5 +233,18 @@ void exclusive_scan_u32_pair(hipStream_t s, const uint32_t* in0, uint32_t* out0,
 #define OFF_MASK ((1ull << OFF_BITS) - 1ull)
 void exclusive_scan_sizes(hipStream_t s, const uint32_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes);
 void exclusive_scan_u32_to_u64(hipStream_t s, const uint32_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes);
+
+// ---- truth SAM of a batch (scs_k_truth.hip): sizing pass -> 64-bit offsets -> emit pass, after the batch's k_reads
+struct TruthArgs {
+    const PairRec* pairs; uint32_t np; int paired;
+    const uint32_t* ev_hdr; const uint4* ev_dat;           // the batch's indel pass
+    const uint64_t* off1; const uint64_t* off2; const char* fq1; const char* fq2;   // its FASTQ text and record offsets (OFF_MASK)
+    const uint8_t* g;                                      // the byte genome
+    const uint64_t* rec_off; const uint32_t* name_off; const char* names; uint32_t n_rec;   // record starts (n_rec + 1), names
+    DevTables tb; RngKey key; uint32_t slot; uint32_t* flags;
+};
+void launch_truth_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);                 // SAM bytes per pair (both mates); offsets: exclusive_scan_u32_to_u64
+uint32_t truth_pairs_per_block(uint64_t fq_bytes, uint32_t np);                             // the emit pass' LDS run, from the batch's FASTQ bytes
+void launch_truth_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, char* out);
 
 }  // namespace scs

@@ -43,6 +43,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_READSLOT) m += " read slot (indel-extended read longer than the slot)";
         if (f & FLAG_INTERNAL) m += " internal";
         if (f & FLAG_KEYSPACE) m += " primer budget of a fragment beyond 2^20 (-p / -r far outside the reference's ranges)";
+        if (f & FLAG_TRUTH) m += " truth SAM (a read with more than 32 indel events, or pair flags that are not a strand)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }
@@ -81,7 +82,7 @@ int scs_create(const scs_config* cfg, scs_ctx** out) {
         HIP_OK(hipSetDevice(cfg->device));
         if (cfg->stream) c->stream = (hipStream_t)cfg->stream; else { HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
         c->key = RngKey{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32)};
-        for (KernelTimer* t : {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f}) t->gate = &c->timing_gate;
+        for (KernelTimer* t : {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f, &c->tm_truth}) t->gate = &c->timing_gate;
         c->flags.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->flags.p, 0, 256, c->stream));
         c->dsums.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->dsums.p, 0, 256, c->stream));
         c->d_tot.reserve(256, c->stream);
@@ -100,7 +101,8 @@ void scs_destroy(scs_ctx* c) {
                       &c->d_isize, &c->d_gcmeans, &c->genome, &c->genome2, &c->gx_gc_bits, &c->gx_n_bits, &c->gx_gc_cnt, &c->gx_n_cnt, &c->gx_gc_pref, &c->gx_n_pref, &c->gx_gc_pair, &c->d_binom, &c->df_blob, &c->df_primers, &c->df_hasn, &c->primer_cnt, &c->primer_delta, &c->primer_cut, &c->primer_gdelta, &c->st_eidx, &c->st_etype, &c->st_estart, &c->st_info, &c->st_list, &c->st_sorted, &c->st_tmp, &c->att_wave_first,
                       &c->slots, &c->slot_tmpl, &c->slots_fr, &c->slot_tmpl_fr, &c->valid, &c->valid_off, &c->valid_f, &c->valid_off_f, &c->scan_tmp, &c->flags, &c->weights, &c->read_numbers,
                       &c->pair_off, &c->pairs, &c->odd_before, &c->a_part, &c->a_tp, &c->a_probs, &c->a_quota, &c->a_poff, &c->a_plan, &c->a_crn, &c->a_scratch, &c->a_brow, &c->a_bmap, &c->a_send, &c->a_gath, &c->a_odd, &c->d_hostred, &c->d_tot, &c->d_stage, &c->d_mail, &c->budget_f, &c->budget_s, &c->poisson_part, &c->slot_off_f,
-                      &c->slot_off_s, &c->dsums, &c->slot_b, &c->slot_q, &c->lens, &c->ev_hdr, &c->ev_dat, &c->sizes1, &c->sizes2, &c->off1, &c->off2, &c->out1, &c->out2, &c->out1b, &c->out2b, &c->rl_cls, &c->rl_pos, &c->rl_lists, &c->d_bounds, &c->d_cks}) b->release();
+                      &c->slot_off_s, &c->dsums, &c->slot_b, &c->slot_q, &c->lens, &c->ev_hdr, &c->ev_dat, &c->sizes1, &c->sizes2, &c->off1, &c->off2, &c->out1, &c->out2, &c->out1b, &c->out2b, &c->rl_cls, &c->rl_pos, &c->rl_lists, &c->d_bounds, &c->d_cks, &c->t_sizes, &c->t_offs, &c->t_scan, &c->t_out[0], &c->t_out[1], &c->t_recs}) b->release();
+    if (c->h_t) (void)hipHostFree(c->h_t); if (c->ev_t) (void)hipEventDestroy(c->ev_t);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->errs_stream) { (void)hipStreamDestroy(c->errs_stream); (void)hipEventDestroy(c->ev_att); (void)hipEventDestroy(c->ev_errs); }
     if (c->pre_stream) { (void)hipStreamDestroy(c->pre_stream); (void)hipEventDestroy(c->ev_plan); for (int k = 0; k < 2; ++k) { (void)hipEventDestroy(c->ev_pre[k]); (void)hipEventDestroy(c->ev_free[k]); } }
@@ -109,7 +111,7 @@ void scs_destroy(scs_ctx* c) {
     for (int k = 0; k < 2; ++k) { c->z_plan[k].release(); c->z_sizes[k].release(); c->z_offs[k].release(); c->z_out[k][0].release(); c->z_out[k][1].release(); if (c->ev_z[k]) (void)hipEventDestroy(c->ev_z[k]); }
     c->z_crc.release(); if (c->h_z) (void)hipHostFree(c->h_z);
     c->semis.release(); c->fulls.release();
-    for (KernelTimer* t : {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f}) t->release();
+    for (KernelTimer* t : {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f, &c->tm_truth}) t->release();
     if (c->h_rb) (void)hipHostFree(c->h_rb);
     if (c->h_frag) (void)hipHostFree(c->h_frag);
     sink_pipe_free(c);
@@ -208,15 +210,20 @@ int scs_simuvars(scs_ctx* c, const char* ref_fasta, const char* snp_file, const 
 int scs_create_frags(scs_ctx* c) { return guarded(c, [&] { double t = now_s(); do_create_frags(c); c->st.t_stage[1] = now_s() - t; }); }
 int scs_amplify(scs_ctx* c) { return guarded(c, [&] { double t = now_s(); do_amplify(c); c->st.t_stage[2] = now_s() - t; }); }
 int scs_allocate_reads(scs_ctx* c, uint64_t reads) { return guarded(c, [&] { do_allocate(c, reads); }); }
+static int discard_sink(void*, const char*, size_t, const char*, size_t) { return 0; }
 int scs_yield_reads(scs_ctx* c, scs_sink_fn sink, void* user) {
     return guarded(c, [&] {
-        double t = now_s(); CallbackSink cb(sink, user);
-        OutTarget tg{false, nullptr, nullptr, 0, 0, sink ? &cb : nullptr}; do_yield(c, tg, nullptr, nullptr, nullptr); c->st.t_stage[5] = now_s() - t;
+        truth_check(c, false, 1);
+        // with truth on, a NULL sink still takes the sink path: the SAM needs its writer; the FASTQ text stays on the device
+        double t = now_s(); CallbackSink cb(sink ? sink : discard_sink, user);
+        OutTarget tg{false, nullptr, nullptr, 0, 0, (sink || !c->truth_path.empty()) ? &cb : nullptr}; tg.discard = !sink;
+        do_yield(c, tg, nullptr, nullptr, nullptr); c->st.t_stage[5] = now_s() - t;
     });
 }
 int scs_yield_reads_device(scs_ctx* c, void* d1, size_t cap1, void* d2, size_t cap2, uint64_t* n1, uint64_t* n2, uint64_t* pairs) {
     return guarded(c, [&] {
         if (!d1 || (c->cfg.paired && !d2)) throw ScsError(SCS_EINVAL, "scs_yield_reads_device: null output buffer");
+        truth_check(c, true, 1);
         double t = now_s(); OutTarget tg{true, (char*)d1, (char*)d2, cap1, cap2, nullptr}; do_yield(c, tg, n1, n2, pairs); c->st.t_stage[5] = now_s() - t;
     });
 }
@@ -229,6 +236,7 @@ int scs_yield_reads_files_ex(scs_ctx* c, const char* prefix, int writers, int ge
         if (flags & ~(SCS_SINK_BGZF | SCS_SINK_IN_PLACE)) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: unknown sink flag");
         if (!prefix || !*prefix) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: no output prefix");
         if (writers > 64 || generations > 64 || (int64_t)std::max(1, writers) * std::max(1, generations) > 99) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: at most 64 writers and 99 parts");
+        truth_check(c, false, writers);
         const bool pe = c->cfg.paired != 0, shard = c->cfg.shard_count > 1; const std::string pre = prefix;
         const std::string base = shard ? shard_base(pre, c->cfg.shard_rank) : pre;
         FastqParts files; std::string err;
@@ -311,18 +319,67 @@ int scs_batch_checksums(const scs_ctx* c, uint64_t* out, size_t cap, size_t* n_b
 }
 int scs_get_stats(const scs_ctx* c, scs_stats* out) { if (!c || !out) return SCS_EINVAL; *out = c->st; return SCS_OK; }
 
+int scs_set_truth_sam(scs_ctx* c, const char* path) { if (!c) return SCS_EINVAL; c->truth_path = path ? path : ""; return SCS_OK; }
+int scs_truth_bytes(const scs_ctx* c, uint64_t* bytes) { if (!c || !bytes) return SCS_EINVAL; *bytes = c->truth_bytes; return SCS_OK; }
+int scs_download_frags(scs_ctx* c, uint64_t* goff, uint32_t* len, int8_t* strand) {
+    return guarded(c, [&] {
+        if (!c->have_frags) throw ScsError(SCS_EINVAL, "scs_download_frags: call scs_create_frags first");
+        const size_t n = c->f_len.size();
+        if (goff && n) memcpy(goff, c->f_goff.data(), n * 8);
+        if (len && n) memcpy(len, c->f_len.data(), n * 4);
+        if (strand && n) memcpy(strand, c->f_strand.data(), n);
+    });
+}
+// host-only: one read's record through the formatter the truth kernels run (scs_truth.h)
+int scs_truth_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                           int64_t pos0, int reverse, const int32_t* events, int nev,
+                           int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                           const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
+                           char* out, size_t cap, size_t* n_out) {
+    if (!rname || !seq || !qual || !genome || !n_out || n <= 0 || nev < 0 || mate_nev < 0 || (nev && !events) || (paired && mate_nev && !mate_events)) return SCS_EINVAL;
+    auto pack = [](const int32_t* e, int k, std::vector<uint32_t>& v) {
+        for (int i = 0; i < k; ++i) {
+            if (e[3 * i] < 0 || e[3 * i] > 0xFFFF || e[3 * i + 2] <= 0 || e[3 * i + 2] > 0x7FFF) return false;
+            v.push_back(tev_pack((uint32_t)e[3 * i], e[3 * i + 1] ? 1u : 0u, (uint32_t)e[3 * i + 2]));
+        }
+        return true;
+    };
+    std::vector<uint32_t> e1, e2;
+    if (!pack(events, nev, e1) || (paired && !pack(mate_events, mate_nev, e2))) return SCS_EINVAL;
+    TruthAln a{pos0, reverse ? 1 : 0, n, nev, e1.data(), 0, 0, 0}, m{mate_pos0, mate_reverse ? 1 : 0, n, mate_nev, e2.data(), 0, 0, 0};
+    if (!truth_place(a) || a.qlen != len || (paired && !truth_place(m))) return SCS_EINVAL;
+    if (a.lo < genome_start || a.hi >= genome_start + (int64_t)genome_len) return SCS_EINVAL;
+    TruthLine li{amp, cnt, 0u, paired ? 1 : 0, rname, (uint32_t)strlen(rname), 0, 0, 0};
+    if (paired) {
+        const int64_t left = std::min(a.lo, m.lo), right = std::max(a.hi, m.hi), t = right - left + 1;
+        li.flag = 0x3u | (is_read2 ? 0x80u : 0x40u) | (a.rev ? 0x10u : 0u) | (m.rev ? 0x20u : 0u);
+        li.mate_lo = m.lo;
+        li.tlen = (a.lo < m.lo || (a.lo == m.lo && !is_read2)) ? t : -t;   // positive on the leftmost read (read 1 on a tie, as the kernels)
+    } else li.flag = a.rev ? 0x10u : 0u;
+    struct Src {
+        const char* s; const char* q; const char* g; int64_t g0;
+        char seq(int i) const { return s[i]; } char qual(int i) const { return q[i]; }
+        char gen(int64_t x) const { const char ch = g[x - g0]; return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' ? ch : ch == 'a' ? 'A' : ch == 'c' ? 'C' : ch == 'g' ? 'G' : ch == 't' ? 'T' : 'N'; }
+    } src{seq, qual, genome, genome_start};
+    struct VecOut { std::string t; void put(char ch) { t.push_back(ch); } } o;
+    truth_record(o, a, li, src);
+    *n_out = o.t.size();
+    if (out) { if (o.t.size() > cap) return SCS_EOVERFLOW; memcpy(out, o.t.data(), o.t.size()); }
+    return SCS_OK;
+}
+
 int scs_kernel_time(const scs_ctx* c, int which, const char** name, uint64_t* launches, double* ms, uint64_t* units) {
     if (!c) return SCS_EINVAL;
-    const KernelTimer* t[] = {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f};
-    if (which < 0 || which >= 6) return SCS_EINVAL;
+    const KernelTimer* t[] = {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f, &c->tm_truth};
+    if (which < 0 || which >= 7) return SCS_EINVAL;
     if (name) *name = t[which]->name; if (launches) *launches = t[which]->launches; if (ms) *ms = t[which]->ms; if (units) *units = t[which]->units;
     return SCS_OK;
 }
 
 int scs_set_kernel_timing(scs_ctx* c, unsigned mask, unsigned every) {
     if (!c || every == 0) return SCS_EINVAL;
-    KernelTimer* t[] = {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f};
-    for (int i = 0; i < 6; ++i) t[i]->on = (mask >> i) & 1u;
+    KernelTimer* t[] = {&c->tm_errscan, &c->tm_errscan_f, &c->tm_reads, &c->tm_attach, &c->tm_indels, &c->tm_attach_f, &c->tm_truth};
+    for (int i = 0; i < 7; ++i) t[i]->on = (mask >> i) & 1u;
     c->timing_every = every; c->amplify_calls = 0; c->yield_calls = 0;
     return SCS_OK;
 }

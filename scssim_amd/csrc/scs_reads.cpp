@@ -1,5 +1,6 @@
 // scs_reads.cpp -- Malbac::setReadCounts and Malbac::yieldReads on the device, and the FASTQ sink (SeqWriter's replacement)
 #include "scs_ctx.h"
+#include <cerrno>
 
 namespace scs {
 // ---------------------------------------------------------------- a8 + a9: Malbac::setReadCounts (Malbac.cpp:370-408) on the device
@@ -162,12 +163,17 @@ struct NumaScope {
 
 struct SinkPipe {
     std::vector<int> local_cpus;                                                   // of the device's NUMA node (gpu_local_cpus)
-    struct Slot { char* h[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0}; hipEvent_t ev = nullptr; bool busy = false; };
-    struct Job { int slot, region; size_t n1, n2; };
+    struct Slot { char* h[3] = {nullptr, nullptr, nullptr}; size_t cap[3] = {0, 0, 0}; hipEvent_t ev = nullptr; bool busy = false; };   // h[2]: the batch's truth SAM
+    struct Job { int slot, region; size_t n1, n2, n3; };
     struct Writer { std::thread th; std::vector<Job> q; };
     std::vector<Slot> slots; std::vector<Writer> writers;
     std::mutex mu; std::condition_variable cv; bool done = false, failed = false;
     BatchSink* sink = nullptr; bool paired = true; int device = 0;
+    int truth_fd = -1;                                                             // the truth SAM (one writer: batch order), or -1
+    static bool write_all(int fd, const char* p, size_t n) {
+        while (n) { const ssize_t w = ::write(fd, p, n); if (w < 0 && errno == EINTR) continue; if (w <= 0) return false; p += w; n -= (size_t)w; }
+        return true;
+    }
     void start(BatchSink* f, bool pe, int dev) {
         sink = f; paired = pe; device = dev; done = failed = false;
         local_cpus = gpu_local_cpus(dev);
@@ -186,21 +192,23 @@ struct SinkPipe {
                 Slot& sl = slots[(size_t)j.slot];
                 bool bad = hipEventSynchronize(sl.ev) != hipSuccess;
                 if (!bad && !failed) bad = sink->put(j.region, sl.h[0], j.n1, paired ? sl.h[1] : nullptr, j.n2) != 0;
+                if (!bad && !failed && j.n3) bad = !write_all(truth_fd, sl.h[2], j.n3);
                 { std::lock_guard<std::mutex> lk(mu); sl.busy = false; if (bad) failed = true; }
                 cv.notify_all();
             }
         });
     }
     // a free pinned slot with room for the batch (blocks while every slot is with a writer); -1: the sink failed
-    int acquire(size_t need1, size_t need2) {
+    int acquire(size_t need1, size_t need2, size_t need3 = 0) {
         int k = -1;
         { std::unique_lock<std::mutex> lk(mu);
           cv.wait(lk, [&] { if (failed) return true; for (size_t i = 0; i < slots.size(); ++i) if (!slots[i].busy) { k = (int)i; return true; } return false; });
           if (failed) return -1;
           slots[(size_t)k].busy = true; }
         Slot& sl = slots[(size_t)k];
-        for (int f = 0; f < 2; ++f) {
-            const size_t need = f == 0 ? need1 : need2;
+        for (int f = 0; f < 3; ++f) {
+            const size_t need = f == 0 ? need1 : f == 1 ? need2 : need3;
+            if (f == 2 && need == 0) continue;
             if (need > sl.cap[f]) {
                 if (sl.h[f]) HIP_OK(hipHostFree(sl.h[f]));
                 sl.h[f] = nullptr; sl.cap[f] = 0;
@@ -211,16 +219,16 @@ struct SinkPipe {
         }
         return k;
     }
-    void submit(int region, int slot, size_t n1, size_t n2) { { std::lock_guard<std::mutex> lk(mu); writers[(size_t)region % writers.size()].q.push_back(Job{slot, region, n1, n2}); } cv.notify_all(); }
+    void submit(int region, int slot, size_t n1, size_t n2, size_t n3 = 0) { { std::lock_guard<std::mutex> lk(mu); writers[(size_t)region % writers.size()].q.push_back(Job{slot, region, n1, n2, n3}); } cv.notify_all(); }
     bool finish() { { std::lock_guard<std::mutex> lk(mu); done = true; } cv.notify_all(); for (auto& W : writers) if (W.th.joinable()) W.th.join(); writers.clear(); return !failed; }
-    void release() { for (auto& sl : slots) { for (int f = 0; f < 2; ++f) if (sl.h[f]) (void)hipHostFree(sl.h[f]); if (sl.ev) (void)hipEventDestroy(sl.ev); } slots.clear(); }
+    void release() { for (auto& sl : slots) { for (int f = 0; f < 3; ++f) if (sl.h[f]) (void)hipHostFree(sl.h[f]); if (sl.ev) (void)hipEventDestroy(sl.ev); } slots.clear(); }
 };
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out) {
     if (!c->allocated) throw ScsError(SCS_EINVAL, "scs_yield_reads: call scs_allocate_reads first");
     hipStream_t s = c->stream; const int paired = c->cfg.paired != 0;
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
-    c->tm_reads.reset(); c->tm_indels.reset();
+    c->tm_reads.reset(); c->tm_indels.reset(); c->tm_truth.reset();
     const uint64_t P = c->n_pairs_planned;
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
@@ -231,6 +239,8 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     HIP_OK(hipMemsetAsync(c->dsums.as<unsigned long long>() + DS_HOLES, 0, 8, s));
     const bool to_sink = !tg.device && tg.sink;
     const int regions = to_sink ? std::max(1, tg.sink->regions) : 1;
+    const bool truth = !c->truth_path.empty();
+    if (truth) { truth_check(c, tg.device, to_sink ? tg.sink->writers : 1); if (!to_sink) throw ScsError(SCS_EINVAL, "truth SAM: the reads must go to a sink"); }
     // pairs per batch: 8 M with the text staying in HBM (5 GB of text per batch: the base pass' grids are long enough for their tails and
     // the per-batch pre-pass not to matter: 2 M -> 8 M gave -11 % on the stage).  Towards a sink a batch fills a pinned slot and every
     // writer holds one: as large as leaves each part file of each generation a couple of batches -- 2 M pairs (1.3 GB of text) on a
@@ -269,10 +279,39 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         for (int r = g0; r < g1; ++r) { next[(size_t)(r - g0)] = (uint32_t)((uint64_t)nbatch * r / regions); end[(size_t)(r - g0)] = (uint32_t)((uint64_t)nbatch * (r + 1) / regions); left += end[(size_t)(r - g0)] - next[(size_t)(r - g0)]; }
         while (left) for (int r = g0; r < g1; ++r) if (next[(size_t)(r - g0)] < end[(size_t)(r - g0)]) { order.push_back(next[(size_t)(r - g0)]++); region_of.push_back((uint32_t)r); --left; }
     }
+    struct FdGuard { int fd = -1; ~FdGuard() { if (fd >= 0) ::close(fd); } } truth_fd;          // (closed after the pipe's writers have ended: declared first)
+    TruthArgs ta{}; uint64_t truth_sum = 0;
+    if (truth) {
+        // the header first, then the batches' records from the pipe's writer; the kernels' record table: starts, name offsets, names
+        truth_fd.fd = ::open(c->truth_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
+        if (truth_fd.fd < 0) throw ScsError(SCS_EIO, "truth SAM: can not open " + c->truth_path + ": " + strerror(errno));
+        std::string hd = "@HD\tVN:1.6\tSO:unsorted\n";
+        const uint32_t nr = (uint32_t)c->recs.size();
+        std::vector<uint64_t> roff(nr + 1, 0); std::vector<uint32_t> noff(nr + 1, 0); std::string names;
+        for (uint32_t r = 0; r < nr; ++r) {
+            hd += "@SQ\tSN:" + c->recs[r].name + "\tLN:" + std::to_string(c->rec_len[r]) + "\n";
+            roff[r] = c->rec_off[r]; roff[r + 1] = c->rec_off[r] + c->rec_len[r];
+            names += c->recs[r].name; noff[r + 1] = (uint32_t)names.size();
+        }
+        hd += "@PG\tID:scssim\tPN:scssim\n";
+        if (!SinkPipe::write_all(truth_fd.fd, hd.data(), hd.size())) throw ScsError(SCS_EIO, "truth SAM: writing " + c->truth_path + " failed");
+        truth_sum = hd.size();
+        const size_t o_name = (size_t)(nr + 1) * 8, o_text = o_name + (size_t)(nr + 1) * 4;
+        std::vector<uint8_t> blob(o_text + names.size() + 16, 0);
+        memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nr + 1) * 4); memcpy(blob.data() + o_text, names.data(), names.size());
+        upload(c->t_recs, blob, s);
+        c->t_sizes.reserve((batch + 1) * 4, s); c->t_offs.reserve((batch + 1) * 8, s); c->t_scan.reserve(scan_temp_bytes(batch), s);
+        if (!c->h_t) { HIP_OK(hipHostMalloc((void**)&c->h_t, 64, hipHostMallocDefault)); HIP_OK(hipEventCreateWithFlags(&c->ev_t, hipEventDisableTiming | hipEventBlockingSync)); }
+        HIP_OK(hipStreamSynchronize(s));                                           // (the host blob goes)
+        const uint8_t* tb = c->t_recs.as<uint8_t>();
+        ta.g = c->genome.as<uint8_t>(); ta.rec_off = (const uint64_t*)tb; ta.name_off = (const uint32_t*)(tb + o_name); ta.names = (const char*)(tb + o_text); ta.n_rec = nr;
+        ta.paired = paired; ta.tb = c->dtb; ta.key = c->key; ta.slot = slot; ta.flags = c->flags.as<uint32_t>();
+    }
     struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } } guard{nullptr};
     if (to_sink) {
         if (!c->pipe) c->pipe = new SinkPipe;
         if (!c->copy_stream) { HIP_OK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); for (int k = 0; k < 2; ++k) { HIP_OK(hipEventCreateWithFlags(&c->ev_made[k], hipEventDisableTiming)); HIP_OK(hipEventCreateWithFlags(&c->ev_d2h[k], hipEventDisableTiming)); } }
+        c->pipe->truth_fd = truth_fd.fd;
         c->pipe->start(tg.sink, paired != 0, c->cfg.device); guard.p = c->pipe;
     }
     const bool bgzf = to_sink && tg.bgzf;
@@ -352,20 +391,21 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     }
     bool d2h_rec[2] = {false, false};
     uint64_t sunk1 = 0, sunk2 = 0;                                                  // bytes handed to the sink (= the text's, or its BGZF blocks')
-    struct Ship { char* p1; char* p2; uint64_t n1, n2; int dsl; uint32_t region; };
+    struct Ship { char* p1; char* p2; uint64_t n1, n2; int dsl; uint32_t region; char* p3; uint64_t n3; };   // p3 / n3: the batch's truth SAM
     Ship pending{}; bool have_pending = false;
     auto ship = [&](Ship sh) {                                                      // D2H on the copy stream into a free pinned slot, then to the region's writer
         SinkPipe* pp = c->pipe;
         if (bgzf) { HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl])); sh.n1 = c->h_z[sh.dsl * 2]; sh.n2 = c->h_z[sh.dsl * 2 + 1]; }   // the blocks' totals have arrived
-        const int hs = pp->acquire(sh.n1, sh.n2);                                   // (a pinned slot no writer holds: the host waits here when the sink is the slower side)
+        const int hs = pp->acquire(sh.n1, sh.n2, sh.n3);                                   // (a pinned slot no writer holds: the host waits here when the sink is the slower side)
         if (hs < 0) throw ScsError(SCS_EIO, "sink aborted");
         SinkPipe::Slot& H = pp->slots[(size_t)hs];
         HIP_OK(hipStreamWaitEvent(c->copy_stream, c->ev_made[sh.dsl], 0));          // ... and crosses PCIe on the copy stream, beside the next batch's kernels
         if (sh.n1) HIP_OK(hipMemcpyAsync(H.h[0], sh.p1, sh.n1, hipMemcpyDeviceToHost, c->copy_stream));
         if (sh.n2) HIP_OK(hipMemcpyAsync(H.h[1], sh.p2, sh.n2, hipMemcpyDeviceToHost, c->copy_stream));
+        if (sh.n3) HIP_OK(hipMemcpyAsync(H.h[2], sh.p3, sh.n3, hipMemcpyDeviceToHost, c->copy_stream));
         HIP_OK(hipEventRecord(H.ev, c->copy_stream));
         HIP_OK(hipEventRecord(c->ev_d2h[sh.dsl], c->copy_stream)); d2h_rec[sh.dsl] = true;
-        pp->submit((int)sh.region, hs, sh.n1, sh.n2);
+        pp->submit((int)sh.region, hs, sh.n1, sh.n2, sh.n3);
         sunk1 += sh.n1; sunk2 += sh.n2;
     };
     c->cks.clear();
@@ -416,10 +456,33 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             launch_text_checksum(s, o1, b1, c->d_cks.as<unsigned long long>() + 2 * (size_t)bidx);
             launch_text_checksum(s, o2, paired ? b2 : 0, c->d_cks.as<unsigned long long>() + 2 * (size_t)bidx + 1);
         }
+        char* t_text = nullptr; uint64_t t_n = 0;
+        if (truth) {
+            // the batch's SAM: sizing pass + 64-bit offsets, the total to the host (it sizes the output), emit pass.  Before ev_free: the
+            // passes read the batch's indel events and record offsets
+            ta.pairs = pr; ta.np = np; ta.ev_hdr = B.ev_hdr; ta.ev_dat = B.ev_dat; ta.off1 = B.off1; ta.off2 = B.off2; ta.fq1 = o1; ta.fq2 = o2;
+            c->tm_truth.begin(s);
+            launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
+            exclusive_scan_u32_to_u64(s, c->t_sizes.as<uint32_t>(), c->t_offs.as<uint64_t>(), np, c->t_scan.p, c->t_scan.cap);
+            HIP_OK(hipMemcpyAsync(c->h_t, c->t_offs.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, s));
+            HIP_OK(hipEventRecord(c->ev_t, s));
+            c->tm_truth.end(s);
+            HIP_OK(hipEventSynchronize(c->ev_t));
+            { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("truth sizing pass failed: ") + hipGetErrorString(le)); }
+            t_n = *c->h_t;
+            DevBuf& to = c->t_out[dsl];
+            if (std::max<uint64_t>(t_n, 16) > to.cap && d2h_rec[dsl]) HIP_OK(hipEventSynchronize(c->ev_d2h[dsl]));   // the buffer is about to move: its last copy must be out
+            to.reserve(std::max<uint64_t>(t_n + t_n / 16, 16), s);
+            c->tm_truth.begin(s);
+            launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(b1 + b2, np), to.as<char>());
+            c->tm_truth.end(s);
+            c->tm_truth.add_units(np);
+            t_text = to.as<char>(); truth_sum += t_n;
+        }
         if (ps != s) { HIP_OK(hipEventRecord(c->ev_free[it & 1], s)); free_rec[it & 1] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
         if (pp) {
-            Ship sh{o1, o2, b1, b2, dsl, region_of[it]};
+            Ship sh{o1, o2, tg.discard ? 0 : b1, tg.discard ? 0 : b2, dsl, region_of[it], t_text, t_n};
             if (bgzf) {
                 // the text becomes BGZF blocks where it lies: plan (code lengths, exact block sizes), prefix sum, emit at the final offsets.
                 // The blocks' total is only known on the device: it travels to a pinned word behind ev_z, and the batch is shipped ONE
@@ -459,11 +522,12 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     // (Amplicon.cpp:484-489): k_plan_pairs counted them on the device
     { Mail m; m.add(c->flags.p, 4, 30); m.add(c->dsums.as<unsigned long long>() + DS_HOLES, 8, 2); mail_post(c, m, true); }   // flags + hole count land before the final synchronize: no second round trip
     HIP_OK(hipStreamSynchronize(s));
-    if (to_sink) { HIP_OK(hipStreamSynchronize(c->copy_stream)); guard.p = nullptr; if (!c->pipe->finish()) throw ScsError(SCS_EIO, "sink aborted"); }
+    if (to_sink) { HIP_OK(hipStreamSynchronize(c->copy_stream)); guard.p = nullptr; const bool ok = c->pipe->finish(); c->pipe->truth_fd = -1; if (!ok) throw ScsError(SCS_EIO, truth ? "sink aborted (or the truth SAM could not be written)" : "sink aborted"); }
+    if (truth) { const int fd = truth_fd.fd; truth_fd.fd = -1; if (::close(fd) != 0) throw ScsError(SCS_EIO, "truth SAM: closing " + c->truth_path + " failed"); c->truth_bytes = truth_sum; }
     mail_wait(c); flags_eval(c);
     if (c->want_cks && !tg.device && nbatch) { c->cks.assign((size_t)nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
     pairs_written = P - c->h_rb[2];
-    c->tm_reads.collect(); c->tm_indels.collect();
+    c->tm_reads.collect(); c->tm_indels.collect(); c->tm_truth.collect();
     c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
     c->st.fastq_bytes[0] = tot1; c->st.fastq_bytes[1] = tot2;
     c->st.sink_bytes[0] = to_sink ? sunk1 : 0; c->st.sink_bytes[1] = to_sink ? sunk2 : 0;
@@ -473,6 +537,13 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     if (n1_out) *n1_out = tot1; if (n2_out) *n2_out = tot2; if (pairs_out) *pairs_out = pairs_written;
     if (seam_env("SCS_PHASE_CLOCK")) phase_clock_report();                         // (prints only in a -DSCS_PHASE_CLOCK build)
     if (c->cfg.verbose) fprintf(stderr, "\nReads generation done!\n");
+}
+
+void truth_check(scs_ctx* c, bool device, int writers) {
+    if (c->truth_path.empty()) return;
+    if (device) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): not available with scs_yield_reads_device; turn it off with scs_set_truth_sam(ctx, NULL)");
+    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): not available for a sharded job (shard_count > 1)");
+    if (writers > 1) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): needs writers <= 1 (part files are made out of record order)");
 }
 
 void sink_pipe_free(scs_ctx* c) { if (c->pipe) { c->pipe->release(); delete c->pipe; c->pipe = nullptr; } }

@@ -1,0 +1,145 @@
+// scs_truth.h -- the SAM record of a read's true alignment (scs_set_truth_sam).  One formatter for the
+// device passes (scs_k_truth.hip: sizing with a counting sink, emit into LDS) and the host probe (scs_truth_record_probe), so the
+// test seam runs the code the kernels run.
+//
+// A read's alignment comes from its indel events alone (Profile::predict, Profile.cpp:1605-1650): in read orientation the window
+// bases cur .. j of an insertion at j are M, then its k inserted bases I; a deletion of k bases at j is j - cur bases M, then k D
+// (already clipped to the window end).  Op 2 i is the M run before event i, op 2 i + 1 the event, op 2 nev the M run after the
+// last one, so the ops can be walked in either orientation without storing them.  The record is written genome-forward: a read
+// whose window runs backwards on the genome (bit 0x10) walks its ops from the last; D runs before the first M or after the last M
+// are dropped (POS moves past a leading one), equal neighbours merge, and an I at either end stays.
+#pragma once
+#include <stdint.h>
+#include "scs_common.h"
+
+namespace scs {
+
+#define TRUTH_EVCAP 32                                     // indel events per read the passes hold (more: FLAG_TRUTH, never a wrong record)
+
+// an event: window position | length << 16 | deletion << 31
+SCS_HD uint32_t tev_pack(uint32_t pos, uint32_t del, uint32_t len) { return pos | (len << 16) | (del << 31); }
+SCS_HD uint32_t tev_pos(uint32_t e) { return e & 0xFFFFu; }
+SCS_HD uint32_t tev_len(uint32_t e) { return (e >> 16) & 0x7FFFu; }
+SCS_HD uint32_t tev_del(uint32_t e) { return e >> 31; }
+SCS_HD uint32_t tev_end(uint32_t e) { return tev_pos(e) + (tev_del(e) ? tev_len(e) : 1u); }   // first window base after the event
+
+// one read: g0 = genome index of window base 0, rev = the window runs backwards (and complemented) on the genome
+struct TruthAln {
+    int64_t g0; int rev; int n; int nev; const uint32_t* ev;
+    int64_t lo, hi;                                        // leftmost / rightmost aligned genome index
+    int qlen;                                              // bases of the read (M + I)
+};
+
+// op k (read orientation) of 2 nev + 1: kind 'M', 'I' or 'D' and its length (an M run may be empty)
+SCS_HD void truth_op(const TruthAln& a, int k, char& kind, uint32_t& len) {
+    if (k & 1) { const uint32_t e = a.ev[k >> 1]; kind = tev_del(e) ? 'D' : 'I'; len = tev_len(e); return; }
+    const int i = k >> 1;
+    const uint32_t cur = i ? tev_end(a.ev[i - 1]) : 0u;
+    const uint32_t stop = i < a.nev ? tev_pos(a.ev[i]) + (tev_del(a.ev[i]) ? 0u : 1u) : (uint32_t)a.n;
+    kind = 'M'; len = stop - cur;
+}
+
+// checks the event list, applies the n + delta < 50 rollback (Profile.cpp:1623-1630; a no-op on the device's lists, which are
+// rolled back already) and places the read.  false: not a valid alignment
+SCS_HD bool truth_place(TruthAln& a) {
+    int delta = 0; uint32_t cur = 0;
+    for (int i = 0; i < a.nev; ++i) {
+        const uint32_t e = a.ev[i];
+        if (tev_pos(e) < cur || tev_len(e) == 0 || tev_end(e) > (uint32_t)a.n || (!tev_del(e) && tev_pos(e) >= (uint32_t)a.n)) return false;
+        delta += tev_del(e) ? -(int)tev_len(e) : (int)tev_len(e);
+        cur = tev_end(e);
+    }
+    if (a.n + delta < 50) { a.nev = 0; delta = 0; }
+    a.qlen = a.n + delta;
+    int first = -1, last = -1;                             // window bases of the first and the last M
+    for (int k = 0; k <= 2 * a.nev; k += 2) {
+        char kind; uint32_t len; truth_op(a, k, kind, len);
+        const uint32_t cur0 = (k >> 1) ? tev_end(a.ev[(k >> 1) - 1]) : 0u;
+        if (len) { if (first < 0) first = (int)cur0; last = (int)(cur0 + len - 1); }
+    }
+    if (first < 0) return false;
+    if (a.rev) { a.lo = a.g0 - last; a.hi = a.g0 - first; } else { a.lo = a.g0 + first; a.hi = a.g0 + last; }
+    return true;
+}
+
+// the CIGAR ops genome-forward, leading / trailing D dropped, neighbours of one kind merged: f(kind, len)
+template <class F>
+SCS_HD void truth_cigar_walk(const TruthAln& a, F f) {
+    char lk = 0; uint32_t ll = 0, pend_d = 0; bool seen_m = false;
+    auto push = [&](char k, uint32_t l) { if (k == lk) ll += l; else { if (lk) f(lk, ll); lk = k; ll = l; } };
+    const int nops = 2 * a.nev + 1;
+    for (int j = 0; j < nops; ++j) {
+        char kind; uint32_t len; truth_op(a, a.rev ? nops - 1 - j : j, kind, len);
+        if (!len) continue;
+        if (kind == 'D') { if (seen_m) pend_d += len; continue; }
+        if (pend_d) { push('D', pend_d); pend_d = 0; }
+        if (kind == 'M') seen_m = true;
+        push(kind, len);
+    }
+    if (lk) f(lk, ll);
+}
+
+SCS_HD char truth_comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
+
+template <class Out>
+SCS_HD void truth_num(Out& o, uint64_t v) {
+    char d[20]; int n = 0;
+    do { d[n++] = (char)('0' + v % 10u); v /= 10u; } while (v);
+    while (n) o.put(d[--n]);
+}
+template <class Out>
+SCS_HD void truth_snum(Out& o, int64_t v) { if (v < 0) { o.put('-'); truth_num(o, (uint64_t)(-v)); } else truth_num(o, (uint64_t)v); }
+
+// the rest of a record: who it is and where its mate lies
+struct TruthLine {
+    uint32_t amp, cnt, flag; int paired;
+    const char* rname; uint32_t rname_len; int64_t rec0;   // rec0: genome index of the record's first base
+    int64_t mate_lo; int64_t tlen;
+};
+
+// src: seq(i) / qual(i) = the FASTQ record's base / quality i (read orientation), gen(g) = genome base g as 'A' 'C' 'G' 'T' 'N'.
+// Writes the record with its newline through o.put(char).
+template <class Out, class Src>
+SCS_HD void truth_record(Out& o, const TruthAln& a, const TruthLine& li, const Src& src) {
+    const int q = a.qlen;
+    truth_num(o, li.amp); o.put('#'); truth_num(o, li.cnt); o.put('\t');
+    truth_num(o, li.flag); o.put('\t');
+    for (uint32_t i = 0; i < li.rname_len; ++i) o.put(li.rname[i]);
+    o.put('\t'); truth_num(o, (uint64_t)(a.lo - li.rec0 + 1)); o.put('\t');
+    o.put('2'); o.put('5'); o.put('5'); o.put('\t');
+    truth_cigar_walk(a, [&](char k, uint32_t l) { truth_num(o, l); o.put(k); });
+    o.put('\t');
+    if (li.paired) { o.put('='); o.put('\t'); truth_num(o, (uint64_t)(li.mate_lo - li.rec0 + 1)); o.put('\t'); truth_snum(o, li.tlen); }
+    else { o.put('*'); o.put('\t'); o.put('0'); o.put('\t'); o.put('0'); }
+    o.put('\t');
+    for (int i = 0; i < q; ++i) o.put(a.rev ? truth_comp(src.seq(q - 1 - i)) : src.seq(i));
+    o.put('\t');
+    for (int i = 0; i < q; ++i) o.put(src.qual(a.rev ? q - 1 - i : i));
+    // NM / MD against the genome: one walk counts, the second prints
+    uint32_t nm = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        int64_t g = a.lo; int qi = 0; uint32_t run = 0;
+        if (pass == 1) { o.put('\t'); o.put('N'); o.put('M'); o.put(':'); o.put('i'); o.put(':'); truth_num(o, nm); o.put('\t'); o.put('M'); o.put('D'); o.put(':'); o.put('Z'); o.put(':'); }
+        truth_cigar_walk(a, [&](char k, uint32_t l) {
+            if (k == 'I') { qi += (int)l; if (!pass) nm += l; return; }
+            if (k == 'D') {
+                if (!pass) { nm += l; g += l; return; }
+                truth_num(o, run); run = 0; o.put('^');
+                for (uint32_t t = 0; t < l; ++t) o.put(src.gen(g++));
+                return;
+            }
+            for (uint32_t t = 0; t < l; ++t, ++qi, ++g) {
+                const char r = a.rev ? truth_comp(src.seq(q - 1 - qi)) : src.seq(qi), gc = src.gen(g);
+                if (r == gc) { ++run; continue; }
+                if (!pass) ++nm; else { truth_num(o, run); o.put(gc); }
+                run = 0;
+            }
+        });
+        if (pass == 1) truth_num(o, run);
+    }
+    o.put('\n');
+}
+
+struct TruthCount { uint64_t n = 0; SCS_HD void put(char) { ++n; } };
+
+}  // namespace scs
