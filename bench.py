@@ -17,15 +17,17 @@ plain FASTQ through the library's file sink (scs_yield_reads_files_ex: D2H on a 
 to its own part file per mate, `--generations` generations) into fresh files on tmpfs.  `value` = pairs / that time: SURVEY 8(d)'s
 "records in _1.fq / wall".  The memory cgroup cannot hold two steps' text, so background threads unlink every part once it is
 final and a step's sink starts when <= 40 GB of older text are left -- inside the timed region.
-Beside it, at N = 1 and outside the timed region:
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs, the result line (with the timed region's own kernel
+times and k_reads roofline).  --full adds, outside the timed region (generation_hbm on every rank, the rest at N = 1):
   generation_hbm : 5 steps with a NULL sink (text generated batch by batch into HBM buffers and counted): what the kernels do
                    when nothing crosses PCIe; the dominant kernel's roofline is taken here (8 M pairs per launch);
   d2h_only       : one step through a sink that only counts: what PCIe allows;
   bgzf           : 2 steps with the text made into BGZF blocks ON THE GPU before it crosses PCIe (.fq.gz parts; an extension);
   sweep          : configs[1] (1 Mb) and configs[2]'s size (63 Mb) with the same model and options;
   cli_wall       : the `scssim genreads` binary end to end (FASTA parse, profile, job, files) at chr20 size (configs[2]);
-  cpu_baseline   : the reference itself (oracle/_ref/scssim_ref, compiled from /root/reference by oracle/Makefile) with
+  cpu_baseline   : the reference itself (oracle/_ref/scssim_ref, compiled from the reference's sources by oracle/Makefile) with
                    -t <cores> and -t 1 on bounded samples of the same genome; the oracle port beside it.
+--no-extra-legs and --no-cpu-baseline leave legs out of a --full run.
 --hbm-only times the steps with a NULL sink instead (round 2's headline; what tools/profile_bench.sh profiles).
 N > 1 (driver: torch.distributed.run, one rank per GPU): the SAME job sharded N ways by fragment lineage (strong
 scaling); per-pass primer-stock all-reduce and the allocation partials over RCCL; every rank writes its own FASTQ shard
@@ -649,13 +651,16 @@ def main():
     ap.add_argument("--cleaners", type=int, default=6, help="background threads that unlink finished part files")
     ap.add_argument("--out-dir", default="", help="where the timed steps write their FASTQ part files (default: a fresh directory on /dev/shm)")
     ap.add_argument("--hbm-only", action="store_true", help="time the steps with a NULL sink (text generated into HBM buffers, no files): the generation_hbm leg as the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the generation-only, D2H-only, small-configuration and CLI legs")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the legs beside the headline (generation only, D2H only, one job alone, "
+                    "in place, BGZF, small configurations, CLI wall, CPU baseline; see the module's docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the generation-only, D2H-only, small-configuration and CLI legs")
     ap.add_argument("--cpu-sample-mb", type=float, default=4.0)
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (see the module's docstring)")
     a = ap.parse_args()
     if a.dump_outputs and (a.gpus != 1 or a.steps < 1):
         ap.error("--dump-outputs needs --gpus 1 and at least one timed step")
+    extra_legs = a.full and not a.no_extra_legs
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus))                               # (this process never touches the GPU)
@@ -701,10 +706,10 @@ def main():
     t_up = time.perf_counter() - t_up
     # samples for the CPU / CLI legs come from the same genome: taken before it is released
     cpu_sample = cli_sample = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         n_cpu = min(rl[0], int(a.cpu_sample_mb * 1e6))
         cpu_sample = bases[:n_cpu].cpu().numpy()
-        if not a.no_extra_legs:
+        if extra_legs:
             i20 = 2 * 19 if len(rl) >= 40 else 0                     # chromosome 20 (configs[2]: chr20-size)
             o20 = sum(rl[:i20])
             cli_sample = bases[o20:o20 + rl[i20]].cpu().numpy()
@@ -863,7 +868,7 @@ def main():
     # ---- generation only (every rank takes part: the steps hold the job's collectives): the same job with a NULL sink -- the text is
     # written into HBM batch buffers (8 M pairs per launch) and counted.  What the kernels do when nothing has to cross PCIe; the
     # dominant kernel's roofline is taken here.
-    H = timed(1, 5, "null", 100) if not a.no_extra_legs and not a.hbm_only else None
+    H = timed(1, 5, "null", 100) if extra_legs and not a.hbm_only else None
 
     if rank == 0:
         L = g.read_length
@@ -928,7 +933,7 @@ def main():
                                              "lanes_per_valu_inst": {k: v["lanes_per_valu_inst"] for k, v in lanes.items() if k.startswith("k_attach") or k.startswith("k_errs")},
                                              "salu_per_valu": {k: v["salu_per_valu"] for k, v in lanes.items() if k.startswith("k_attach") or k.startswith("k_errs")}}
         out["roofline"] = roof
-        if world == 1 and not a.no_extra_legs and not a.hbm_only:
+        if world == 1 and extra_legs and not a.hbm_only:
             # ---- D2H only: the same batches through a sink that only counts -- what PCIe allows
             seen = [0]
 
@@ -1011,7 +1016,7 @@ def main():
                         out["cli_wall"] = {"error": r.stderr[-300:]}
                 finally:
                     shutil.rmtree(cd, ignore_errors=True)
-        if world == 1 and not a.no_cpu_baseline and cpu_sample is not None:
+        if world == 1 and a.full and not a.no_cpu_baseline and cpu_sample is not None:
             n = len(cpu_sample)
             out["cpu_baseline"] = cpu_baseline(td, prof, ["1_1_%d" % n, "1_2_%d" % n], [cpu_sample, cpu_sample],
                                                "first %.1f Mb of chromosome 1 of the bench genome (x 2 haplotypes), PE150 %gx, same profile and options" % (n / 1e6, a.coverage), a.coverage)

@@ -515,7 +515,7 @@ def test_bench_two_rank_control_flow(ranks, tmp_path):
     # (launch_ranks); 4 ranks: the driver's own command
     launcher = [] if ranks == 2 else ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
                                       "--master-port", str(29791 + ranks)]
-    r = subprocess.run([sys.executable] + launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--genome-mb", "4"],
+    r = subprocess.run([sys.executable] + launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--genome-mb", "4", "--full"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -531,11 +531,11 @@ def test_bench_two_rank_control_flow(ranks, tmp_path):
 
 
 def test_bench_single_gpu_contract(tmp_path):
-    """bench.py at N = 1 on a scaled-down genome: every leg runs (timed steps through the file sink, generation only, D2H only, the
+    """bench.py --full at N = 1 on a scaled-down genome: every leg runs (timed steps through the file sink, generation only, D2H only, the
     small configurations, CLI wall, CPU baseline at -t 1 and -t cores) and the JSON line carries the contract's fields."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--genome-mb", "6", "--cpu-sample-mb", "0.2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--genome-mb", "6", "--cpu-sample-mb", "0.2", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -553,6 +553,31 @@ def test_bench_single_gpu_contract(tmp_path):
     assert isinstance(d["sweep"], list) and len(d["sweep"]) == 2 and all(x["generation_hbm_pairs_per_s"] > 0 for x in d["sweep"])
     assert d["cli_wall"].get("value", 0) > 0, d["cli_wall"]
     assert abs(d["value"] - d["config"]["pairs_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.05
+
+
+def test_bench_plain_run_does_only_the_headline(tmp_path):
+    """bench.py without --full at N = 1: set-up, warm-up, the timed steps, --dump-outputs and the result line -- none of the legs
+    that --full adds -- and the line carries the headline's fields."""
+    import json
+    import sys
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--genome-mb", "6", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "roofline"):
+        assert k in d, k
+    assert d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - d["config"]["pairs_per_step"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.05
+    assert d["roofline"]["kernel"] == "k_reads" and d["roofline"]["timed_launches"] > 0 and "generation_hbm_leg" not in d["roofline"]
+    for k in ("generation_hbm", "roofline_amplification", "d2h_only", "single_job_on_empty_tmpfs", "files_overwritten_in_place", "bgzf", "sweep",
+              "two_file_layout", "cli_wall", "cpu_baseline"):
+        assert k not in d, k
+    counts = np.load(str(dump / "job_counts.npy"))
+    assert abs(counts[0] - d["config"]["pairs_per_step"]) < 0.05 * counts[0]                    # the last timed step's pairs
+    assert np.load(str(dump / "read1_bases.npy")).shape == (8192, 150 + 64)
 
 
 def test_medium_genome_bit_exact(oracle_bin, models, tmp_path):
