@@ -307,6 +307,24 @@ int         scs_devbuf_probe(int device, uint64_t first_bytes, uint64_t second_b
  * lds_out_cap (0 = the kernels' limit) -- run on the CPU over the same functions; out receives the BGZF blocks of the text
  * (no end-of-file block), *n_out their size (out may be NULL to ask for it).  The checker is zlib. */
 int         scs_bgzf_probe(const void* text, uint64_t nbytes, uint32_t lds_out_cap, void* out, uint64_t cap, uint64_t* n_out);
+/* Test seam of the BGZF kernels themselves (needs a GPU, touches no ctx, reads no environment variable): text[0..nbytes) is
+ * copied to a fresh device buffer -- 16-byte aligned, as the product's text buffers are -- and goes through exactly what a
+ * batch's mate goes through: the plan kernel, the one-workgroup exclusive scan of the block sizes (no scratch), the emit kernel
+ * with the tables of bgzf_host_tables, the blocks written from byte zbase (0..3) of a 4-byte aligned output buffer.  out
+ * receives the blocks (no end-of-file block), *n_out their size; cap >= nbytes + 31 per 64512-byte block is always enough
+ * (SCS_EOVERFLOW otherwise, with *n_out set).  The output buffer has at least 64 guard bytes below byte zbase (the bytes below
+ * zbase down to the dword boundary are guard too) and 64 behind the last block, filled with a fixed non-zero pattern before the
+ * launches: *guards_ok = 1 when every guard byte is untouched, 0 otherwise.  nbytes == 0: 0 bytes, nothing is launched.
+ * The stream is synchronised and hipGetLastError checked before any result is read; a device error is SCS_EDEVICE with its
+ * text in scs_last_error(NULL), as for scs_devbuf_probe.  The checkers are zlib and scs_bgzf_probe (byte for byte). */
+int         scs_bgzf_device_probe(int device, const void* text, uint64_t nbytes, uint32_t zbase, void* out, uint64_t cap, uint64_t* n_out, int* guards_ok);
+/* Test seam of the library's 32-bit exclusive scans (needs a GPU, touches no ctx, reads no environment variable): in0[0..n0)
+ * (and in1[0..n1) unless in1 is NULL) are uploaded into buffers with n + 1 readable entries, as the scans require -- entry n
+ * holds a non-zero word that must not reach any sum --; exclusive_scan_u32_pair runs (exclusive_scan_u32 when in1 is NULL) with
+ * scratch sized by scan_temp_bytes: arrays up to 262144 entries take the one-workgroup kernel, longer ones rocPRIM.
+ * out0[0..n0] and out1[0..n1] (n + 1 entries each, out[n] = the total mod 2^32) come back.  A scan that writes behind out[n] is
+ * reported as SCS_EDEVICE.  Errors as for scs_devbuf_probe. */
+int         scs_scan_probe(int device, const uint32_t* in0, uint64_t n0, const uint32_t* in1, uint64_t n1, uint32_t* out0, uint32_t* out1);
 /* Host-only: leave <fasta_path>.fai beside the file if there is none, exactly as scs_load_genome_fasta does (the
  * reference indexes its input through fastahack, lib/fastahack/Fasta.cpp:241-249: name, length, offset, bases per
  * line, bytes per line). */

@@ -225,6 +225,40 @@ def devbuf_probe(first_bytes, second_bytes, device=0):
     return caps[0], caps[1], bool(same.value)
 
 
+def bgzf_device_probe(data, zbase=0, device=0):
+    """Test seam (needs a GPU): the BGZF blocks the device kernels make of `data` (plan, scan, emit -- what a batch's mate goes
+    through), written from byte `zbase` (0..3) of a guarded output buffer.  Returns (blocks, guards_ok)."""
+    L = load_library()
+    L.scs_bgzf_device_probe.argtypes = [C.c_int, C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    data = bytes(data)
+    cap = len(data) + 31 * ((len(data) + 64511) // 64512) + 64
+    out, n, ok = C.create_string_buffer(cap), C.c_uint64(), C.c_int()
+    rc = L.scs_bgzf_device_probe(device, data, len(data), zbase, out, cap, C.byref(n), C.byref(ok))
+    if rc:
+        raise ScsError(rc, "scs_bgzf_device_probe: " + (L.scs_last_error(None) or b"").decode())
+    return out.raw[:n.value], bool(ok.value)
+
+
+def scan_probe(a0, a1=None, device=0):
+    """Test seam (needs a GPU): the library's exclusive scan of the uint32 array a0 (n + 1 entries come back), or of the pair
+    (a0, a1) in one call when a1 is given.  Returns out0, or (out0, out1)."""
+    import numpy as np
+    L = load_library()
+    L.scs_scan_probe.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    a0 = np.ascontiguousarray(a0, np.uint32)
+    o0 = np.empty(a0.size + 1, np.uint32)
+    if a1 is None:
+        rc = L.scs_scan_probe(device, a0.ctypes.data, a0.size, None, 0, o0.ctypes.data, None)
+    else:
+        a1 = np.ascontiguousarray(a1, np.uint32)
+        o1 = np.empty(a1.size + 1, np.uint32)
+        p1 = a1 if a1.size else np.zeros(1, np.uint32)                # an empty second array is still a second array: a valid pointer
+        rc = L.scs_scan_probe(device, a0.ctypes.data, a0.size, p1.ctypes.data, a1.size, o0.ctypes.data, o1.ctypes.data)
+    if rc:
+        raise ScsError(rc, "scs_scan_probe: " + (L.scs_last_error(None) or b"").decode())
+    return o0 if a1 is None else (o0, o1)
+
+
 def truth_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, genome_start=0, rname="chr", amp=0, cnt=1,
                        paired=False, is_read2=False, mate=None):
     """Host-only: one read's truth SAM line (with its newline) through the formatter the truth kernels run.  n = window length;

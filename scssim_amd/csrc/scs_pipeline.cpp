@@ -526,6 +526,89 @@ int scs_bgzf_probe(const void* text, uint64_t nbytes, uint32_t lds_out_cap, void
     if (out) { if (z.size() > cap) return SCS_EOVERFLOW; memcpy(out, z.data(), z.size()); }
     return SCS_OK;
 }
+namespace {
+struct ProbeMem {                                         // plain hipMalloc blocks of a device probe, freed on every way out (no seam: not a DevBuf)
+    std::vector<void*> blocks;
+    void* get(size_t bytes) { void* p = nullptr; HIP_OK(hipMalloc(&p, std::max<size_t>((bytes + 15) & ~(size_t)15, 16))); blocks.push_back(p); return p; }
+    ~ProbeMem() { for (void* p : blocks) (void)hipFree(p); }
+};
+constexpr size_t kProbeGuard = 64;                        // guard bytes on each side of a probe's output
+constexpr int kProbeFill = 0xA5;
+void probe_sync() {
+    HIP_OK(hipDeviceSynchronize());
+    const hipError_t le = take_launch_error();                                    // hipGetLastError + what the launchers noted
+    if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("probe kernel failed: ") + hipGetErrorString(le));
+}
+}  // namespace
+// device test seam: plan, scan and emit over a fresh text buffer, exactly the calls scs_reads.cpp makes per mate
+int scs_bgzf_device_probe(int device, const void* text, uint64_t nbytes, uint32_t zbase, void* out, uint64_t cap, uint64_t* n_out, int* guards_ok) {
+    if ((!text && nbytes) || (!out && nbytes) || !n_out || !guards_ok || zbase > 3 || bgzf_bound(nbytes) > 0xFFFFFFF0ull) return SCS_EINVAL;
+    *n_out = 0; *guards_ok = 1;
+    if (!nbytes) return SCS_OK;
+    try {
+        HIP_OK(hipSetDevice(device));
+        ProbeMem mem;
+        const uint32_t nblk = bgzf_blocks(nbytes);
+        const size_t zcap = kProbeGuard + 4 + (size_t)bgzf_bound(nbytes) + kProbeGuard;   // [guard | zbase | the blocks, at most bgzf_bound | guard]
+        char* d_text = (char*)mem.get(nbytes);
+        uint8_t* d_plan = (uint8_t*)mem.get((size_t)nblk * BGZF_PLAN_BYTES);
+        uint32_t* d_sizes = (uint32_t*)mem.get(((size_t)nblk + 2) * 4); uint32_t* d_offs = (uint32_t*)mem.get(((size_t)nblk + 2) * 4);
+        uint32_t* d_crc = (uint32_t*)mem.get(512 * 4);
+        char* d_z = (char*)mem.get(zcap);
+        uint32_t tabs[512]; bgzf_host_tables(tabs, tabs + 256);
+        HIP_OK(hipMemcpy(d_text, text, nbytes, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_crc, tabs, sizeof tabs, hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(d_sizes, 0, ((size_t)nblk + 2) * 4));
+        HIP_OK(hipMemset(d_z, kProbeFill, zcap));
+        HIP_OK(hipDeviceSynchronize());
+        launch_bgzf_plan(nullptr, d_text, nbytes, d_plan, d_sizes);
+        exclusive_scan_u32(nullptr, d_sizes, d_offs, nblk, nullptr, 0);
+        launch_bgzf_emit(nullptr, d_text, nbytes, d_plan, d_sizes, d_offs, d_crc, d_crc + 256, d_z + kProbeGuard, zbase);
+        probe_sync();
+        uint32_t total = 0;
+        HIP_OK(hipMemcpy(&total, d_offs + nblk, 4, hipMemcpyDeviceToHost));
+        *n_out = total;
+        if (total > bgzf_bound(nbytes)) throw ScsError(SCS_EDEVICE, "BGZF probe: the blocks' total exceeds bgzf_bound");
+        std::vector<uint8_t> z(zcap);
+        HIP_OK(hipMemcpy(z.data(), d_z, zcap, hipMemcpyDeviceToHost));
+        const size_t lo = kProbeGuard + zbase, hi = lo + total;                       // everything outside [lo, hi) is guard
+        for (size_t i = 0; i < zcap; ++i) if ((i < lo || i >= hi) && z[i] != (uint8_t)kProbeFill) { *guards_ok = 0; break; }
+        if (total > cap) return SCS_EOVERFLOW;
+        memcpy(out, z.data() + lo, total);
+        return SCS_OK;
+    } catch (const std::exception& e) { g_create_error = e.what(); return SCS_EDEVICE; }
+}
+// device test seam: the exclusive scans of scs_k_misc.hip over uploaded arrays
+int scs_scan_probe(int device, const uint32_t* in0, uint64_t n0, const uint32_t* in1, uint64_t n1, uint32_t* out0, uint32_t* out1) {
+    if ((!in0 && n0) || !out0 || (in1 && !out1) || (!in1 && n1) || n0 > 0x7FFFFFF0ull || n1 > 0x7FFFFFF0ull) return SCS_EINVAL;
+    try {
+        HIP_OK(hipSetDevice(device));
+        ProbeMem mem;
+        const uint32_t* hin[2] = {in0, in1}; const uint64_t n[2] = {n0, n1}; uint32_t* hout[2] = {out0, out1};
+        uint32_t* din[2] = {nullptr, nullptr}; uint32_t* dout[2] = {nullptr, nullptr};
+        const int arrays = in1 ? 2 : 1;
+        const size_t guard_words = kProbeGuard / 4;
+        for (int a = 0; a < arrays; ++a) {
+            din[a] = (uint32_t*)mem.get((n[a] + 2) * 4); dout[a] = (uint32_t*)mem.get((n[a] + 1 + guard_words) * 4);
+            HIP_OK(hipMemset(din[a], kProbeFill, (n[a] + 2) * 4));                    // in[n] is readable and must be ignored: it is not zero
+            if (n[a]) HIP_OK(hipMemcpy(din[a], hin[a], n[a] * 4, hipMemcpyHostToDevice));
+            HIP_OK(hipMemset(dout[a], kProbeFill, (n[a] + 1 + guard_words) * 4));
+        }
+        const size_t tb = scan_temp_bytes((size_t)std::max(n0, n1));
+        void* temp = (char*)mem.get(tb);
+        HIP_OK(hipDeviceSynchronize());
+        if (in1) exclusive_scan_u32_pair(nullptr, din[0], dout[0], n0, din[1], dout[1], n1, temp, tb);
+        else exclusive_scan_u32(nullptr, din[0], dout[0], n0, temp, tb);
+        probe_sync();
+        for (int a = 0; a < arrays; ++a) {
+            std::vector<uint32_t> h(n[a] + 1 + guard_words);
+            HIP_OK(hipMemcpy(h.data(), dout[a], h.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t i = n[a] + 1; i < h.size(); ++i) if (h[i] != 0xA5A5A5A5u) throw ScsError(SCS_EDEVICE, "scan probe: a scan wrote behind out[n]");
+            memcpy(hout[a], h.data(), (n[a] + 1) * 4);
+        }
+        return SCS_OK;
+    } catch (const std::exception& e) { g_create_error = e.what(); return SCS_EDEVICE; }
+}
 int scs_fasta_write_index(const char* path, char* errbuf, size_t errlen) {
     if (!path) return SCS_EINVAL;
     std::vector<FastaRecord> recs;

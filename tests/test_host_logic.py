@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, SEAMS_CLI, SEAMS_LIB
+import bgzf_cases
 
 import scssim_amd
 
@@ -330,7 +331,7 @@ def test_bgzf_arithmetic_inflates_with_zlib():
     fib = [1, 1]
     while sum(fib) < 60000:
         fib.append(fib[-1] + fib[-2])
-    cases = {"fastq": fq, "tiny": b"A", "two": b"AB", "one_symbol": b"N" * 70000, "random": os.urandom(150000), "empty": b"",
+    cases = {"fastq": fq, "tiny": b"A", "two": b"AB", "one_symbol": b"N" * 70000, "random": np.random.default_rng(2).integers(0, 256, 150000, dtype=np.uint8).tobytes(), "empty": b"",
              "exact_block": fq[:64512], "block_plus_1": fq[:64513], "fibonacci": b"".join(bytes([65 + i]) * f for i, f in enumerate(fib))}
     # trees deeper than 17: every count one more than the sum of all but the latest before it (1, 2, 4, 7, 12, 20, 33, ...).  The
     # 15-bit repair must count the internal nodes below the limit too (zlib's gen_bitlen), or the code is oversubscribed
@@ -351,6 +352,59 @@ def test_bgzf_arithmetic_inflates_with_zlib():
             if data:
                 assert gzip.decompress(z) == data
     assert len(scssim_amd.bgzf_probe(fq)) < 0.6 * len(fq)             # 2 bits per base + the qualities' entropy (5 bits here)
+
+
+@pytest.mark.parametrize("name", list(bgzf_cases.CASES))
+def test_bgzf_cases_reach_the_branches_they_name(name):
+    """The shared BGZF case table (tests/bgzf_cases.py; the GPU test runs the device over it) under the host emulation: every
+    case reaches the branch it is there for -- per block stored (byte 18 = 0x01) or dynamic Huffman (low bits 0b101), and of the
+    stored ones which reason (incompressible, or over the LDS cap: it deflates once the cap is lifted); the repair cases have an
+    unrestricted Huffman tree deeper than 15 over block 0's histogram (end-of-block count included); the LDS-cap cases lie within
+    64 bytes of BGZF_LDS_OUT on their side; `mixed` has all three kinds of block and all four residues of the block offsets mod 4
+    -- and passes the zlib checks of test_bgzf_arithmetic_inflates_with_zlib.  A case that a later change of scs_bgzf.h moves off
+    its branch fails here."""
+    import gzip
+    import zlib
+    bc = bgzf_cases
+    data, (_, want, reach) = bc.data(name), bc.CASES[name]
+    z = scssim_amd.bgzf_probe(data)
+    blocks = scssim_amd.bgzf_blocks(z)
+    assert len(blocks) == (len(data) + bc.BGZF_IN - 1) // bc.BGZF_IN
+    assert b"".join(zlib.decompress(b, 31) for b, _ in blocks) == data
+    assert [i for _, i in blocks] == bc.cut(data)
+    if data:
+        assert gzip.decompress(z) == data
+    kinds = bc.block_kinds(data)
+    if want is not None:
+        assert len(kinds) == len(want) and all(w is None or w == k for w, k in zip(want, kinds)), (reach, kinds[:16])
+    if name in bc.DEEP:
+        assert len(blocks) == 1 and bc.huffman_depth(bc.block_hist(data)) > 15, reach
+    cb = len(blocks[0][0]) - 26 if blocks else 0                      # the first block's deflate data
+    if name == "lds_cap_below":
+        assert bc.BGZF_LDS_OUT - bc.CAP_WINDOW < cb < bc.BGZF_LDS_OUT and len(data) == bc.BGZF_IN, cb
+    if name == "lds_cap_exact":
+        assert cb == bc.BGZF_LDS_OUT and len(data) == bc.BGZF_IN, cb
+    if name == "lds_cap_above":
+        free = len(scssim_amd.bgzf_probe(data, 1 << 30)) - 26           # what it would deflate to without the cap
+        assert bc.BGZF_LDS_OUT < free < bc.BGZF_LDS_OUT + bc.CAP_WINDOW and len(data) == bc.BGZF_IN, free
+    if name == "mixed":
+        offs = np.cumsum([0] + [len(b) for b, _ in blocks])[:-1]
+        assert len(blocks) >= 12 and set(kinds) == {"deflated", "stored_incompressible", "stored_cap"} and set(int(o) % 4 for o in offs) == {0, 1, 2, 3}
+        assert all(len(data[i * bc.BGZF_IN:(i + 1) * bc.BGZF_IN]) == bc.BGZF_IN for i in range(len(blocks)))
+    if name.startswith("len_"):
+        assert len(data) == int(name[4:]) < 256
+    if name == "one_symbol":
+        assert len(set(data)) == 1 and len(blocks) == 2
+    if name.startswith("all_256"):
+        assert len(set(data)) == 256
+    if name == "all_256_flat":
+        assert len(set(np.bincount(np.frombuffer(data, np.uint8)))) == 1 and len(data) == bc.BGZF_IN
+    if name == "two_symbols_equal":
+        assert sorted(np.bincount(np.frombuffer(data, np.uint8))[[65, 66]]) == [len(data) // 2] * 2
+    if name == "ties_with_eob":
+        assert int((np.bincount(np.frombuffer(data, np.uint8)) == 1).sum()) >= 100
+    if name == "big_text":
+        assert len(blocks) > 300
 
 
 def test_part_files_are_one_logical_file_for_both_merges(tmp_path):
