@@ -647,7 +647,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(G == 4 
 //      SIMD): the pass is priced by its fp64 / 32-bit-multiply instructions (Philox seeding, the 64-bit scaling of the draw,
 //      the decode's division and square root), not by loop control.  Not kept.
 // ------------------------------------------------------------------------------------------------
-#define ATTACH_DENSE_STRIDE 56u
+#define ATTACH_DENSE_STRIDE 56u                                                    // (tests/attach_cases.py counts chunks with this stride, 64 lanes and the 1024 bitmap words below)
 __global__ void __launch_bounds__(256) k_attach_plan(const uint32_t* __restrict__ slot_off, uint32_t nt, uint32_t n_slots, uint32_t n_waves, uint32_t* __restrict__ item_tmpl,
                                                      uint32_t* __restrict__ wave_first, uint32_t* __restrict__ valid) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -835,7 +835,7 @@ void launch_poisson(hipStream_t s, DevFrags fr, DevAmps semis, uint32_t n_semis,
 // template in one round when the job is small and the pass is latency bound (measured: 15 vs 18 ms at 13 M semis,
 // 0.35 vs 0.5 ms per step at 44 k)
 static int attach_semi_group(uint32_t n_semis) {
-    static const int forced = seam_env("SCS_ATTACH_G") ? atoi(seam_env("SCS_ATTACH_G")) : 0;   // tuning experiments
+    static const int forced = seam_env("SCS_ATTACH_G") ? atoi(seam_env("SCS_ATTACH_G")) : 0;   // tuning experiments, and tests/test_gpu_attach.py
     return forced == 2 || forced == 4 || forced == 8 || forced == 16 ? forced : (n_semis >= (1u << 18) ? 4 : 8);
 }
 uint32_t attach_dense_waves(uint32_t n_slots) { return n_slots / ATTACH_DENSE_STRIDE + 1u; }
