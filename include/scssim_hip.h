@@ -325,6 +325,12 @@ int         scs_bgzf_device_probe(int device, const void* text, uint64_t nbytes,
  * out0[0..n0] and out1[0..n1] (n + 1 entries each, out[n] = the total mod 2^32) come back.  A scan that writes behind out[n] is
  * reported as SCS_EDEVICE.  Errors as for scs_devbuf_probe. */
 int         scs_scan_probe(int device, const uint32_t* in0, uint64_t n0, const uint32_t* in1, uint64_t n1, uint32_t* out0, uint32_t* out1);
+/* Test seam of the library's resource ownership (no ctx; process-wide): what its owning handles hold at this moment --
+ * out[0] = bytes of device buffers, out[1] = streams it created (a caller's cfg.stream is not one), out[2] = events, out[3] = bytes
+ * of pinned host memory.  Counted by the handles themselves as they allocate and free, not asked of the driver, so other
+ * processes on the card do not show; the two side streams and three events of a ctx's k_reads class kernels are outside the count.
+ * All four are zero once every ctx is destroyed. */
+int         scs_live_resources(uint64_t out[4]);
 /* Host-only: leave <fasta_path>.fai beside the file if there is none, exactly as scs_load_genome_fasta does (the
  * reference indexes its input through fastahack, lib/fastahack/Fasta.cpp:241-249: name, length, offset, bases per
  * line, bytes per line). */

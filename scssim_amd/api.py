@@ -225,6 +225,18 @@ def devbuf_probe(first_bytes, second_bytes, device=0):
     return caps[0], caps[1], bool(same.value)
 
 
+def live_resources():
+    """Test seam: (device-buffer bytes, streams, events, pinned bytes) the library's owning handles hold right now in this
+    process, by their own count (scs_live_resources).  All zero once every GenReads is closed."""
+    L = load_library()
+    L.scs_live_resources.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    rc = L.scs_live_resources(out)
+    if rc:
+        raise ScsError(rc, "scs_live_resources")
+    return tuple(out)
+
+
 def bgzf_device_probe(data, zbase=0, device=0):
     """Test seam (needs a GPU): the BGZF blocks the device kernels make of `data` (plan, scan, emit -- what a batch's mate goes
     through), written from byte `zbase` (0..3) of a guarded output buffer.  Returns (blocks, guards_ok)."""

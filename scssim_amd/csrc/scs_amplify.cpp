@@ -162,7 +162,7 @@ void launch_pass(scs_ctx* c, bool from_frag, uint32_t pass, int rb_slot) {
         out.reserve((uint64_t)out.n + n_slots, s);
         out.reserve_pool(std::max<uint32_t>(1u << 16, (uint32_t)std::min<uint64_t>(((uint64_t)out.n + n_slots) / 256 + 4096, 0xFFFFFFF0ull)), s);
     }
-    KernelTimer& tma = from_frag ? c->tm_attach_f : c->tm_attach;
+    KernelTimer& tma = from_frag ? c->tm[TM_ATTACH_F] : c->tm[TM_ATTACH];
     if (some) tma.begin(s);
     attach_pass(c, from_frag, p, nt, n_slots);
     if (some) { tma.end(s); tma.add_units(nt); }
@@ -176,7 +176,7 @@ void launch_pass(scs_ctx* c, bool from_frag, uint32_t pass, int rb_slot) {
     const uint8_t* g = c->genome.as<uint8_t>();
     if (from_frag) launch_frag_len_sum(s, c->poisson_part.as<unsigned long long>(), nt, c->dsums.as<unsigned long long>() + DS_SEMI_LEN);
     exclusive_scan_u32(s, valid.as<uint32_t>(), valid_off.as<uint32_t>(), nt, c->scan_tmp.p, c->scan_tmp.cap);
-    KernelTimer& tm = from_frag ? c->tm_errscan_f : c->tm_errscan;
+    KernelTimer& tm = from_frag ? c->tm[TM_ERRSCAN_F] : c->tm[TM_ERRSCAN];
     // the stock update rides on k_errs (launched with at least 256 workgroups: one primer type per thread); a sharded job
     // closes the pass with shard_close
     const bool ride = !c->sharded();
@@ -185,10 +185,7 @@ void launch_pass(scs_ctx* c, bool from_frag, uint32_t pass, int rb_slot) {
     // stock update it used to carry runs on the main stream.  Joined before the next setPrimers rewrites the slot offsets.
     hipStream_t es = s;
     if (!from_frag && !seam_env("SCS_ERRS_INLINE")) {
-        if (!c->errs_stream) {
-            HIP_OK(hipStreamCreateWithFlags(&c->errs_stream, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&c->ev_att, hipEventDisableTiming)); HIP_OK(hipEventCreateWithFlags(&c->ev_errs, hipEventDisableTiming));
-        }
+        c->errs_stream.ensure(hipStreamNonBlocking); c->ev_att.ensure(hipEventDisableTiming); c->ev_errs.ensure(hipEventDisableTiming);
         HIP_OK(hipEventRecord(c->ev_att, s)); HIP_OK(hipStreamWaitEvent(c->errs_stream, c->ev_att, 0));
         es = c->errs_stream;
     }
@@ -226,7 +223,7 @@ void collect_post(scs_ctx* c, bool post_now) {
 // ... and are taken over by the host after the next mail_wait: counts of new amplicons, total length of the semis
 void collect_read(scs_ctx* c, int rb_fulls, int rb_semis) {
     if (rb_fulls >= 0) {
-        c->fulls.n += (uint32_t)c->h_rb[rb_fulls]; c->tm_errscan.add_units(c->h_rb[rb_fulls]);
+        c->fulls.n += (uint32_t)c->h_rb[rb_fulls]; c->tm[TM_ERRSCAN].add_units(c->h_rb[rb_fulls]);
         if (c->pending_seg_cycle >= 0) {                                          // stored order within a cycle: fragment pass p descending
             const size_t nb = std::min<size_t>(c->semi_block_end.size(), 8);
             for (int b = (int)nb - 1; b >= 0; --b) {
@@ -236,7 +233,7 @@ void collect_read(scs_ctx* c, int rb_fulls, int rb_semis) {
             c->pending_seg_cycle = -1;
         }
     }
-    if (rb_semis >= 0) { c->semis.n += (uint32_t)c->h_rb[rb_semis]; c->tm_errscan_f.add_units(c->h_rb[rb_semis]); c->semi_block_end.push_back(c->semis.n); }
+    if (rb_semis >= 0) { c->semis.n += (uint32_t)c->h_rb[rb_semis]; c->tm[TM_ERRSCAN_F].add_units(c->h_rb[rb_semis]); c->semi_block_end.push_back(c->semis.n); }
     c->semi_total_len = c->h_rb[8];
     if (c->sharded()) c->total_primers = c->h_rb[9];                               // whole-job pool size after the budgets exchanged so far
     c->min_stock_lb = c->h_rb[10];                                                 // the smallest primer stock in use after the passes mailed so far
@@ -252,7 +249,7 @@ void do_amplify(scs_ctx* c) {
     if (c->cfg.verbose) fprintf(stderr, "\nMALBAC amplification...\n");
     c->semis.reset_counts(); c->fulls.reset_counts(); c->semi_block_end.clear(); c->full_segs.clear(); c->pending_seg_cycle = -1; c->pend = Mail();
     c->timing_gate = (c->amplify_calls++ % c->timing_every) == 0;
-    c->tm_errscan.reset(); c->tm_errscan_f.reset(); c->tm_attach.reset(); c->tm_attach_f.reset();
+    c->tm[TM_ERRSCAN].reset(); c->tm[TM_ERRSCAN_F].reset(); c->tm[TM_ATTACH].reset(); c->tm[TM_ATTACH_F].reset();
     c->primer_cnt.reserve(65536 * 8, s); c->primer_cut.reserve(65536 * 8, s); c->primer_delta.reserve(65536 * 4, s);   // createPrimers: 4^8 types x `primers` copies
     if (c->sharded()) c->primer_gdelta.reserve((65536 + SHARD_TAIL_WORDS) * 4, s);
     c->min_stock_lb = c->cfg.primers > 0 ? (uint64_t)c->cfg.primers : 0; c->st.stock_checks = c->st.stock_exhausted_passes = c->st.stock_rounds = 0;
@@ -289,7 +286,7 @@ void do_amplify(scs_ctx* c) {
     c->pend.add(c->flags.p, 4, 30);                                              // the overflow flags ride on the last collect: one wait, not two
     collect_post(c, true); mail_wait(c); collect_read(c, open_fulls, open_semis);
     flags_eval(c);
-    c->tm_errscan.collect(); c->tm_errscan_f.collect(); c->tm_attach.collect(); c->tm_attach_f.collect();
+    c->tm[TM_ERRSCAN].collect(); c->tm[TM_ERRSCAN_F].collect(); c->tm[TM_ATTACH].collect(); c->tm[TM_ATTACH_F].collect();
     c->amplified = true; c->allocated = false;
     c->st.semi_amplicons = c->semis.n; c->st.full_amplicons = c->fulls.n; c->st.primers_left = c->total_primers;
 }

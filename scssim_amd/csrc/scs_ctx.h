@@ -24,12 +24,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
-
 
 namespace scs {
 
@@ -40,13 +41,25 @@ struct ScsError : std::runtime_error { int code; ScsError(int c, const std::stri
 
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// growable device buffer.  Small buffers are plain hipMalloc blocks.  A buffer that grows past 64 MB moves (once) into
+// what the owning handles below hold at this moment, process-wide (scs_live_resources: the tests' leak check); relaxed: it orders nothing
+struct Census { std::atomic<uint64_t> dev_bytes{0}, streams{0}, events{0}, pinned_bytes{0}; };
+inline Census& census() { static Census c; return c; }
+inline void census_add(std::atomic<uint64_t>& a, uint64_t d) { a.fetch_add(d, std::memory_order_relaxed); }   // (d = -n: n fewer)
+struct LiveBytes {           // DevBuf's capacity: a size_t whose every change is also made to census().dev_bytes
+    size_t v = 0;
+    operator size_t() const { return v; }
+    LiveBytes& operator=(size_t n) { census_add(census().dev_bytes, (uint64_t)n - v); v = n; return *this; }
+    LiveBytes& operator+=(size_t n) { return *this = v + n; }
+};
+
+// growable device buffer, freed by its destructor.  Small buffers are plain hipMalloc blocks.  A buffer that grows past 64 MB moves (once) into
 // a reserved virtual address range and from then on grows IN PLACE by mapping more physical memory behind it
 // (hipMemAddressReserve / hipMemCreate / hipMemMap): no reallocate-copy-free cycles while the amplicon arrays of a
 // whole-genome job grow cycle by cycle, no transient 2.5x footprint -- and fresh hipMalloc memory costs about 20 ms per
 // GB on its first touch on this platform (measured), mapped chunks do not.
 struct DevBuf {
-    void* p = nullptr; size_t cap = 0;       // cap: usable (mapped) bytes
+    void* p = nullptr; LiveBytes cap;        // cap: usable (mapped) bytes
+    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete; ~DevBuf() { release(); }
     size_t va = 0;                           // reserved address range in bytes (0: plain hipMalloc block)
     // equal-sized chunks: on ROCm 7.2 hipMemSetAccess rejects a chunk mapped right behind one of a different size (probed)
     static constexpr size_t kRange = 384ull << 30, kGran = 128ull << 20;
@@ -102,6 +115,38 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// The other device-side resources, owned the same way: made by ensure() / reserve() where they are first needed (a second call
+// is a no-op), usable wherever the raw handle is, destroyed with their owner when they were made.
+struct Stream {
+    hipStream_t s = nullptr; bool owned = false;
+    Stream() = default; Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s && owned) { (void)hipStreamDestroy(s); census_add(census().streams, -1); } }
+    void ensure(unsigned flags) { if (s) return; HIP_OK(hipStreamCreateWithFlags(&s, flags)); owned = true; census_add(census().streams, 1); }
+    void adopt(hipStream_t theirs) { s = theirs; owned = false; }                // the caller's stream (cfg->stream): used, never destroyed
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default; Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }         // (movable, for vectors of them; not copyable)
+    ~Event() { if (e) { (void)hipEventDestroy(e); census_add(census().events, -1); } }
+    void ensure(unsigned flags) { if (e) return; HIP_OK(hipEventCreateWithFlags(&e, flags)); census_add(census().events, 1); }
+    operator hipEvent_t() const { return e; }
+};
+template <class T> struct Pinned {                                               // a pinned host block of T
+    T* p = nullptr; size_t bytes = 0;
+    Pinned() = default; Pinned(Pinned&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    ~Pinned() { release(); }
+    void reserve(size_t need, unsigned flags, size_t alloc = 0) {                // at least `need` bytes; a block that must grow is made max(alloc, need) large, its contents are lost
+        if (need <= bytes) return;
+        release(); alloc = std::max(alloc, need);
+        HIP_OK(hipHostMalloc((void**)&p, alloc, flags)); bytes = alloc; census_add(census().pinned_bytes, bytes);
+    }
+    void release() { if (p) { (void)hipHostFree(p); census_add(census().pinned_bytes, -(uint64_t)bytes); } p = nullptr; bytes = 0; }
+    operator T*() const { return p; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "DevBuf owns its memory");
+static_assert(!std::is_copy_constructible<Stream>::value && !std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Pinned<char>>::value, "the handles own what they hold");
+
 struct AmpStore {            // SoA amplicon arrays (DevAmps) with capacity management
     DevBuf parent, sl, gc, primers, uid, errs; uint32_t n = 0, cap = 0;
     DevBuf pool, pool_head; uint32_t pool_cap = 0;
@@ -127,16 +172,15 @@ struct AmpStore {            // SoA amplicon arrays (DevAmps) with capacity mana
     DevErrPool pool_view() const { return DevErrPool{pool.as<uint32_t>(), pool_head.as<uint32_t>(), pool_cap}; }
     void reset(hipStream_t s) { n = 0; if (pool_head.p) HIP_OK(hipMemsetAsync(pool_head.p, 0, 4, s)); }
     void reset_counts() { n = 0; }                                                // the pool head is zeroed by k_amplify_init
-    void release() { parent.release(); sl.release(); gc.release(); primers.release(); uid.release(); errs.release(); pool.release(); pool_head.release(); n = cap = pool_cap = 0; }
-};
+};                           // (its DevBufs free themselves: not copyable, nothing to release by hand)
 
 static const bool kAlwaysTimed = true;
 struct KernelTimer {         // HIP events on the ctx stream around the launches of one kernel (scs_set_kernel_timing turns one off)
-    const char* name; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; double ms = 0; uint64_t launches = 0; uint64_t units = 0; bool on = true; const bool* gate = &kAlwaysTimed;
+    const char* name; std::vector<std::pair<Event, Event>> ev; size_t used = 0; double ms = 0; uint64_t launches = 0; uint64_t units = 0; bool on = true; const bool* gate = &kAlwaysTimed;
     void add_units(uint64_t n) { if (on && *gate) units += n; }
     void begin(hipStream_t s) {
         if (!on || !*gate) return;
-        if (used == ev.size()) { hipEvent_t a, b; HIP_OK(hipEventCreate(&a)); HIP_OK(hipEventCreate(&b)); ev.push_back({a, b}); }
+        if (used == ev.size()) { std::pair<Event, Event> p; p.first.ensure(hipEventDefault); p.second.ensure(hipEventDefault); ev.push_back(std::move(p)); }
         HIP_OK(hipEventRecord(ev[used].first, s));
     }
     void end(hipStream_t s) { if (!on || !*gate) return; HIP_OK(hipEventRecord(ev[used].second, s)); ++used; }
@@ -145,11 +189,12 @@ struct KernelTimer {         // HIP events on the ctx stream around the launches
         used = 0;
     }
     void reset() { ms = 0; launches = 0; units = 0; used = 0; }
-    void release() { for (auto& e : ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } ev.clear(); }
 };
+enum { TM_ERRSCAN, TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
-
-struct SinkPipe;
+struct SinkPipe;             // scs_reads.cpp
+struct SinkPipeDelete { void operator()(SinkPipe* p) const; };
+struct RcclDelete { void operator()(RcclComm* r) const { rccl_destroy(r); } };   // (skips ncclCommDestroy after scs_comm_abort)
 }  // namespace scs
 using namespace scs;
 
@@ -158,9 +203,14 @@ struct Mail {                // a batch of device scalars for one k_mail post (a
     void add(const void* p, int width, int slot, bool clear_after = false) { src[n] = p; wd[n] = width; dst[n] = slot; if (clear_after) clear |= 1u << n; ++n; }
 };
 
+// Every device-side resource below is an owning handle: `delete ctx` is the whole teardown.  Members are destroyed in REVERSE order
+// of declaration, and three places rely on it: the ctx stream comes first (it goes last, after everything that was ever queued on
+// it), the RCCL communicator right behind it (it goes just before the stream its collectives ran on), and the sink pipe last (it
+// goes first, before the pinned blocks and events of the batches it shipped; its writers are joined at the end of every yield).
 struct scs_ctx {
+    Stream stream;                                                                 // cfg.stream adopted, or the ctx's own
+    std::unique_ptr<RcclComm, RcclDelete> rccl;            // scs_comm_init: RCCL communicator of this shard (the device collectives then run on it)
     scs_config cfg; std::string err;
-    hipStream_t stream = nullptr; bool own_stream = false;
     RngKey key{0, 0};
     // model
     ProfileTables prof; bool have_profile = false; DevTables dtb{};
@@ -172,10 +222,10 @@ struct scs_ctx {
     uint64_t f_gidx_base = 0; bool have_frags = false;
     uint64_t slice_base = 0, slice_len = 0; bool sliced = false;   // sharded job staged from a FASTA: only the bases of this shard's fragments are resident (genome coordinate slice_base ..)
     DevBuf df_blob, df_primers, df_hasn; size_t df_len_off = 0, df_strand_off = 0;           // fragments: offsets | lengths | strands in one block
-    uint8_t* h_frag = nullptr; size_t h_frag_cap = 0; bool frag_copy_pending = false;   // its pinned staging copy
+    Pinned<uint8_t> h_frag; bool frag_copy_pending = false;                                  // its pinned staging copy
     // amplicons
     AmpStore semis, fulls;
-    DevBuf budget_f, budget_s, slot_off_f, slot_off_s, dsums, poisson_part; uint64_t* h_rb = nullptr;   // dsums: device scalars; h_rb: pinned, device-mapped mailbox (32 words)
+    DevBuf budget_f, budget_s, slot_off_f, slot_off_s, dsums, poisson_part; Pinned<uint64_t> h_rb;   // dsums: device scalars; h_rb: pinned, device-mapped mailbox (32 words)
     unsigned long long* d_rb = nullptr; uint64_t mail_seq = 0;                      // device address of h_rb; sequence of the last post
     Mail pend;                                                                     // counts of the passes launched since the last collect
     bool timing_gate = true; uint32_t timing_every = 1; uint64_t amplify_calls = 0, yield_calls = 0;   // scs_set_kernel_timing: events on every n-th call
@@ -186,22 +236,22 @@ struct scs_ctx {
     DevBuf slots, slot_tmpl, valid, valid_off, valid_f, valid_off_f, scan_tmp, flags;
     // allocation + reads
     DevBuf weights, read_numbers, pair_off, pairs, odd_before, a_part, a_tp, a_probs, a_quota, a_poff, a_plan, a_crn, a_scratch, a_brow, a_bmap, a_send, a_gath, a_odd; SegMap gmap{}; std::vector<uint32_t> h_read_numbers; uint64_t reads_requested = 0, n_pairs_planned = 0; bool allocated = false;
-    DevBuf slot_b, slot_q, lens, ev_hdr, ev_dat, sizes1, sizes2, off1, off2, out1, out2, out1b, out2b, rl_cls, rl_pos, rl_lists, d_bounds; SinkPipe* pipe = nullptr;
-    hipStream_t errs_stream = nullptr; hipEvent_t ev_att = nullptr, ev_errs = nullptr; bool errs_pending = false;   // k_errs<semi->full> of a cycle runs beside the fragment pass that follows it
+    DevBuf slot_b, slot_q, lens, ev_hdr, ev_dat, sizes1, sizes2, off1, off2, out1, out2, out1b, out2b, rl_cls, rl_pos, rl_lists, d_bounds;
+    Stream errs_stream; Event ev_att, ev_errs; bool errs_pending = false;   // k_errs<semi->full> of a cycle runs beside the fragment pass that follows it
     DevBuf slots_fr, slot_tmpl_fr;                        // the fragment passes' own slot arrays (the semi pass's are still being read then)
     // BGZF made on the device (scs_bgzf.hip): per mate the blocks' plans / sizes / offsets, two sets of output buffers, the CRC tables; the
     // blocks' total per batch reaches the host through a small pinned array (h_z) behind an event, one batch late (see do_yield)
-    DevBuf z_plan[2], z_sizes[2], z_offs[2], z_out[2][2], z_crc; uint32_t* h_z = nullptr; hipEvent_t ev_z[2] = {nullptr, nullptr};
+    DevBuf z_plan[2], z_sizes[2], z_offs[2], z_out[2][2], z_crc; Pinned<uint32_t> h_z; Event ev_z[2];
     bool want_cks = false; DevBuf d_cks; std::vector<uint64_t> cks;   // scs_set_batch_checksums: per batch and mate, computed where the text lies in HBM
     // truth SAM (scs_set_truth_sam): the path (empty: off), per batch the pairs' SAM sizes and 64-bit offsets, two output buffers (the
     // batch's text crosses PCIe on the copy stream while the next batch is made), the record table the kernels name records from,
     // and the batch's total, read back through a pinned word behind ev_t
     std::string truth_path; uint64_t truth_bytes = 0;
-    DevBuf t_sizes, t_offs, t_scan, t_out[2], t_recs; uint64_t* h_t = nullptr; hipEvent_t ev_t = nullptr;
+    DevBuf t_sizes, t_offs, t_scan, t_out[2], t_recs; Pinned<uint64_t> h_t; Event ev_t;
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
-    hipStream_t pre_stream = nullptr; hipEvent_t ev_pre[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_plan = nullptr;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
+    Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)
-    hipStream_t copy_stream = nullptr; hipEvent_t ev_made[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};   // sink mode: D2H on its own stream, behind the batch's k_reads
+    Stream copy_stream; Event ev_made[2], ev_d2h[2];   // sink mode: D2H on its own stream, behind the batch's k_reads
     // sharded single job: collectives supplied by the caller + segment bookkeeping of the local amplicon lists
     scs_allreduce_fn allreduce = nullptr; scs_allgatherv_fn allgatherv = nullptr; void* coll_user = nullptr;
     scs_allreduce_dev_fn allreduce_dev = nullptr; scs_allgather_dev_fn allgather_dev = nullptr; void* coll_dev_user = nullptr;
@@ -209,7 +259,6 @@ struct scs_ctx {
     std::vector<uint32_t> semi_block_end;                  // local semi count after each fragment pass
     struct Seg { int c, p; uint32_t count; }; std::vector<Seg> full_segs;   // local fulls list = these, in order
     DevBuf d_hostred;
-    RcclComm* rccl = nullptr;                              // scs_comm_init: RCCL communicator of this shard (the device collectives then run on it)
     uint32_t seg_lo[ALLOC_SLOTS + 1] = {0};                // first local amplicon of each list segment slot (do_allocate); [ALLOC_SLOTS] = amplicon count
     int pending_seg_cycle = -1;
     // collectives run when the job is sharded -- or whenever hooks are installed (1-shard jobs then exercise them too)
@@ -246,17 +295,21 @@ struct scs_ctx {
         HIP_OK(hipMemcpyAsync(d_recv, all.data(), all.size(), hipMemcpyHostToDevice, stream)); HIP_OK(hipStreamSynchronize(stream));
     }
     scs_stats st{};
-    KernelTimer tm_errscan{"k_errs<semi->full>"}, tm_errscan_f{"k_errs<frag->semi>"}, tm_reads{"k_reads"}, tm_attach{"k_attach<semi>"}, tm_indels{"k_indels"}, tm_attach_f{"k_attach<frag>"}, tm_truth{"k_truth"};
+    KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}};
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
         return DevFrags{(uint64_t*)b, (uint32_t*)(b + df_len_off), (int8_t*)(b + df_strand_off), df_primers.as<uint32_t>(), (uint32_t)f_len.size(), f_gidx_base, df_hasn.as<uint8_t>()};
     }
+    std::unique_ptr<SinkPipe, SinkPipeDelete> pipe;        // the sink's writers and pinned slots, made by the first yield into a sink
 };
 
 
 namespace scs {
-// ---- mailbox: device scalars -> pinned host words (scs_pipeline.cpp)
+// ---- scs_pipeline.cpp
+std::string& create_error();                // this thread's scs_last_error(NULL): what scs_create and the ctx-less entry points report
+inline void copy_err(char* errbuf, size_t errlen, const char* msg) { if (errbuf && errlen) { strncpy(errbuf, msg, errlen - 1); errbuf[errlen - 1] = 0; } }
+// mailbox: device scalars -> pinned host words
 void mail_post(scs_ctx* c, const Mail& m, bool last, hipStream_t st = nullptr);   // last: the post the host will wait for; st: the ctx stream unless given
 void mail_wait(scs_ctx* c);                                                      // everything posted so far has landed in h_rb
 void flags_eval(scs_ctx* c);
@@ -290,7 +343,6 @@ struct OutTarget { bool device; char* d1; char* d2; size_t cap1, cap2; BatchSink
                    bool discard = false; };                                       // discard: the FASTQ text is not wanted on the host (a NULL sink with truth on)                                          // bgzf: the sink gets BGZF blocks made on the device instead of the text   // seg_off: byte offset of each list segment's first record (shard index)
 
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out);
-void sink_pipe_free(scs_ctx* c);            // releases and deletes c->pipe
 // truth SAM: refuses (SCS_EINVAL) the targets it does not apply to; device: scs_yield_reads_device, writers: the file sink's
 void truth_check(scs_ctx* c, bool device, int writers);
 std::vector<int> gpu_local_cpus(int device);

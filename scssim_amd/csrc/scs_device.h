@@ -190,7 +190,10 @@ void launch_pair_offsets(hipStream_t s, const uint32_t* rn, uint32_t ac, int pai
 // reads of pairs [p0, p0+np): slot layout [2*np][slot] bases / quals (SE: [np][slot])
 // the two side streams the small class kernels of a batch run on beside the big one, with their fork / join events: owned by
 // the ctx whose batches they order (created by the first launch_reads that uses them, on the current device)
-struct ReadsSide { hipStream_t st[2] = {nullptr, nullptr}; hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr}; void release(); };
+struct ReadsSide {
+    hipStream_t st[2] = {nullptr, nullptr}; hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr}; void release();
+    ReadsSide() = default; ReadsSide(const ReadsSide&) = delete; ReadsSide& operator=(const ReadsSide&) = delete; ~ReadsSide() { release(); }
+};
 size_t reads_lds_bytes(const DevTables& tb, bool uni = false);   // uni: the uniform-walk variant (event-free ACGT-only reads)
 //          // dynamic LDS of one inject_errors workgroup for this profile
 void launch_reads(hipStream_t s, const uint8_t* g, const uint32_t* g2, DevErrPool spool, DevErrPool fpool,

@@ -163,7 +163,7 @@ struct NumaScope {
 
 struct SinkPipe {
     std::vector<int> local_cpus;                                                   // of the device's NUMA node (gpu_local_cpus)
-    struct Slot { char* h[3] = {nullptr, nullptr, nullptr}; size_t cap[3] = {0, 0, 0}; hipEvent_t ev = nullptr; bool busy = false; };   // h[2]: the batch's truth SAM
+    struct Slot { Pinned<char> h[3]; Event ev; bool busy = false; };               // h[2]: the batch's truth SAM
     struct Job { int slot, region; size_t n1, n2, n3; };
     struct Writer { std::thread th; std::vector<Job> q; };
     std::vector<Slot> slots; std::vector<Writer> writers;
@@ -179,7 +179,7 @@ struct SinkPipe {
         local_cpus = gpu_local_cpus(dev);
         const size_t nw = (size_t)std::max(1, f->writers), want = nw + 2;
         // (blocking events: a writer that waits for its batch's copy sleeps instead of spinning -- the host's cores are the sink's bottleneck)
-        while (slots.size() < want) { Slot sl; HIP_OK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming | hipEventBlockingSync)); slots.push_back(sl); }
+        while (slots.size() < want) { Slot sl; sl.ev.ensure(hipEventDisableTiming | hipEventBlockingSync); slots.push_back(std::move(sl)); }
         for (auto& sl : slots) sl.busy = false;
         writers = std::vector<Writer>(nw);
         for (size_t w = 0; w < writers.size(); ++w) writers[w].th = std::thread([this, w] {
@@ -209,26 +209,23 @@ struct SinkPipe {
         for (int f = 0; f < 3; ++f) {
             const size_t need = f == 0 ? need1 : f == 1 ? need2 : need3;
             if (f == 2 && need == 0) continue;
-            if (need > sl.cap[f]) {
-                if (sl.h[f]) HIP_OK(hipHostFree(sl.h[f]));
-                sl.h[f] = nullptr; sl.cap[f] = 0;
-                const size_t nc = std::max<size_t>(need + need / 8, 1 << 20);
+            if (need > sl.h[f].bytes) {
                 NumaScope here(local_cpus);                                        // the slot's pages on the GPU's node
-                HIP_OK(hipHostMalloc((void**)&sl.h[f], nc, hipHostMallocDefault)); sl.cap[f] = nc;
+                sl.h[f].reserve(need, hipHostMallocDefault, std::max<size_t>(need + need / 8, 1 << 20));
             }
         }
         return k;
     }
     void submit(int region, int slot, size_t n1, size_t n2, size_t n3 = 0) { { std::lock_guard<std::mutex> lk(mu); writers[(size_t)region % writers.size()].q.push_back(Job{slot, region, n1, n2, n3}); } cv.notify_all(); }
     bool finish() { { std::lock_guard<std::mutex> lk(mu); done = true; } cv.notify_all(); for (auto& W : writers) if (W.th.joinable()) W.th.join(); writers.clear(); return !failed; }
-    void release() { for (auto& sl : slots) { for (int f = 0; f < 3; ++f) if (sl.h[f]) (void)hipHostFree(sl.h[f]); if (sl.ev) (void)hipEventDestroy(sl.ev); } slots.clear(); }
 };
+void SinkPipeDelete::operator()(SinkPipe* p) const { delete p; }                   // (the slots' pinned blocks and events free themselves)
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out) {
     if (!c->allocated) throw ScsError(SCS_EINVAL, "scs_yield_reads: call scs_allocate_reads first");
     hipStream_t s = c->stream; const int paired = c->cfg.paired != 0;
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
-    c->tm_reads.reset(); c->tm_indels.reset(); c->tm_truth.reset();
+    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset();
     const uint64_t P = c->n_pairs_planned;
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
@@ -301,7 +298,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nr + 1) * 4); memcpy(blob.data() + o_text, names.data(), names.size());
         upload(c->t_recs, blob, s);
         c->t_sizes.reserve((batch + 1) * 4, s); c->t_offs.reserve((batch + 1) * 8, s); c->t_scan.reserve(scan_temp_bytes(batch), s);
-        if (!c->h_t) { HIP_OK(hipHostMalloc((void**)&c->h_t, 64, hipHostMallocDefault)); HIP_OK(hipEventCreateWithFlags(&c->ev_t, hipEventDisableTiming | hipEventBlockingSync)); }
+        c->h_t.reserve(64, hipHostMallocDefault); c->ev_t.ensure(hipEventDisableTiming | hipEventBlockingSync);
         HIP_OK(hipStreamSynchronize(s));                                           // (the host blob goes)
         const uint8_t* tb = c->t_recs.as<uint8_t>();
         ta.g = c->genome.as<uint8_t>(); ta.rec_off = (const uint64_t*)tb; ta.name_off = (const uint32_t*)(tb + o_name); ta.names = (const char*)(tb + o_text); ta.n_rec = nr;
@@ -309,15 +306,15 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     }
     struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } } guard{nullptr};
     if (to_sink) {
-        if (!c->pipe) c->pipe = new SinkPipe;
-        if (!c->copy_stream) { HIP_OK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); for (int k = 0; k < 2; ++k) { HIP_OK(hipEventCreateWithFlags(&c->ev_made[k], hipEventDisableTiming)); HIP_OK(hipEventCreateWithFlags(&c->ev_d2h[k], hipEventDisableTiming)); } }
+        if (!c->pipe) c->pipe.reset(new SinkPipe);
+        c->copy_stream.ensure(hipStreamNonBlocking); for (int k = 0; k < 2; ++k) { c->ev_made[k].ensure(hipEventDisableTiming); c->ev_d2h[k].ensure(hipEventDisableTiming); }
         c->pipe->truth_fd = truth_fd.fd;
-        c->pipe->start(tg.sink, paired != 0, c->cfg.device); guard.p = c->pipe;
+        c->pipe->start(tg.sink, paired != 0, c->cfg.device); guard.p = c->pipe.get();
     }
     const bool bgzf = to_sink && tg.bgzf;
-    if (bgzf && !c->h_z) {
-        HIP_OK(hipHostMalloc((void**)&c->h_z, 64, hipHostMallocDefault)); memset(c->h_z, 0, 64);
-        for (int k = 0; k < 2; ++k) HIP_OK(hipEventCreateWithFlags(&c->ev_z[k], hipEventDisableTiming | hipEventBlockingSync));
+    if (bgzf && !c->z_crc.p) {                                                     // (z_crc: the last of the group to be made)
+        c->h_z.reserve(64, hipHostMallocDefault); memset(c->h_z, 0, 64);
+        for (int k = 0; k < 2; ++k) c->ev_z[k].ensure(hipEventDisableTiming | hipEventBlockingSync);
         std::vector<uint32_t> tabs(512); bgzf_host_tables(tabs.data(), tabs.data() + 256);
         upload(c->z_crc, tabs, s); HIP_OK(hipStreamSynchronize(s));
     }
@@ -348,10 +345,8 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     static const bool serial_pre = seam_env("SCS_READS_SERIAL") != nullptr;
     hipStream_t ps = s; bool free_rec[2] = {false, false};
     if (!serial_pre) {
-        if (!c->pre_stream) {
-            HIP_OK(hipStreamCreateWithFlags(&c->pre_stream, hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(&c->ev_plan, hipEventDisableTiming));
-            for (int k = 0; k < 2; ++k) { HIP_OK(hipEventCreateWithFlags(&c->ev_pre[k], hipEventDisableTiming)); HIP_OK(hipEventCreateWithFlags(&c->ev_free[k], hipEventDisableTiming)); }
-        }
+        c->pre_stream.ensure(hipStreamNonBlocking); c->ev_plan.ensure(hipEventDisableTiming);
+        for (int k = 0; k < 2; ++k) { c->ev_pre[k].ensure(hipEventDisableTiming); c->ev_free[k].ensure(hipEventDisableTiming); }
         ps = c->pre_stream;
         HIP_OK(hipEventRecord(c->ev_plan, s)); HIP_OK(hipStreamWaitEvent(ps, c->ev_plan, 0));   // the pair records (and everything before) are made
     }
@@ -366,10 +361,10 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
                               c->gmap, c->dtb, c->key, paired, c->pairs.as<PairRec>(), c->dsums.as<unsigned long long>() + DS_HOLES);
         }
         // the indel pass fixes every read's length, hence the record sizes and (prefix sums) the record offsets
-        c->tm_indels.begin(s);
+        c->tm[TM_INDELS].begin(s);
         launch_indels(s, pr, np, paired, c->dtb, c->key, slot, B.ev_hdr, B.ev_dat, B.sizes1, B.sizes2, B.d1f1, B.d1f2, c->flags.as<uint32_t>());
-        c->tm_indels.end(s);
-        c->tm_indels.add_units(np);
+        c->tm[TM_INDELS].end(s);
+        c->tm[TM_INDELS].add_units(np);
         exclusive_scan_sizes(s, B.sizes1, B.off1, np, c->scan_tmp.p, c->scan_tmp.cap);   // byte offsets + positions in the class lists: one scan per mate
         if (paired) exclusive_scan_sizes(s, B.sizes2, B.off2, np, c->scan_tmp.p, c->scan_tmp.cap);
         launch_read_lists(s, np, paired, B.sizes1, B.off1, B.d1f1, B.d1p1, B.sizes2, B.off2, B.d1f2, B.d1p2, B.slist1, B.slist2, B.clist1, B.clist2, B.dlist1, B.dlist2,
@@ -394,7 +389,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     struct Ship { char* p1; char* p2; uint64_t n1, n2; int dsl; uint32_t region; char* p3; uint64_t n3; };   // p3 / n3: the batch's truth SAM
     Ship pending{}; bool have_pending = false;
     auto ship = [&](Ship sh) {                                                      // D2H on the copy stream into a free pinned slot, then to the region's writer
-        SinkPipe* pp = c->pipe;
+        SinkPipe* pp = c->pipe.get();
         if (bgzf) { HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl])); sh.n1 = c->h_z[sh.dsl * 2]; sh.n2 = c->h_z[sh.dsl * 2 + 1]; }   // the blocks' totals have arrived
         const int hs = pp->acquire(sh.n1, sh.n2, sh.n3);                                   // (a pinned slot no writer holds: the host waits here when the sink is the slower side)
         if (hs < 0) throw ScsError(SCS_EIO, "sink aborted");
@@ -430,7 +425,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             seg_at.push_back(SegAt{j, bidx, o1v & OFF_MASK, o2v & OFF_MASK});
         }
         char *o1, *o2;
-        SinkPipe* pp = to_sink ? c->pipe : nullptr; const int dsl = (int)(bi & 1);
+        SinkPipe* pp = to_sink ? c->pipe.get() : nullptr; const int dsl = (int)(bi & 1);
         if (tg.device) {
             if (tot1 + b1 > tg.cap1 || tot2 + b2 > tg.cap2) throw ScsError(SCS_EOVERFLOW, "scs_yield_reads_device: output buffer too small");
             o1 = tg.d1 + tot1; o2 = tg.d2 ? tg.d2 + tot2 : nullptr;
@@ -446,12 +441,12 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             d1.reserve(want1, s); d2.reserve(want2, s);
             o1 = d1.as<char>(); o2 = d2.as<char>();
         }
-        c->tm_reads.begin(s);                                                      // the base pass writes the FASTQ text at the record offsets
+        c->tm[TM_READS].begin(s);                                                      // the base pass writes the FASTQ text at the record offsets
         launch_reads(s, c->genome.as<uint8_t>(), c->genome2.as<uint32_t>() + 16, c->semis.pool_view(), c->fulls.pool_view(), pr, np, 0,
                      c->dtb, c->d_tables.as<DevTables>(), c->key, paired, slot, B.ev_hdr, B.ev_dat,
                      B.off1, B.off2, o1, o2, c->flags.as<uint32_t>(), b1, b2, B.slist1, B.slist2, B.clist1, B.clist2, nc1, nc2, B.dlist1, B.dlist2, nd1, nd2, &c->reads_side);
-        c->tm_reads.end(s);
-        c->tm_reads.add_units(np);
+        c->tm[TM_READS].end(s);
+        c->tm[TM_READS].add_units(np);
         if (c->want_cks && !tg.device) {
             launch_text_checksum(s, o1, b1, c->d_cks.as<unsigned long long>() + 2 * (size_t)bidx);
             launch_text_checksum(s, o2, paired ? b2 : 0, c->d_cks.as<unsigned long long>() + 2 * (size_t)bidx + 1);
@@ -461,22 +456,22 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             // the batch's SAM: sizing pass + 64-bit offsets, the total to the host (it sizes the output), emit pass.  Before ev_free: the
             // passes read the batch's indel events and record offsets
             ta.pairs = pr; ta.np = np; ta.ev_hdr = B.ev_hdr; ta.ev_dat = B.ev_dat; ta.off1 = B.off1; ta.off2 = B.off2; ta.fq1 = o1; ta.fq2 = o2;
-            c->tm_truth.begin(s);
+            c->tm[TM_TRUTH].begin(s);
             launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
             exclusive_scan_u32_to_u64(s, c->t_sizes.as<uint32_t>(), c->t_offs.as<uint64_t>(), np, c->t_scan.p, c->t_scan.cap);
             HIP_OK(hipMemcpyAsync(c->h_t, c->t_offs.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, s));
             HIP_OK(hipEventRecord(c->ev_t, s));
-            c->tm_truth.end(s);
+            c->tm[TM_TRUTH].end(s);
             HIP_OK(hipEventSynchronize(c->ev_t));
             { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("truth sizing pass failed: ") + hipGetErrorString(le)); }
             t_n = *c->h_t;
             DevBuf& to = c->t_out[dsl];
             if (std::max<uint64_t>(t_n, 16) > to.cap && d2h_rec[dsl]) HIP_OK(hipEventSynchronize(c->ev_d2h[dsl]));   // the buffer is about to move: its last copy must be out
             to.reserve(std::max<uint64_t>(t_n + t_n / 16, 16), s);
-            c->tm_truth.begin(s);
+            c->tm[TM_TRUTH].begin(s);
             launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(b1 + b2, np), to.as<char>());
-            c->tm_truth.end(s);
-            c->tm_truth.add_units(np);
+            c->tm[TM_TRUTH].end(s);
+            c->tm[TM_TRUTH].add_units(np);
             t_text = to.as<char>(); truth_sum += t_n;
         }
         if (ps != s) { HIP_OK(hipEventRecord(c->ev_free[it & 1], s)); free_rec[it & 1] = true; }   // this batch's buffer set is free for the pre-pass after next
@@ -527,7 +522,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     mail_wait(c); flags_eval(c);
     if (c->want_cks && !tg.device && nbatch) { c->cks.assign((size_t)nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
     pairs_written = P - c->h_rb[2];
-    c->tm_reads.collect(); c->tm_indels.collect(); c->tm_truth.collect();
+    c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect();
     c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
     c->st.fastq_bytes[0] = tot1; c->st.fastq_bytes[1] = tot2;
     c->st.sink_bytes[0] = to_sink ? sunk1 : 0; c->st.sink_bytes[1] = to_sink ? sunk2 : 0;
@@ -546,5 +541,4 @@ void truth_check(scs_ctx* c, bool device, int writers) {
     if (writers > 1) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): needs writers <= 1 (part files are made out of record order)");
 }
 
-void sink_pipe_free(scs_ctx* c) { if (c->pipe) { c->pipe->release(); delete c->pipe; c->pipe = nullptr; } }
 }  // namespace scs

@@ -122,11 +122,9 @@ void stage_fasta_on_device(scs_ctx* c, const std::string& path_in) {
     struct Unmap { const char* b; size_t n; int fd; ~Unmap() { munmap((void*)b, n); close(fd); } } unmap{base, size, fd};
     hipStream_t s = c->stream;
     const size_t CH = 64u << 20; const uint32_t hdr_cap = 1u << 20;
-    DevBuf d_raw[2], d_kind, d_keep, d_pos, d_st, d_hdr, d_tmp; char* h_raw[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; bool ev_used[2] = {false, false};
-    struct Rel { DevBuf* b[8]; char** h; hipEvent_t* e; ~Rel() { for (DevBuf* x : b) x->release(); for (int k = 0; k < 2; ++k) { if (h[k]) (void)hipHostFree(h[k]); if (e[k]) (void)hipEventDestroy(e[k]); } } }
-        rel{{&d_raw[0], &d_raw[1], &d_kind, &d_keep, &d_pos, &d_st, &d_hdr, &d_tmp}, h_raw, ev};
+    DevBuf d_raw[2], d_kind, d_keep, d_pos, d_st, d_hdr, d_tmp; Pinned<char> h_raw[2]; Event ev[2]; bool ev_used[2] = {false, false};
     const size_t ch = std::min(CH, size);
-    for (int k = 0; k < 2; ++k) { d_raw[k].reserve(ch + 16, s); HIP_OK(hipHostMalloc((void**)&h_raw[k], ch, hipHostMallocDefault)); HIP_OK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming)); }
+    for (int k = 0; k < 2; ++k) { d_raw[k].reserve(ch + 16, s); h_raw[k].reserve(ch, hipHostMallocDefault); ev[k].ensure(hipEventDisableTiming); }
     d_kind.reserve(ch + 16, s); d_keep.reserve((ch + 2) * 4, s); d_pos.reserve((ch + 2) * 4, s); d_st.reserve(64, s); d_hdr.reserve((size_t)hdr_cap * 16, s);
     d_tmp.reserve(fasta_chunk_temp_bytes((uint32_t)ch), s);
     HIP_OK(hipMemsetAsync(d_st.p, 0, 64, s));
@@ -252,12 +250,11 @@ bool stage_fasta_slice(scs_ctx* c, const std::string& path) {
     const uint64_t n_slice = g_hi - g_lo;
     if (n_slice == 0) return false;                                                 // (more shards than fragments: nothing of its own to stage)
     c->genome.reserve(std::max<uint64_t>(n_slice, 16), s);
-    DevBuf d_ragged; struct RelR { DevBuf* b; ~RelR() { b->release(); } } relr{&d_ragged};
+    DevBuf d_ragged;
     d_ragged.reserve(16, s); HIP_OK(hipMemsetAsync(d_ragged.p, 0, 4, s));
     // record by record: the bytes of [a, b) -> pinned -> device, line ends dropped by the gather
-    const size_t CH = 64u << 20; DevBuf d_raw; char* h_raw = nullptr;
-    struct Rel { DevBuf* b; char** h; ~Rel() { b->release(); if (*h) (void)hipHostFree(*h); } } rel{&d_raw, &h_raw};
-    HIP_OK(hipHostMalloc((void**)&h_raw, CH, hipHostMallocDefault)); d_raw.reserve(CH + 16, s);
+    const size_t CH = 64u << 20; DevBuf d_raw; Pinned<char> h_raw;
+    h_raw.reserve(CH, hipHostMallocDefault); d_raw.reserve(CH + 16, s);
     for (size_t r = 0; r < ents.size() && n_slice; ++r) {
         if (ents[r].len == 0) continue;                                             // an empty record (index line "name 0 off 0 0"): nothing to read, no line geometry
         const uint64_t r0 = c->rec_off[r], r1 = r0 + ents[r].len;
@@ -305,10 +302,7 @@ void do_create_frags(scs_ctx* c) {
     {
         const size_t nfr = c->f_len.size(), o_len = nfr * 8, o_str = o_len + nfr * 4, bytes = std::max<size_t>(o_str + nfr, 16);
         if (c->frag_copy_pending) { HIP_OK(hipStreamSynchronize(c->stream)); c->frag_copy_pending = false; }
-        if (bytes > c->h_frag_cap) {
-            if (c->h_frag) HIP_OK(hipHostFree(c->h_frag));
-            c->h_frag_cap = bytes + bytes / 2; HIP_OK(hipHostMalloc((void**)&c->h_frag, c->h_frag_cap, hipHostMallocDefault));
-        }
+        c->h_frag.reserve(bytes, hipHostMallocDefault, bytes + bytes / 2);
         if (nfr) { memcpy(c->h_frag, c->f_goff.data(), nfr * 8); memcpy(c->h_frag + o_len, c->f_len.data(), nfr * 4); memcpy(c->h_frag + o_str, c->f_strand.data(), nfr); }
         c->df_blob.reserve(bytes, c->stream);
         if (nfr) { HIP_OK(hipMemcpyAsync(c->df_blob.p, c->h_frag, o_str + nfr, hipMemcpyHostToDevice, c->stream)); c->frag_copy_pending = true; }

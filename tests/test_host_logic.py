@@ -18,10 +18,31 @@ def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "scssim_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     names = set(re.findall(r"\b(scs_[a-z_0-9]+)\s*\(", hdr)) - {"scs_sink_fn"}
-    assert len(names) >= 20
+    assert len(names) >= 20 and "scs_live_resources" in names
     lib = scssim_amd.load_library()
     for n in sorted(names):
         assert hasattr(lib, n), "libscssim_hip.so does not export %s" % n
+
+
+def test_host_probes_hold_no_device_resource(golden_inputs):
+    """The census of the library's owning handles (scs_live_resources) in a fresh process that has only used host probes: nothing
+    was allocated, so all four counters -- device bytes, streams, events, pinned bytes -- are zero."""
+    import subprocess
+    import sys
+    code = """
+import sys
+sys.path.insert(0, %r)
+import scssim_amd
+assert scssim_amd.live_resources() == (0, 0, 0, 0)
+assert len(scssim_amd.bgzf_probe(b"ACGT" * 5000)) > 0
+names, total, _ = scssim_amd.fasta_probe(%r)
+assert names and total > 0
+assert scssim_amd.truth_record_probe("ACGTACGT", "IIIIIIII", "ACGTACGT", 0, 8).endswith("\\n")
+print(scssim_amd.live_resources())
+""" % (ROOT, golden_inputs["g1_hiseq2500_pe"])
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip() == "(0, 0, 0, 0)"
 
 
 def test_no_cpu_fallback_without_gpu():
