@@ -229,6 +229,16 @@ int         scs_merge_fastq_parts(const char* prefix, int paired, int keep_parts
  * scs_truth_bytes: SAM bytes of the last yield call (header included). */
 int         scs_set_truth_sam(scs_ctx* ctx, const char* path);
 int         scs_truth_bytes(const scs_ctx* ctx, uint64_t* bytes);
+/* scs_set_truth_bam(ctx, path): the same records, in the same order, from the same calls, as BAM (NULL: off, the default).  The
+ * header (magic, the SAM's header text, the record table) is made on the host, the records on the GPU, where they also become
+ * BGZF blocks; the file ends with the 28-byte BGZF end-of-file block (a job with no reads writes the header and that block).
+ * refID = index of the staged record, pos = POS - 1, mapq 255, bin = reg2bin(pos, end), CIGAR ops len << 4 | (M 0, I 1, D 2),
+ * next_refID / next_pos = refID / PNEXT - 1 (PE) or -1 / -1 (SE), SEQ 4 bits per base, QUAL = Phred, tags NM:i (int32) and MD:Z.
+ * At most one truth output per ctx: setting one while the other is on fails with SCS_EINVAL; NULL clears only its own.  A staged
+ * record of 2^29 bases or more (the BAM bin scheme ends there) and more than 2^31 - 1 records fail with SCS_EINVAL before any
+ * GPU work.  scs_truth_bytes then reports the BAM file's size (compressed; header and end-of-file block included), and
+ * scs_kernel_time(which = 6) the BAM passes with their BGZF launches. */
+int         scs_set_truth_bam(scs_ctx* ctx, const char* path);
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);
@@ -243,6 +253,13 @@ int         scs_truth_record_probe(int paired, int is_read2, uint32_t amp, uint3
                                    int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
                                    const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
                                    char* out, size_t cap, size_t* n_out);
+/* The same seam for the truth BAM: out receives the one BAM record the kernels would make, block_size included, uncompressed;
+ * refID = 0, next_refID = 0 (PE) or -1 (SE).  Same arguments, same error codes. */
+int         scs_truth_bam_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                                       int64_t pos0, int reverse, const int32_t* events, int nev,
+                                       int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                                       const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
+                                       char* out, size_t cap, size_t* n_out);
 
 /* ---- kernel-level entry points (unit parity tests; same kernels as the pipeline) ------------ */
 

@@ -271,16 +271,12 @@ def scan_probe(a0, a1=None, device=0):
     return o0 if a1 is None else (o0, o1)
 
 
-def truth_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, genome_start=0, rname="chr", amp=0, cnt=1,
-                       paired=False, is_read2=False, mate=None):
-    """Host-only: one read's truth SAM line (with its newline) through the formatter the truth kernels run.  n = window length;
-    pos0 = 0-based record coordinate of window base 0 (the rightmost base when reverse); events = [(window position, deletion?,
-    length), ...] in read orientation; seq / qual = the FASTQ record's; genome = the record's bases from genome_start on;
-    mate = (pos0, reverse, events) of the other read of a pair (paired=True)."""
+def _truth_probe(fn, seq, qual, genome, pos0, n, events, reverse, genome_start, rname, amp, cnt, paired, is_read2, mate):
     L = load_library()
-    L.scs_truth_record_probe.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int,
-                                         C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int64, C.c_uint64,
-                                         C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    f = getattr(L, fn)
+    f.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int,
+                  C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int64, C.c_uint64,
+                  C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     enc = lambda x: x.encode() if isinstance(x, str) else bytes(x)
     seq, qual, genome = enc(seq), enc(qual), enc(genome)
     ev = lambda es: (C.c_int32 * max(1, 3 * len(es)))(*[int(v) for e in es for v in e])
@@ -288,14 +284,30 @@ def truth_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, gen
     args = [int(paired), int(is_read2), amp, cnt, enc(rname), n, pos0, int(reverse), ev(events), len(events),
             m_pos, int(m_rev), ev(m_ev), len(m_ev), seq, qual, len(seq), genome, genome_start, len(genome)]
     size = C.c_size_t()
-    rc = L.scs_truth_record_probe(*args, None, 0, C.byref(size))
+    rc = f(*args, None, 0, C.byref(size))
     if rc:
-        raise ScsError(rc, "scs_truth_record_probe: not a valid alignment")
+        raise ScsError(rc, fn + ": not a valid alignment")
     out = C.create_string_buffer(size.value)
-    rc = L.scs_truth_record_probe(*args, out, size.value, C.byref(size))
+    rc = f(*args, out, size.value, C.byref(size))
     if rc:
-        raise ScsError(rc, "scs_truth_record_probe")
-    return out.raw[:size.value].decode()
+        raise ScsError(rc, fn)
+    return out.raw[:size.value]
+
+
+def truth_bam_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, genome_start=0, rname="chr", amp=0, cnt=1,
+                           paired=False, is_read2=False, mate=None):
+    """Host-only: one read's truth BAM record (bytes, block_size included, uncompressed) through the formatter the truth kernels
+    run; refID = 0, next_refID = 0 (paired) or -1.  The arguments are truth_record_probe's."""
+    return _truth_probe("scs_truth_bam_record_probe", seq, qual, genome, pos0, n, events, reverse, genome_start, rname, amp, cnt, paired, is_read2, mate)
+
+
+def truth_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, genome_start=0, rname="chr", amp=0, cnt=1,
+                       paired=False, is_read2=False, mate=None):
+    """Host-only: one read's truth SAM line (with its newline) through the formatter the truth kernels run.  n = window length;
+    pos0 = 0-based record coordinate of window base 0 (the rightmost base when reverse); events = [(window position, deletion?,
+    length), ...] in read orientation; seq / qual = the FASTQ record's; genome = the record's bases from genome_start on;
+    mate = (pos0, reverse, events) of the other read of a pair (paired=True)."""
+    return _truth_probe("scs_truth_record_probe", seq, qual, genome, pos0, n, events, reverse, genome_start, rname, amp, cnt, paired, is_read2, mate).decode()
 
 
 def fasta_probe(path):
@@ -529,8 +541,13 @@ class GenReads:
         self._L.scs_set_truth_sam.argtypes = [C.c_void_p, C.c_char_p]
         self._ck(self._L.scs_set_truth_sam(self._ctx, os.fsencode(path) if path is not None else None))
 
+    def set_truth_bam(self, path):
+        """The same records as BAM, made and compressed on the GPU (None: off).  One truth output per ctx: fails while the SAM is on."""
+        self._L.scs_set_truth_bam.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_set_truth_bam(self._ctx, os.fsencode(path) if path is not None else None))
+
     def truth_bytes(self):
-        """Bytes of the truth SAM the last yield call wrote (header included)."""
+        """Bytes of the truth SAM (header included) or BAM (compressed, header and end-of-file block included) the last yield call wrote."""
         self._L.scs_truth_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         n = C.c_uint64()
         self._ck(self._L.scs_truth_bytes(self._ctx, C.byref(n)))

@@ -248,6 +248,10 @@ struct scs_ctx {
     // and the batch's total, read back through a pinned word behind ev_t
     std::string truth_path; uint64_t truth_bytes = 0;
     DevBuf t_sizes, t_offs, t_scan, t_out[2], t_recs; Pinned<uint64_t> h_t; Event ev_t;
+    // truth BAM (scs_set_truth_bam): truth_path names a BAM; t_out then holds the batch's binary records, which become BGZF blocks in
+    // tz_out (plans / sizes / offsets of their own); the blocks' total reaches the host through h_tz[slot] behind ev_z (FASTQ BGZF on) or ev_tz
+    bool truth_bam = false;
+    DevBuf tz_plan, tz_sizes, tz_offs, tz_out[2]; Pinned<uint32_t> h_tz; Event ev_tz[2];
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)

@@ -237,7 +237,7 @@ void exclusive_scan_u32_pair(hipStream_t s, const uint32_t* in0, uint32_t* out0,
 void exclusive_scan_sizes(hipStream_t s, const uint32_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes);
 void exclusive_scan_u32_to_u64(hipStream_t s, const uint32_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes);
 
-// ---- truth SAM of a batch (scs_k_truth.hip): sizing pass -> 64-bit offsets -> emit pass, after the batch's k_reads
+// ---- truth SAM / BAM of a batch (scs_k_truth.hip): sizing pass -> 64-bit offsets -> emit pass, after the batch's k_reads
 struct TruthArgs {
     const PairRec* pairs; uint32_t np; int paired;
     const uint32_t* ev_hdr; const uint4* ev_dat;           // the batch's indel pass
@@ -249,5 +249,9 @@ struct TruthArgs {
 void launch_truth_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);                 // SAM bytes per pair (both mates); offsets: exclusive_scan_u32_to_u64
 uint32_t truth_pairs_per_block(uint64_t fq_bytes, uint32_t np);                             // the emit pass' LDS run, from the batch's FASTQ bytes
 void launch_truth_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, char* out);
+// the same passes for the truth BAM: BAM bytes per pair; the records (lds: the emit pass' LDS run in bytes, 0 = all it has)
+void launch_truth_bam_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);
+uint32_t truth_bam_pairs_per_block(uint64_t fq_bytes, uint32_t np);
+void launch_truth_bam_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, uint32_t lds, char* out);
 
 }  // namespace scs

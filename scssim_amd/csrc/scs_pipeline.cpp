@@ -44,7 +44,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_READSLOT) m += " read slot (indel-extended read longer than the slot)";
         if (f & FLAG_INTERNAL) m += " internal";
         if (f & FLAG_KEYSPACE) m += " primer budget of a fragment beyond 2^20 (-p / -r far outside the reference's ranges)";
-        if (f & FLAG_TRUTH) m += " truth SAM (a read with more than 32 indel events, or pair flags that are not a strand)";
+        if (f & FLAG_TRUTH) m += " truth SAM / BAM (a read with more than 32 indel events, pair flags that are not a strand, or a pair whose BAM records outgrow the emit pass' LDS)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }
@@ -298,7 +298,21 @@ int scs_batch_checksums(const scs_ctx* c, uint64_t* out, size_t cap, size_t* n_b
 }
 int scs_get_stats(const scs_ctx* c, scs_stats* out) { if (!c || !out) return SCS_EINVAL; *out = c->st; return SCS_OK; }
 
-int scs_set_truth_sam(scs_ctx* c, const char* path) { if (!c) return SCS_EINVAL; c->truth_path = path ? path : ""; return SCS_OK; }
+// one truth output per ctx: truth_path is the SAM's or (truth_bam) the BAM's; NULL clears only the caller's own
+static int set_truth(scs_ctx* c, const char* path, bool bam) {
+    if (!c) return SCS_EINVAL;
+    const bool on = !c->truth_path.empty();
+    if (path && on && c->truth_bam != bam) {
+        c->err = bam ? "scs_set_truth_bam: the truth SAM is on (scs_set_truth_sam); one truth output per ctx: clear it with scs_set_truth_sam(ctx, NULL) first"
+                     : "scs_set_truth_sam: the truth BAM is on (scs_set_truth_bam); one truth output per ctx: clear it with scs_set_truth_bam(ctx, NULL) first";
+        return SCS_EINVAL;
+    }
+    if (path) { c->truth_path = path; c->truth_bam = bam; }
+    else if (!on || c->truth_bam == bam) { c->truth_path.clear(); c->truth_bam = false; }
+    return SCS_OK;
+}
+int scs_set_truth_sam(scs_ctx* c, const char* path) { return set_truth(c, path, false); }
+int scs_set_truth_bam(scs_ctx* c, const char* path) { return set_truth(c, path, true); }
 int scs_truth_bytes(const scs_ctx* c, uint64_t* bytes) { if (!c || !bytes) return SCS_EINVAL; *bytes = c->truth_bytes; return SCS_OK; }
 int scs_download_frags(scs_ctx* c, uint64_t* goff, uint32_t* len, int8_t* strand) {
     return guarded(c, [&] {

@@ -3,14 +3,12 @@
 // scans, DevBuf, Philox, det_log, Profile::predict), and the census of live device resources.  Nothing here is on a job's path.
 #include "scs_ctx.h"
 
-extern "C" {
-
-// host-only: one read's record through the formatter the truth kernels run (scs_truth.h)
-int scs_truth_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
-                           int64_t pos0, int reverse, const int32_t* events, int nev,
-                           int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
-                           const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
-                           char* out, size_t cap, size_t* n_out) {
+// host-only: one read's record through the formatter the truth kernels run (scs_truth.h), as SAM text or as a BAM record
+static int truth_probe(bool bam, int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                       int64_t pos0, int reverse, const int32_t* events, int nev,
+                       int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                       const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
+                       char* out, size_t cap, size_t* n_out) {
     if (!rname || !seq || !qual || !genome || !n_out || n <= 0 || nev < 0 || mate_nev < 0 || (nev && !events) || (paired && mate_nev && !mate_events)) return SCS_EINVAL;
     auto pack = [](const int32_t* e, int k, std::vector<uint32_t>& v) {
         for (int i = 0; i < k; ++i) {
@@ -36,11 +34,38 @@ int scs_truth_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt,
         char seq(int i) const { return s[i]; } char qual(int i) const { return q[i]; }
         char gen(int64_t x) const { const char ch = g[x - g0]; return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' ? ch : ch == 'a' ? 'A' : ch == 'c' ? 'C' : ch == 'g' ? 'G' : ch == 't' ? 'T' : 'N'; }
     } src{seq, qual, genome, genome_start};
-    struct VecOut { std::string t; void put(char ch) { t.push_back(ch); } } o;
-    truth_record(o, a, li, src);
+    struct VecOut {
+        std::string t;
+        void put(char ch) { t.push_back(ch); }
+        uint32_t pos() const { return (uint32_t)t.size(); }
+        void poke32(uint32_t at, uint32_t v) { for (int k = 0; k < 4; ++k) t[at + k] = (char)(v >> (8 * k)); }
+    } o;
+    if (bam) {
+        truth_bam_record(o, a, li, src, 0);
+        if (o.t.size() != truth_bam_size(a, li, src)) return SCS_EDEVICE;              // (the sizing pass' arithmetic and the formatter must agree)
+    } else truth_record(o, a, li, src);
     *n_out = o.t.size();
     if (out) { if (o.t.size() > cap) return SCS_EOVERFLOW; memcpy(out, o.t.data(), o.t.size()); }
     return SCS_OK;
+}
+
+extern "C" {
+
+int scs_truth_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                           int64_t pos0, int reverse, const int32_t* events, int nev,
+                           int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                           const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
+                           char* out, size_t cap, size_t* n_out) {
+    return truth_probe(false, paired, is_read2, amp, cnt, rname, n, pos0, reverse, events, nev, mate_pos0, mate_reverse, mate_events, mate_nev,
+                       seq, qual, len, genome, genome_start, genome_len, out, cap, n_out);
+}
+int scs_truth_bam_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                               int64_t pos0, int reverse, const int32_t* events, int nev,
+                               int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                               const char* seq, const char* qual, int len, const char* genome, int64_t genome_start, uint64_t genome_len,
+                               char* out, size_t cap, size_t* n_out) {
+    return truth_probe(true, paired, is_read2, amp, cnt, rname, n, pos0, reverse, events, nev, mate_pos0, mate_reverse, mate_events, mate_nev,
+                       seq, qual, len, genome, genome_start, genome_len, out, cap, n_out);
 }
 
 int scs_predict_batch(scs_ctx* c, const uint8_t* windows, size_t n_reads, const uint64_t* uids, const uint32_t* attempts, const uint8_t* is_read1,

@@ -163,13 +163,13 @@ struct NumaScope {
 
 struct SinkPipe {
     std::vector<int> local_cpus;                                                   // of the device's NUMA node (gpu_local_cpus)
-    struct Slot { Pinned<char> h[3]; Event ev; bool busy = false; };               // h[2]: the batch's truth SAM
+    struct Slot { Pinned<char> h[3]; Event ev; bool busy = false; };               // h[2]: the batch's truth SAM (or its BAM blocks)
     struct Job { int slot, region; size_t n1, n2, n3; };
     struct Writer { std::thread th; std::vector<Job> q; };
     std::vector<Slot> slots; std::vector<Writer> writers;
     std::mutex mu; std::condition_variable cv; bool done = false, failed = false;
     BatchSink* sink = nullptr; bool paired = true; int device = 0;
-    int truth_fd = -1;                                                             // the truth SAM (one writer: batch order), or -1
+    int truth_fd = -1;                                                             // the truth SAM / BAM (one writer: batch order), or -1
     static bool write_all(int fd, const char* p, size_t n) {
         while (n) { const ssize_t w = ::write(fd, p, n); if (w < 0 && errno == EINTR) continue; if (w <= 0) return false; p += w; n -= (size_t)w; }
         return true;
@@ -236,8 +236,14 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     HIP_OK(hipMemsetAsync(c->dsums.as<unsigned long long>() + DS_HOLES, 0, 8, s));
     const bool to_sink = !tg.device && tg.sink;
     const int regions = to_sink ? std::max(1, tg.sink->regions) : 1;
-    const bool truth = !c->truth_path.empty();
-    if (truth) { truth_check(c, tg.device, to_sink ? tg.sink->writers : 1); if (!to_sink) throw ScsError(SCS_EINVAL, "truth SAM: the reads must go to a sink"); }
+    const bool truth = !c->truth_path.empty(), bam = truth && c->truth_bam;
+    const std::string tname = bam ? "truth BAM" : "truth SAM";
+    if (truth) { truth_check(c, tg.device, to_sink ? tg.sink->writers : 1); if (!to_sink) throw ScsError(SCS_EINVAL, tname + ": the reads must go to a sink"); }
+    if (bam) {                                                                     // what BAM's int32 fields and its bin scheme cannot hold: refused before any GPU work
+        for (size_t r = 0; r < c->rec_len.size(); ++r)
+            if (c->rec_len[r] >= (1ull << 29)) throw ScsError(SCS_EINVAL, "truth BAM (scs_set_truth_bam): record " + c->recs[r].name + " has 2^29 bases or more (the BAM bin scheme ends there); the truth SAM (scs_set_truth_sam) has no such limit");
+        if ((paired ? 2 * P : P) > 0x7FFFFFFFull) throw ScsError(SCS_EINVAL, "truth BAM (scs_set_truth_bam): more than 2^31 - 1 records");
+    }
     // pairs per batch: 8 M with the text staying in HBM (5 GB of text per batch: the base pass' grids are long enough for their tails and
     // the per-batch pre-pass not to matter: 2 M -> 8 M gave -11 % on the stage).  Towards a sink a batch fills a pinned slot and every
     // writer holds one: as large as leaves each part file of each generation a couple of batches -- 2 M pairs (1.3 GB of text) on a
@@ -281,7 +287,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     if (truth) {
         // the header first, then the batches' records from the pipe's writer; the kernels' record table: starts, name offsets, names
         truth_fd.fd = ::open(c->truth_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
-        if (truth_fd.fd < 0) throw ScsError(SCS_EIO, "truth SAM: can not open " + c->truth_path + ": " + strerror(errno));
+        if (truth_fd.fd < 0) throw ScsError(SCS_EIO, tname + ": can not open " + c->truth_path + ": " + strerror(errno));
         std::string hd = "@HD\tVN:1.6\tSO:unsorted\n";
         const uint32_t nr = (uint32_t)c->recs.size();
         std::vector<uint64_t> roff(nr + 1, 0); std::vector<uint32_t> noff(nr + 1, 0); std::string names;
@@ -291,7 +297,15 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             names += c->recs[r].name; noff[r + 1] = (uint32_t)names.size();
         }
         hd += "@PG\tID:scssim\tPN:scssim\n";
-        if (!SinkPipe::write_all(truth_fd.fd, hd.data(), hd.size())) throw ScsError(SCS_EIO, "truth SAM: writing " + c->truth_path + " failed");
+        if (bam) {                                                                 // magic, l_text, the SAM's header text, n_ref, per record l_name / name / l_ref: BGZF made on the host
+            std::string bh = "BAM\1";
+            auto le32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) bh.push_back((char)(v >> (8 * k))); };
+            le32((uint32_t)hd.size()); bh += hd; le32(nr);
+            for (uint32_t r = 0; r < nr; ++r) { le32((uint32_t)c->recs[r].name.size() + 1u); bh += c->recs[r].name; bh.push_back('\0'); le32((uint32_t)c->rec_len[r]); }
+            std::vector<uint8_t> z; bgzf_compress_host((const uint8_t*)bh.data(), bh.size(), BGZF_LDS_OUT, z);
+            hd.assign((const char*)z.data(), z.size());
+        }
+        if (!SinkPipe::write_all(truth_fd.fd, hd.data(), hd.size())) throw ScsError(SCS_EIO, tname + ": writing " + c->truth_path + " failed");
         truth_sum = hd.size();
         const size_t o_name = (size_t)(nr + 1) * 8, o_text = o_name + (size_t)(nr + 1) * 4;
         std::vector<uint8_t> blob(o_text + names.size() + 16, 0);
@@ -299,6 +313,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         upload(c->t_recs, blob, s);
         c->t_sizes.reserve((batch + 1) * 4, s); c->t_offs.reserve((batch + 1) * 8, s); c->t_scan.reserve(scan_temp_bytes(batch), s);
         c->h_t.reserve(64, hipHostMallocDefault); c->ev_t.ensure(hipEventDisableTiming | hipEventBlockingSync);
+        if (bam) { c->h_tz.reserve(64, hipHostMallocDefault); memset(c->h_tz, 0, 64); for (int k = 0; k < 2; ++k) c->ev_tz[k].ensure(hipEventDisableTiming | hipEventBlockingSync); }
         HIP_OK(hipStreamSynchronize(s));                                           // (the host blob goes)
         const uint8_t* tb = c->t_recs.as<uint8_t>();
         ta.g = c->genome.as<uint8_t>(); ta.rec_off = (const uint64_t*)tb; ta.name_off = (const uint32_t*)(tb + o_name); ta.names = (const char*)(tb + o_text); ta.n_rec = nr;
@@ -312,9 +327,11 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         c->pipe->start(tg.sink, paired != 0, c->cfg.device); guard.p = c->pipe.get();
     }
     const bool bgzf = to_sink && tg.bgzf;
-    if (bgzf && !c->z_crc.p) {                                                     // (z_crc: the last of the group to be made)
+    if (bgzf) {
         c->h_z.reserve(64, hipHostMallocDefault); memset(c->h_z, 0, 64);
         for (int k = 0; k < 2; ++k) c->ev_z[k].ensure(hipEventDisableTiming | hipEventBlockingSync);
+    }
+    if ((bgzf || bam) && !c->z_crc.p) {                                            // the CRC tables of the BGZF kernels (FASTQ blocks and the truth BAM's)
         std::vector<uint32_t> tabs(512); bgzf_host_tables(tabs.data(), tabs.data() + 256);
         upload(c->z_crc, tabs, s); HIP_OK(hipStreamSynchronize(s));
     }
@@ -386,11 +403,16 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     }
     bool d2h_rec[2] = {false, false};
     uint64_t sunk1 = 0, sunk2 = 0;                                                  // bytes handed to the sink (= the text's, or its BGZF blocks')
-    struct Ship { char* p1; char* p2; uint64_t n1, n2; int dsl; uint32_t region; char* p3; uint64_t n3; };   // p3 / n3: the batch's truth SAM
+    struct Ship { char* p1; char* p2; uint64_t n1, n2; int dsl; uint32_t region; char* p3; uint64_t n3; };   // p3 / n3: the batch's truth SAM (BAM: its blocks, n3 known once their total has arrived)
+    static const uint32_t bam_lds = seam_env("SCS_TEST_TRUTH_LDS") ? (uint32_t)atoi(seam_env("SCS_TEST_TRUTH_LDS")) : 0u;   // tests: the BAM emit pass cuts its runs
     Ship pending{}; bool have_pending = false;
     auto ship = [&](Ship sh) {                                                      // D2H on the copy stream into a free pinned slot, then to the region's writer
         SinkPipe* pp = c->pipe.get();
         if (bgzf) { HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl])); sh.n1 = c->h_z[sh.dsl * 2]; sh.n2 = c->h_z[sh.dsl * 2 + 1]; }   // the blocks' totals have arrived
+        if (bam && sh.p3) {                                                        // the BAM blocks' total: behind ev_z with the FASTQ blocks', or behind its own event
+            if (!bgzf) HIP_OK(hipEventSynchronize(c->ev_tz[sh.dsl]));
+            sh.n3 = c->h_tz[sh.dsl]; truth_sum += sh.n3;
+        }
         const int hs = pp->acquire(sh.n1, sh.n2, sh.n3);                                   // (a pinned slot no writer holds: the host waits here when the sink is the slower side)
         if (hs < 0) throw ScsError(SCS_EIO, "sink aborted");
         SinkPipe::Slot& H = pp->slots[(size_t)hs];
@@ -457,7 +479,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             // passes read the batch's indel events and record offsets
             ta.pairs = pr; ta.np = np; ta.ev_hdr = B.ev_hdr; ta.ev_dat = B.ev_dat; ta.off1 = B.off1; ta.off2 = B.off2; ta.fq1 = o1; ta.fq2 = o2;
             c->tm[TM_TRUTH].begin(s);
-            launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
+            if (bam) launch_truth_bam_size(s, ta, c->t_sizes.as<uint32_t>()); else launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
             exclusive_scan_u32_to_u64(s, c->t_sizes.as<uint32_t>(), c->t_offs.as<uint64_t>(), np, c->t_scan.p, c->t_scan.cap);
             HIP_OK(hipMemcpyAsync(c->h_t, c->t_offs.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, s));
             HIP_OK(hipEventRecord(c->ev_t, s));
@@ -469,10 +491,28 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
             if (std::max<uint64_t>(t_n, 16) > to.cap && d2h_rec[dsl]) HIP_OK(hipEventSynchronize(c->ev_d2h[dsl]));   // the buffer is about to move: its last copy must be out
             to.reserve(std::max<uint64_t>(t_n + t_n / 16, 16), s);
             c->tm[TM_TRUTH].begin(s);
-            launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(b1 + b2, np), to.as<char>());
+            if (!bam) {
+                launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(b1 + b2, np), to.as<char>());
+                t_text = to.as<char>(); truth_sum += t_n;
+            } else if (t_n) {
+                // the batch's records, then BGZF over them where they lie (the FASTQ blocks' kernels); the blocks' total to h_tz[dsl]
+                launch_truth_bam_emit(s, ta, c->t_offs.as<uint64_t>(), truth_bam_pairs_per_block(b1 + b2, np), bam_lds, to.as<char>());
+                if (bgzf_bound(t_n) > 0xFFFFFFF0ull) throw ScsError(SCS_EOVERFLOW, "truth BAM: a batch's records exceed 4 GB");
+                const uint32_t nblk = bgzf_blocks(t_n);
+                c->tz_plan.reserve(std::max<size_t>((size_t)nblk * BGZF_PLAN_BYTES, 16), s); c->tz_sizes.reserve(((size_t)nblk + 2) * 4, s); c->tz_offs.reserve(((size_t)nblk + 2) * 4, s);
+                DevBuf& zo = c->tz_out[dsl];
+                if (bgzf_bound(t_n) > zo.cap && d2h_rec[dsl]) HIP_OK(hipEventSynchronize(c->ev_d2h[dsl]));
+                zo.reserve(bgzf_bound(t_n), s);
+                launch_bgzf_plan(s, to.as<char>(), t_n, c->tz_plan.as<uint8_t>(), c->tz_sizes.as<uint32_t>());
+                exclusive_scan_u32(s, c->tz_sizes.as<uint32_t>(), c->tz_offs.as<uint32_t>(), nblk, nullptr, 0);
+                launch_bgzf_emit(s, to.as<char>(), t_n, c->tz_plan.as<uint8_t>(), c->tz_sizes.as<uint32_t>(), c->tz_offs.as<uint32_t>(),
+                                 c->z_crc.as<uint32_t>(), c->z_crc.as<uint32_t>() + 256, zo.as<char>(), 0);
+                HIP_OK(hipMemcpyAsync(c->h_tz + dsl, c->tz_offs.as<uint32_t>() + nblk, 4, hipMemcpyDeviceToHost, s));
+                if (!bgzf) HIP_OK(hipEventRecord(c->ev_tz[dsl], s));
+                t_text = zo.as<char>(); t_n = 0;                                     // (n3: ship reads it from h_tz)
+            }
             c->tm[TM_TRUTH].end(s);
             c->tm[TM_TRUTH].add_units(np);
-            t_text = to.as<char>(); truth_sum += t_n;
         }
         if (ps != s) { HIP_OK(hipEventRecord(c->ev_free[it & 1], s)); free_rec[it & 1] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
@@ -517,8 +557,13 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     // (Amplicon.cpp:484-489): k_plan_pairs counted them on the device
     { Mail m; m.add(c->flags.p, 4, 30); m.add(c->dsums.as<unsigned long long>() + DS_HOLES, 8, 2); mail_post(c, m, true); }   // flags + hole count land before the final synchronize: no second round trip
     HIP_OK(hipStreamSynchronize(s));
-    if (to_sink) { HIP_OK(hipStreamSynchronize(c->copy_stream)); guard.p = nullptr; const bool ok = c->pipe->finish(); c->pipe->truth_fd = -1; if (!ok) throw ScsError(SCS_EIO, truth ? "sink aborted (or the truth SAM could not be written)" : "sink aborted"); }
-    if (truth) { const int fd = truth_fd.fd; truth_fd.fd = -1; if (::close(fd) != 0) throw ScsError(SCS_EIO, "truth SAM: closing " + c->truth_path + " failed"); c->truth_bytes = truth_sum; }
+    if (to_sink) { HIP_OK(hipStreamSynchronize(c->copy_stream)); guard.p = nullptr; const bool ok = c->pipe->finish(); c->pipe->truth_fd = -1; if (!ok) throw ScsError(SCS_EIO, truth ? "sink aborted (or the " + tname + " could not be written)" : std::string("sink aborted")); }
+    if (bam) {                                                                     // the BGZF end-of-file block (SAM specification, section 4.1.2)
+        static const unsigned char eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (!SinkPipe::write_all(truth_fd.fd, (const char*)eof, 28)) throw ScsError(SCS_EIO, "truth BAM: writing " + c->truth_path + " failed");
+        truth_sum += 28;
+    }
+    if (truth) { const int fd = truth_fd.fd; truth_fd.fd = -1; if (::close(fd) != 0) throw ScsError(SCS_EIO, tname + ": closing " + c->truth_path + " failed"); c->truth_bytes = truth_sum; }
     mail_wait(c); flags_eval(c);
     if (c->want_cks && !tg.device && nbatch) { c->cks.assign((size_t)nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
     pairs_written = P - c->h_rb[2];
@@ -536,9 +581,10 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
 
 void truth_check(scs_ctx* c, bool device, int writers) {
     if (c->truth_path.empty()) return;
-    if (device) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): not available with scs_yield_reads_device; turn it off with scs_set_truth_sam(ctx, NULL)");
-    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): not available for a sharded job (shard_count > 1)");
-    if (writers > 1) throw ScsError(SCS_EINVAL, "truth SAM (scs_set_truth_sam): needs writers <= 1 (part files are made out of record order)");
+    const std::string fn = c->truth_bam ? "scs_set_truth_bam" : "scs_set_truth_sam", what = (c->truth_bam ? "truth BAM (" : "truth SAM (") + fn + ")";
+    if (device) throw ScsError(SCS_EINVAL, what + ": not available with scs_yield_reads_device; turn it off with " + fn + "(ctx, NULL)");
+    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, what + ": not available for a sharded job (shard_count > 1)");
+    if (writers > 1) throw ScsError(SCS_EINVAL, what + ": needs writers <= 1 (part files are made out of record order)");
 }
 
 }  // namespace scs

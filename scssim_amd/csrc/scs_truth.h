@@ -1,6 +1,7 @@
 // scs_truth.h -- the SAM record of a read's true alignment (scs_set_truth_sam).  One formatter for the
 // device passes (scs_k_truth.hip: sizing with a counting sink, emit into LDS) and the host probe (scs_truth_record_probe), so the
-// test seam runs the code the kernels run.
+// test seam runs the code the kernels run.  The BAM record of the same alignment (scs_set_truth_bam) is at the end: the same walks,
+// BAM's encoding, and its own probe (scs_truth_bam_record_probe).
 //
 // A read's alignment comes from its indel events alone (Profile::predict, Profile.cpp:1605-1650): in read orientation the window
 // bases cur .. j of an insertion at j are M, then its k inserted bases I; a deletion of k bases at j is j - cur bases M, then k D
@@ -141,5 +142,77 @@ SCS_HD void truth_record(Out& o, const TruthAln& a, const TruthLine& li, const S
 }
 
 struct TruthCount { uint64_t n = 0; SCS_HD void put(char) { ++n; } };
+
+// ---- the same alignment as one BAM record (scs_set_truth_bam): the SAM's values in BAM's encoding, from the same walks
+// a read's MD string through o.put; returns its NM (the SAM record's second walk, counting as it prints)
+template <class Out, class Src>
+SCS_HD uint32_t truth_md(Out& o, const TruthAln& a, const Src& src) {
+    const int q = a.qlen; uint32_t nm = 0, run = 0; int64_t g = a.lo; int qi = 0;
+    truth_cigar_walk(a, [&](char k, uint32_t l) {
+        if (k == 'I') { qi += (int)l; nm += l; return; }
+        if (k == 'D') {
+            nm += l; truth_num(o, run); run = 0; o.put('^');
+            for (uint32_t t = 0; t < l; ++t) o.put(src.gen(g++));
+            return;
+        }
+        for (uint32_t t = 0; t < l; ++t, ++qi, ++g) {
+            const char r = a.rev ? truth_comp(src.seq(q - 1 - qi)) : src.seq(qi), gc = src.gen(g);
+            if (r == gc) { ++run; continue; }
+            ++nm; truth_num(o, run); o.put(gc); run = 0;
+        }
+    });
+    truth_num(o, run);
+    return nm;
+}
+
+SCS_HD uint32_t truth_digits(uint32_t v) { uint32_t d = 1; while (v >= 10u) { v /= 10u; ++d; } return d; }
+// bin of the 0-based region [beg, end) (SAM specification, section 5.3)
+SCS_HD uint32_t truth_reg2bin(int64_t beg, int64_t end) {
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+SCS_HD uint32_t truth_base4(char c) { return c == 'A' ? 1u : c == 'C' ? 2u : c == 'G' ? 4u : c == 'T' ? 8u : 15u; }
+
+// bytes of the record below (block_size included): closed-form but for the CIGAR's op count and the MD string's length
+template <class Src>
+SCS_HD uint32_t truth_bam_size(const TruthAln& a, const TruthLine& li, const Src& src) {
+    uint32_t ncig = 0; truth_cigar_walk(a, [&](char, uint32_t) { ++ncig; });
+    TruthCount md; truth_md(md, a, src);
+    const uint32_t q = (uint32_t)a.qlen;
+    return 36u + truth_digits(li.amp) + 1u + truth_digits(li.cnt) + 1u + 4u * ncig + (q + 1u) / 2u + q + 7u + 3u + (uint32_t)md.n + 1u;
+}
+
+template <class Out> SCS_HD void truth_le16(Out& o, uint32_t v) { o.put((uint8_t)v); o.put((uint8_t)(v >> 8)); }
+template <class Out> SCS_HD void truth_le32(Out& o, uint32_t v) { truth_le16(o, v); truth_le16(o, v >> 16); }
+
+// The BAM record of a read, block_size first.  o: put(uint8_t), pos() = bytes put so far, poke32(at, v) = four little-endian
+// bytes over the ones put at `at` (block_size and NM are known once the tags are written).  ref_id: index of li's record
+template <class Out, class Src>
+SCS_HD void truth_bam_record(Out& o, const TruthAln& a, const TruthLine& li, const Src& src, int32_t ref_id) {
+    const int q = a.qlen; const uint32_t at0 = o.pos();
+    uint32_t ncig = 0; truth_cigar_walk(a, [&](char, uint32_t) { ++ncig; });
+    const int64_t pos = a.lo - li.rec0;
+    truth_le32(o, 0u); truth_le32(o, (uint32_t)ref_id); truth_le32(o, (uint32_t)pos);
+    o.put((uint8_t)(truth_digits(li.amp) + 1u + truth_digits(li.cnt) + 1u)); o.put((uint8_t)255);
+    truth_le16(o, truth_reg2bin(pos, a.hi - li.rec0 + 1)); truth_le16(o, ncig); truth_le16(o, li.flag); truth_le32(o, (uint32_t)q);
+    truth_le32(o, li.paired ? (uint32_t)ref_id : 0xFFFFFFFFu); truth_le32(o, li.paired ? (uint32_t)(li.mate_lo - li.rec0) : 0xFFFFFFFFu);
+    truth_le32(o, li.paired ? (uint32_t)(int32_t)li.tlen : 0u);
+    truth_num(o, li.amp); o.put('#'); truth_num(o, li.cnt); o.put((uint8_t)0);
+    truth_cigar_walk(a, [&](char k, uint32_t l) { truth_le32(o, (l << 4) | (k == 'M' ? 0u : k == 'I' ? 1u : 2u)); });
+    for (int i = 0; i < q; i += 2) {
+        const uint32_t hi4 = truth_base4(a.rev ? truth_comp(src.seq(q - 1 - i)) : src.seq(i));
+        const uint32_t lo4 = i + 1 < q ? truth_base4(a.rev ? truth_comp(src.seq(q - 2 - i)) : src.seq(i + 1)) : 0u;
+        o.put((uint8_t)((hi4 << 4) | lo4));
+    }
+    for (int i = 0; i < q; ++i) o.put((uint8_t)(src.qual(a.rev ? q - 1 - i : i) - 33));
+    o.put('N'); o.put('M'); o.put('i'); const uint32_t at_nm = o.pos(); truth_le32(o, 0u);
+    o.put('M'); o.put('D'); o.put('Z'); const uint32_t nm = truth_md(o, a, src); o.put((uint8_t)0);
+    o.poke32(at_nm, nm); o.poke32(at0, o.pos() - at0 - 4u);
+}
 
 }  // namespace scs

@@ -1,0 +1,223 @@
+"""GPU tests of the truth BAM (scs_set_truth_bam / scssim genreads --truth-bam).  The reference of every comparison is the
+project's own truth SAM of the same job (tests/test_gpu_truth.py pins that one to the genome and the lineage): a child process
+runs the job twice on one ctx with the same seed, once with set_truth_sam and once with set_truth_bam, and the checks here decode
+the BAM with tests/bam_cases.py and compare it with the SAM record for record, column for column.  Run with `-m gpu`."""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+from conftest import ROOT, seams_env
+
+from bam_cases import read_bam, reg2bin
+
+pytestmark = pytest.mark.gpu
+
+_CHILD = r'''
+import json, os, sys
+sys.path.insert(0, %(root)r)
+import scssim_amd
+a = json.loads(%(args)r)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a.get("ber", 3.4e-4))
+out = a["out"]
+g.create_frags(); g.amplify(); g.allocate_reads(0)
+res = {}
+for kind in ("sam", "bam"):
+    g.set_truth_sam(out + ".sam" if kind == "sam" else None)
+    g.set_truth_bam(out + ".bam" if kind == "bam" else None)
+    if a["sink"] == "files":
+        g.yield_reads_files(out + "_" + kind, 1, bgzf=True)
+    else:
+        f1, f2 = g.yield_reads()
+        open(out + "_" + kind + "_1.fq", "wb").write(f1); open(out + "_" + kind + "_2.fq", "wb").write(f2)
+    res[kind] = dict(truth_bytes=g.truth_bytes(), pairs=g.stats()["pairs_written"], k_truth=g.kernel_times()["k_truth"])
+g.close()
+res["live"] = list(scssim_amd.live_resources())
+print("RESULT " + json.dumps(res))
+'''
+
+
+def _run(tmp_path, env=None, timeout=300, **a):
+    a.setdefault("out", str(tmp_path / "job"))
+    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ),
+                       capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return a["out"], json.loads(r.stdout.split("RESULT ")[1])
+
+
+def check_bam_equals_sam(bam_path, sam_path, paired, truth_bytes=None):
+    """The decoded BAM against the SAM: header text, reference table, every record's 13 columns in order; the fields BAM adds
+    (bin, l_read_name, block_size, next_refID) against their definitions.  read_bam asserts the BGZF framing.  Returns the records."""
+    bam = read_bam(bam_path)
+    lines = open(sam_path).read().split("\n")[:-1]
+    hdr = [ln for ln in lines if ln.startswith("@")]
+    sam = [ln.split("\t") for ln in lines[len(hdr):]]
+    assert bam["text"] == "".join(h + "\n" for h in hdr)
+    assert ["@SQ\tSN:%s\tLN:%d" % r for r in bam["refs"]] == hdr[1:-1]
+    recs = bam["records"]
+    assert len(recs) == len(sam)
+    names = {r[0]: i for i, r in enumerate(bam["refs"])}
+    for i, (b, s) in enumerate(zip(recs, sam)):
+        assert b["cols"] == s, (i, b["cols"], s)
+        assert b["refID"] == names[s[2]] and b["block_size"] == b["length"] - 4 and b["l_read_name"] == len(s[0]) + 1 and b["mapq"] == 255
+        assert b["bin"] == reg2bin(b["pos"], b["pos"] + b["span"])
+        assert (b["next_refID"], b["next_pos"]) == ((b["refID"], int(s[7]) - 1) if paired else (-1, -1))
+        assert [(t, ty) for t, ty, _ in b["tags"]] == [("NM", "i"), ("MD", "Z")]
+    if truth_bytes is not None:
+        assert truth_bytes == bam["size"] == os.path.getsize(bam_path)
+    return bam
+
+
+def _same_fastq(out, sink, paired=True):
+    for m in (("_1", "_2") if paired else ("_1",)):
+        ext = ".fq.gz" if sink == "files" else ".fq"
+        a, b = open(out + "_sam" + m + ext, "rb").read(), open(out + "_bam" + m + ext, "rb").read()
+        assert a == b and len(a) > 0
+
+
+def _check_job(out, res, paired, sink="callback", min_records=1000):
+    bam = check_bam_equals_sam(out + ".bam", out + ".sam", paired, res["bam"]["truth_bytes"])
+    _same_fastq(out, sink, paired)
+    assert res["sam"]["truth_bytes"] == os.path.getsize(out + ".sam")
+    assert len(bam["records"]) == res["bam"]["pairs"] * (2 if paired else 1) >= min_records
+    return bam
+
+
+@pytest.mark.parametrize("case,model,layout,cov", [("g1_hiseq2500_pe", "Illumina_HiSeq2500", "PE", 3.0), ("g3_hiseq2000_se", "Illumina_HiSeq2000", "SE", 2.0)])
+def test_golden_bam_equals_sam(case, model, layout, cov, models, golden_inputs, tmp_path):
+    """1 + 6: the golden PE and SE inputs through the callback sink; after the ctx is destroyed nothing is left alive."""
+    out, res = _run(tmp_path, prof=models[model], fa=golden_inputs[case], cov=cov, layout=layout, seed=41, sink="callback")
+    bam = _check_job(out, res, layout == "PE")
+    if layout == "SE":
+        assert all(r["next_refID"] == -1 and r["next_pos"] == -1 and r["tlen"] == 0 for r in bam["records"])
+    assert res["live"] == [0, 0, 0, 0]
+
+
+def _exact_profile(src, dst, ins, dele):
+    """Substitution rows with all their mass on the row's own base (kmer XYZ -> Z), and the given indel rates."""
+    lines = open(src).read().split("\n")
+    out, i, L = [], 0, None
+    while i < len(lines):
+        ln = lines[i]
+        if ln.startswith("readLength:"):
+            L = int(ln.split(":")[1])
+        if ln in ("[Insert Rate]", "[Deletion Rate]"):
+            out += [ln, "%g" % (ins if ln == "[Insert Rate]" else dele)]
+            i += 2
+            continue
+        m = re.match(r"kmer: ([ACGTNX]{3})$", ln)
+        if m:
+            b = m.group(1)[2]
+            out.append(ln)
+            row = "\t".join("1" if c == b else "0" for c in "ACGT")
+            out += [row if b in "ACGT" else r for r in lines[i + 1:i + 1 + 2 * L]]
+            i += 1 + 2 * L
+            continue
+        out.append(ln)
+        i += 1
+    open(dst, "w").write("\n".join(out))
+    return dst
+
+
+def _genome(tmp_path, lengths, seed, n_block=None):
+    fa = str(tmp_path / "g.fa")
+    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", lengths, "--seed", str(seed), "--simu-out", fa]
+                          + (["--n-block", str(n_block)] if n_block else []))
+    return fa
+
+
+@pytest.mark.parametrize("variant", ["plain", "replay", "cut_runs"])
+def test_frequent_indels(variant, models, tmp_path):
+    """2: insertion and deletion rates of 0.01: multi-op CIGARs, reversed for half the reads.  replay: the events come from the
+    replay path of truth_load (SCS_EV_REPLAY).  cut_runs: the emit pass fills 4 KB of LDS at a time (SCS_TEST_TRUTH_LDS), so every
+    workgroup copies its pairs out in about ten runs instead of one."""
+    fa = _genome(tmp_path, "200000,150000", 17)
+    prof = _exact_profile(models["Illumina_HiSeq2500"], str(tmp_path / "x.profile"), 0.01, 0.01)
+    env = {"plain": None, "replay": seams_env(SCS_EV_REPLAY="1"), "cut_runs": seams_env(SCS_TEST_TRUTH_LDS="4096")}[variant]
+    out, res = _run(tmp_path, env=env, prof=prof, fa=fa, cov=4.0, layout="PE", seed=7, sink="callback", ber=0.0)
+    bam = _check_job(out, res, True)
+    multi = sum(r["n_cigar_op"] > 1 for r in bam["records"])
+    assert multi > 0.2 * len(bam["records"]), (multi, len(bam["records"]))
+
+
+@pytest.mark.parametrize("sink", ["files", "callback"])
+def test_many_small_batches_and_an_n_block(sink, models, tmp_path):
+    """3: batches of 1024 pairs (about nine BGZF blocks each): records straddle blocks and batches.  files: BGZF FASTQ, the BAM
+    blocks' total rides the FASTQ blocks' event and the batch ships one iteration late; callback: plain FASTQ, its own event."""
+    fa = _genome(tmp_path, "700000,500000", 31, n_block=20000)
+    out, res = _run(tmp_path, env=seams_env(SCS_TEST_BATCH_SHIFT="10"), prof=models["Illumina_HiSeqXTen"], fa=fa, cov=1.0, layout="PE", seed=8, sink=sink)
+    bam = _check_job(out, res, True, sink)
+    assert res["bam"]["k_truth"]["launches"] > 2          # two event pairs per batch: more than one batch
+    assert bam["members"] > res["bam"]["k_truth"]["launches"] // 2 + 2
+
+
+def test_a_batch_smaller_than_one_block(models, tmp_path):
+    """4: batches of 64 pairs, about 37 KB of records: one BGZF block per batch, and the last batch's short tail."""
+    fa = _genome(tmp_path, "700000,500000", 31, n_block=20000)
+    out, res = _run(tmp_path, env=seams_env(SCS_TEST_BATCH_SHIFT="6"), prof=models["Illumina_HiSeqXTen"], fa=fa, cov=0.02, layout="PE", seed=8, sink="callback")
+    bam = _check_job(out, res, True, min_records=100)
+    batches = res["bam"]["k_truth"]["launches"] // 2
+    assert batches > 1 and bam["members"] == 1 + batches + 1     # header, one block per batch, end of file
+
+
+_ERR = r'''
+import sys, ctypes
+sys.path.insert(0, %(root)r)
+import scssim_amd
+from scssim_amd import ScsError, SCS_EINVAL
+kw = dict(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=kw["profile"], seed=5)
+s.set_truth_bam(%(out)r + "_s.bam")
+try:
+    s.yield_reads(); raise SystemExit("sharded: no error")
+except ScsError as e:
+    assert e.code == SCS_EINVAL and "sharded" in str(e) and "BAM" in str(e), e
+g = scssim_amd.GenReads(**kw)
+g.create_frags(); g.amplify(); g.allocate_reads(0)
+g.set_truth_sam(%(out)r + ".sam")
+try:
+    g.set_truth_bam(%(out)r + ".bam"); raise SystemExit("BAM over SAM: no error")
+except ScsError as e:
+    assert e.code == SCS_EINVAL and "scs_set_truth_sam" in str(e) and "scs_set_truth_bam" in str(e), e
+g.set_truth_bam(None)                                    # clears only its own: the SAM stays on
+f1, f2 = g.yield_reads()
+open(%(out)r + "_sam_1.fq", "wb").write(f1); open(%(out)r + "_sam_2.fq", "wb").write(f2)
+g.set_truth_sam(None)
+g.set_truth_bam(%(out)r + ".bam")
+try:
+    g.set_truth_sam(%(out)r + "_2.sam"); raise SystemExit("SAM over BAM: no error")
+except ScsError as e:
+    assert e.code == SCS_EINVAL and "scs_set_truth_sam" in str(e) and "scs_set_truth_bam" in str(e), e
+g.set_truth_sam(None)                                    # ... and the BAM stays on
+try:
+    g.yield_reads_files(%(out)r + "_w", 3); raise SystemExit("writers: no error")
+except ScsError as e:
+    assert e.code == SCS_EINVAL and "writers" in str(e) and "BAM" in str(e), e
+hip = ctypes.CDLL("libamdhip64.so")
+hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+d1, d2 = ctypes.c_void_p(), ctypes.c_void_p()
+assert hip.hipMalloc(ctypes.byref(d1), 1 << 24) == 0 and hip.hipMalloc(ctypes.byref(d2), 1 << 24) == 0
+try:
+    g.yield_reads_device(d1, 1 << 24, d2, 1 << 24); raise SystemExit("device: no error")
+except ScsError as e:
+    assert e.code == SCS_EINVAL and "scs_yield_reads_device" in str(e) and "BAM" in str(e), e
+f1, f2 = g.yield_reads()
+open(%(out)r + "_bam_1.fq", "wb").write(f1); open(%(out)r + "_bam_2.fq", "wb").write(f2)
+print("ok", g.truth_bytes())
+'''
+
+
+def test_refusals_leave_the_ctx_usable(models, golden_inputs, tmp_path):
+    """5: a sharded ctx, writers = 3 and scs_yield_reads_device with the BAM set fail with SCS_EINVAL and say BAM; one truth output
+    per ctx, either way round; the same ctx then writes a BAM that equals its SAM."""
+    out = str(tmp_path / "e")
+    r = subprocess.run([sys.executable, "-c", _ERR % dict(root=ROOT, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], out=out)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    assert not os.path.exists(out + "_w_1.fq") and not os.path.exists(out + "_2.sam") and not os.path.exists(out + "_s.bam")
+    check_bam_equals_sam(out + ".bam", out + ".sam", True, int(r.stdout.split()[-1]))
+    _same_fastq(out, "callback")
+

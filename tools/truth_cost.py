@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""What the truth SAM costs: a chr20-size PE150 30x job (the genome and model of test_chr20_size_bit_exact)
-written to files with truth off and on.  Prints one JSON line per leg: wall seconds of the yield call, the FASTQ and SAM bytes, and
-the library's HIP-event times of k_reads and of the truth passes on the same batches.  Kernel-level numbers: run it under
-`rocprofv3 --kernel-trace --stats -- python tools/truth_cost.py --legs on` (k_truth_size / k_truth_emit against k_reads_all)."""
+"""What the truth SAM and the truth BAM cost: a chr20-size PE150 30x job (the genome and model of
+test_chr20_size_bit_exact) written to files with truth off, with the SAM on and (--bam) with the BAM on.  Prints one JSON line per
+leg and repeat: wall seconds of the yield call, the FASTQ and truth bytes (BAM: compressed, and uncompressed from the blocks' ISIZE
+fields), and the library's HIP-event times of k_reads and of the truth passes on the same batches.  Kernel-level numbers: run it under
+`rocprofv3 --kernel-trace --stats -- python tools/truth_cost.py --legs on,bam --repeats 1` (k_truth_size / k_truth_emit,
+k_truth_bam_size / k_truth_bam_emit and the BGZF kernels against k_reads_all)."""
 import argparse
 import json
 import os
 import subprocess
 import sys
 import tempfile
+import struct
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,9 +19,24 @@ sys.path.insert(0, ROOT)
 import scssim_amd  # noqa: E402
 
 
+def bgzf_isize_sum(path):
+    """Uncompressed bytes of a BGZF file: the sum of its members' ISIZE fields, found by walking BSIZE."""
+    tot, o, n = 0, 0, os.path.getsize(path)
+    with open(path, "rb") as f:
+        while o < n:
+            f.seek(o + 16)
+            bsize = struct.unpack("<H", f.read(2))[0] + 1
+            f.seek(o + bsize - 4)
+            tot += struct.unpack("<I", f.read(4))[0]
+            o += bsize
+    return tot
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="off,on")
+    ap.add_argument("--legs", default=None, help="comma list of off, on (the SAM), bam [off,on; with --bam: off,on,bam]")
+    ap.add_argument("--bam", action="store_true", help="add the truth BAM leg")
+    ap.add_argument("--repeats", type=int, default=1, help="runs of every leg after one unrecorded warm-up yield")
     ap.add_argument("--out-dir", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
     ap.add_argument("--bases", type=int, default=63025520)
     ap.add_argument("--coverage", type=float, default=30.0)
@@ -32,15 +50,20 @@ def main():
         subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_profile.py"), src, prof, "--read-length", "150"])
         g = scssim_amd.GenReads(profile=prof, input_fasta=fa, coverage=a.coverage, seed=220)
         g.create_frags(); g.amplify(); g.allocate_reads(0)
-        for leg in a.legs.split(","):
+        legs = (a.legs or ("off,on,bam" if a.bam else "off,on")).split(",")
+        if a.repeats > 1:                                   # warm-up: the buffers, the pinned slots and the page cache of the first yield
+            g.yield_reads_files(os.path.join(td, "reads_warm"), 1)
+        for leg in [l for _ in range(a.repeats) for l in legs]:
             out = os.path.join(td, "reads_" + leg)
             g.set_truth_sam(out + ".sam" if leg == "on" else None)
+            g.set_truth_bam(out + ".bam" if leg == "bam" else None)
             t = time.time()
             g.yield_reads_files(out, 1)
             wall = time.time() - t
             st, kt = g.stats(), g.kernel_times()
             rec = dict(leg=leg, wall_s=round(wall, 3), pairs=st["pairs_written"], fastq_bytes=st["fastq_bytes"],
-                       sam_bytes=g.truth_bytes() if leg == "on" else 0, k_reads=kt["k_reads"], k_truth=kt["k_truth"])
+                       sam_bytes=g.truth_bytes() if leg == "on" else 0, bam_bytes=g.truth_bytes() if leg == "bam" else 0,
+                       bam_uncompressed_bytes=bgzf_isize_sum(out + ".bam") if leg == "bam" else 0, k_reads=kt["k_reads"], k_truth=kt["k_truth"])
             print(json.dumps(rec), flush=True)
             for f in os.listdir(td):
                 if f.startswith("reads_"):
