@@ -324,6 +324,14 @@ int         scs_devbuf_probe(int device, uint64_t first_bytes, uint64_t second_b
  * lds_out_cap (0 = the kernels' limit) -- run on the CPU over the same functions; out receives the BGZF blocks of the text
  * (no end-of-file block), *n_out their size (out may be NULL to ask for it).  The checker is zlib. */
 int         scs_bgzf_probe(const void* text, uint64_t nbytes, uint32_t lds_out_cap, void* out, uint64_t cap, uint64_t* n_out);
+/* Host-only test seam of the reads stage's batch plan (no GPU, no ctx, reads no environment variable): how scs_yield_reads cuts
+ * `pairs` planned pairs of reads of read_length bases into batches and in which order it makes them.  to_sink = 0: the text stays in
+ * device memory (writers / regions are ignored); else the sink's writers and regions (regions = writers x generations).  batch_shift:
+ * 0, or the tests' SCS_TEST_BATCH_SHIFT (batches of 2^shift pairs).  *batch = pairs per batch, *nbatch = their number; order[i] = the
+ * batch made i-th, region_of[i] = the region its records belong to (nbatch entries each; both may be NULL to ask for the sizes only;
+ * SCS_EOVERFLOW: cap entries are too few). */
+int         scs_batch_plan_probe(uint64_t pairs, uint32_t read_length, int to_sink, int writers, int regions, int batch_shift,
+                                 uint64_t* batch, uint32_t* nbatch, uint32_t* order, uint32_t* region_of, uint32_t cap);
 /* Test seam of the BGZF kernels themselves (needs a GPU, touches no ctx, reads no environment variable): text[0..nbytes) is
  * copied to a fresh device buffer -- 16-byte aligned, as the product's text buffers are -- and goes through exactly what a
  * batch's mate goes through: the plan kernel, the one-workgroup exclusive scan of the block sizes (no scratch), the emit kernel

@@ -166,6 +166,24 @@ def bgzf_probe(data, lds_out_cap=0):
     return out.raw[:n.value]
 
 
+def batch_plan_probe(pairs, read_length=150, to_sink=False, writers=1, regions=1, batch_shift=0):
+    """Host-only: (pairs per batch, order, region_of) of the batches a yield of `pairs` pairs is cut into: order[i] is the batch made
+    i-th, region_of[i] the sink region its records belong to."""
+    L = load_library()
+    L.scs_batch_plan_probe.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
+    batch, n = C.c_uint64(), C.c_uint32()
+    args = (int(pairs), int(read_length), int(bool(to_sink)), int(writers), int(regions), int(batch_shift), C.byref(batch), C.byref(n))
+    rc = L.scs_batch_plan_probe(*args, None, None, 0)
+    if rc:
+        raise ScsError(rc, "scs_batch_plan_probe")
+    order, region_of = (C.c_uint32 * max(1, n.value))(), (C.c_uint32 * max(1, n.value))()
+    rc = L.scs_batch_plan_probe(*args, order, region_of, n.value)
+    if rc:
+        raise ScsError(rc, "scs_batch_plan_probe")
+    return batch.value, list(order[:n.value]), list(region_of[:n.value])
+
+
 def bgzf_blocks(data):
     """Split BGZF bytes into (block bytes, ISIZE) after checking every block's frame: gzip magic, the BC subfield, BSIZE."""
     out, o = [], 0

@@ -1,6 +1,6 @@
 // scs_ctx.h -- private to the library's host side: the context behind the C ABI's opaque scs_ctx, its device buffers, and the
 // functions the host files share (scs_pipeline.cpp: mailbox, C ABI; scs_stage.cpp: profile, genome, fragments; scs_amplify.cpp:
-// Malbac::amplify; scs_reads.cpp: read allocation, yieldReads, the sink).
+// Malbac::amplify; scs_reads.cpp: read allocation, yieldReads; scs_sink.cpp: the FASTQ sink).
 #pragma once
 #include "../../include/scssim_hip.h"
 #include <sched.h>
@@ -192,7 +192,7 @@ struct KernelTimer {         // HIP events on the ctx stream around the launches
 };
 enum { TM_ERRSCAN, TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
-struct SinkPipe;             // scs_reads.cpp
+struct SinkPipe;             // scs_sink.h
 struct SinkPipeDelete { void operator()(SinkPipe* p) const; };
 struct RcclDelete { void operator()(RcclComm* r) const { rccl_destroy(r); } };   // (skips ncclCommDestroy after scs_comm_abort)
 }  // namespace scs
@@ -236,12 +236,13 @@ struct scs_ctx {
     DevBuf slots, slot_tmpl, valid, valid_off, valid_f, valid_off_f, scan_tmp, flags;
     // allocation + reads
     DevBuf weights, read_numbers, pair_off, pairs, odd_before, a_part, a_tp, a_probs, a_quota, a_poff, a_plan, a_crn, a_scratch, a_brow, a_bmap, a_send, a_gath, a_odd; SegMap gmap{}; std::vector<uint32_t> h_read_numbers; uint64_t reads_requested = 0, n_pairs_planned = 0; bool allocated = false;
-    DevBuf slot_b, slot_q, lens, ev_hdr, ev_dat, sizes1, sizes2, off1, off2, out1, out2, out1b, out2b, rl_cls, rl_pos, rl_lists, d_bounds;
+    DevBuf slot_b, slot_q, lens, ev_hdr, ev_dat, sizes[2], off[2], out[2][2], rl_cls, rl_pos, rl_lists, d_bounds;   // sizes / off: per mate; out[slot][mate]: the FASTQ text (sink mode: two slots)
     Stream errs_stream; Event ev_att, ev_errs; bool errs_pending = false;   // k_errs<semi->full> of a cycle runs beside the fragment pass that follows it
     DevBuf slots_fr, slot_tmpl_fr;                        // the fragment passes' own slot arrays (the semi pass's are still being read then)
-    // BGZF made on the device (scs_bgzf.hip): per mate the blocks' plans / sizes / offsets, two sets of output buffers, the CRC tables; the
-    // blocks' total per batch reaches the host through a small pinned array (h_z) behind an event, one batch late (see do_yield)
-    DevBuf z_plan[2], z_sizes[2], z_offs[2], z_out[2][2], z_crc; Pinned<uint32_t> h_z; Event ev_z[2];
+    // BGZF made on the device (scs_bgzf.hip): per byte stream (z[0], z[1]: the mates' FASTQ text; z[2]: the truth BAM's records) the blocks'
+    // plans / sizes / offsets and two output buffers; the CRC tables; the blocks' totals per batch reach the host through a small pinned
+    // array (h_z[slot][stream]) behind the slot's event, the FASTQ blocks' one batch late (see do_yield)
+    struct BgzfLane { DevBuf plan, sizes, offs, out[2]; } z[3]; DevBuf z_crc; Pinned<uint32_t> h_z; Event ev_z[2];
     bool want_cks = false; DevBuf d_cks; std::vector<uint64_t> cks;   // scs_set_batch_checksums: per batch and mate, computed where the text lies in HBM
     // truth SAM (scs_set_truth_sam): the path (empty: off), per batch the pairs' SAM sizes and 64-bit offsets, two output buffers (the
     // batch's text crosses PCIe on the copy stream while the next batch is made), the record table the kernels name records from,
@@ -249,9 +250,8 @@ struct scs_ctx {
     std::string truth_path; uint64_t truth_bytes = 0;
     DevBuf t_sizes, t_offs, t_scan, t_out[2], t_recs; Pinned<uint64_t> h_t; Event ev_t;
     // truth BAM (scs_set_truth_bam): truth_path names a BAM; t_out then holds the batch's binary records, which become BGZF blocks in
-    // tz_out (plans / sizes / offsets of their own); the blocks' total reaches the host through h_tz[slot] behind ev_z (FASTQ BGZF on) or ev_tz
+    // z[2].out; the blocks' total reaches the host through h_z[slot][2] behind ev_z[slot]
     bool truth_bam = false;
-    DevBuf tz_plan, tz_sizes, tz_offs, tz_out[2]; Pinned<uint32_t> h_tz; Event ev_tz[2];
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)
@@ -342,14 +342,17 @@ struct CallbackSink : BatchSink {           // a caller's scs_sink_fn as a Batch
     int put(int, const char* a, size_t na, const char* b, size_t nb) override { return fn(user, a, na, b, nb); }
 };
 struct OutTarget { bool device; char* d1; char* d2; size_t cap1, cap2; BatchSink* sink;
-                   std::vector<uint64_t>* seg_off1 = nullptr; std::vector<uint64_t>* seg_off2 = nullptr;
-                   bool bgzf = false;
-                   bool discard = false; };                                       // discard: the FASTQ text is not wanted on the host (a NULL sink with truth on)                                          // bgzf: the sink gets BGZF blocks made on the device instead of the text   // seg_off: byte offset of each list segment's first record (shard index)
+                   std::vector<uint64_t>* seg_off1 = nullptr; std::vector<uint64_t>* seg_off2 = nullptr;   // seg_off: byte offset of each list segment's first record (shard index)
+                   bool bgzf = false;                                             // bgzf: the sink gets BGZF blocks made on the device instead of the text
+                   bool discard = false; };                                       // discard: the FASTQ text is not wanted on the host (a NULL sink with truth on)
+// the batches of a yield: pairs per batch, their number, the order they are made in and the writer region of each (pure arithmetic: no device, no ctx)
+struct BatchPlan { uint64_t batch = 1; uint32_t nbatch = 0; std::vector<uint32_t> order, region_of; };
+BatchPlan plan_batches(uint64_t P, uint32_t read_length, bool to_sink, int writers, int regions, int batch_shift);
 
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out);
 // truth SAM: refuses (SCS_EINVAL) the targets it does not apply to; device: scs_yield_reads_device, writers: the file sink's
 void truth_check(scs_ctx* c, bool device, int writers);
-std::vector<int> gpu_local_cpus(int device);
+std::vector<int> gpu_local_cpus(int device);   // scs_sink.cpp
 
 template <class F>
 int guarded(scs_ctx* c, F f) {

@@ -196,20 +196,18 @@ struct ReadsSide {
 };
 size_t reads_lds_bytes(const DevTables& tb, bool uni = false);   // uni: the uniform-walk variant (event-free ACGT-only reads)
 //          // dynamic LDS of one inject_errors workgroup for this profile
-void launch_reads(hipStream_t s, const uint8_t* g, const uint32_t* g2, DevErrPool spool, DevErrPool fpool,
-                  const PairRec* pairs, uint32_t np, uint32_t amp_index_base, DevTables tb, const DevTables* d_tb, RngKey key, int paired, uint32_t slot,
-                  const uint32_t* ev_hdr, const uint4* ev_dat, const uint64_t* off1, const uint64_t* off2, char* out1, char* out2, uint32_t* flags,
-                  uint64_t cap1, uint64_t cap2,   // writes FASTQ text; cap: bytes of the batch's text in each file (records are checked against it)
-                  const uint32_t* slist1, const uint32_t* slist2, const uint32_t* clist1, const uint32_t* clist2, uint32_t nc1, uint32_t nc2,
-                  const uint32_t* dlist1, const uint32_t* dlist2, uint32_t nd1, uint32_t nd2, struct ReadsSide* side);   // launch_read_lists' lists; nc: reads with indel events per mate; side: below (null: one stream)
+// one batch's pre-pass buffers (do_yield keeps two sets); [m]: mate 1 / mate 2.  d1f / d1p: the one-deletion class' flags and their scan
+struct BatchSet { uint32_t* ev_hdr; uint4* ev_dat; uint32_t* sizes[2]; uint64_t* off[2]; uint32_t *d1f[2], *d1p[2], *slist[2], *clist[2], *dlist[2]; };
+// what the pre-pass mails the host per mate: bytes of the batch's text in each file (records are checked against it), reads with indel events, reads of the one-event class
+struct BatchCounts { uint64_t bytes[2]; uint32_t n_general[2], n_one_event[2]; };
+// what every batch of one yield shares; side: above (null: one stream)
+struct ReadsJob { const uint8_t* g; const uint32_t* g2; DevErrPool spool, fpool; DevTables tb; RngKey key; int paired; uint32_t slot; uint32_t* flags; ReadsSide* side; uint32_t amp_index_base = 0; };
+void launch_reads(hipStream_t s, const ReadsJob& J, const PairRec* pairs, uint32_t np, const BatchSet& B, const BatchCounts& n, char* const out[2]);   // writes FASTQ text; B's lists: launch_read_lists'
 // splits the batch's reads into those without indel events and the rest (cls from launch_indels): ascending pair-index lists per mate
-void launch_read_lists(hipStream_t s, uint32_t np, int paired, const uint32_t* sizes1, const uint64_t* off1, const uint32_t* d1f1, uint32_t* d1p1,
-                       const uint32_t* sizes2, const uint64_t* off2, const uint32_t* d1f2, uint32_t* d1p2,
-                       uint32_t* slist1, uint32_t* slist2, uint32_t* clist1, uint32_t* clist2, uint32_t* dlist1, uint32_t* dlist2, void* temp, size_t temp_bytes);
+void launch_read_lists(hipStream_t s, uint32_t np, int paired, const BatchSet& B, void* temp, size_t temp_bytes);
 // the indel pass of a batch (n' and events per read, FASTQ record sizes per pair and mate), ahead of launch_reads
 void phase_clock_report();   // -DSCS_PHASE_CLOCK builds: prints and zeroes the uniform walk's phase times (no-op otherwise)
-void launch_indels(hipStream_t s, const PairRec* pairs, uint32_t np, int paired, DevTables tb, RngKey key, uint32_t slot, uint32_t* ev_hdr, uint4* ev_dat,
-                   uint32_t* sizes1, uint32_t* sizes2, uint32_t* d1f1, uint32_t* d1f2, uint32_t* flags);
+void launch_indels(hipStream_t s, const ReadsJob& J, const PairRec* pairs, uint32_t np, const BatchSet& B);
 void launch_predict_windows(hipStream_t s, const uint8_t* windows, uint32_t n_reads, const uint64_t* uids, const uint32_t* atts,
                             const uint8_t* is_read1, DevTables tb, const DevTables* d_tb, RngKey key, uint32_t slot, char* slot_b, char* slot_q,
                             uint32_t* lens, uint32_t* flags);

@@ -1297,7 +1297,7 @@ static void launch_reads_kernel(hipStream_t s, dim3 grid, const DevTables& tb, A
     const size_t lds = reads_lds_bytes(tb, FROM_PAIRS && (CLS == 1 || CLS == 3));
     // > 64 KB of dynamic LDS needs the opt-in; the limit is raised to exactly what this profile needs (once per size:
     // the call sits on the host's critical path of a small job)
-    static size_t opted_all[64][3] = {};                                           // (static per instantiation <FROM_PAIRS, CLS>)                                           // per device and instantiation (the attribute belongs to the device's code object)
+    static size_t opted_all[64][3] = {};                                           // per device and instantiation <FROM_PAIRS, CLS> (the attribute belongs to the device's code object)
     int dev = 0; (void)hipGetDevice(&dev);
     size_t* opted = opted_all[dev & 63];
 #define SCS_LAUNCH_READS(QKV, SLOT) do { \
@@ -1310,27 +1310,22 @@ static uint32_t reads_force_replay() {                                          
     static const uint32_t v = (seam_env("SCS_EV_REPLAY") ? 1u : 0u) | (seam_env("SCS_TEST_REDO") ? 2u : 0u) | (seam_env("SCS_TEST_GENERAL") ? 4u : 0u) | (seam_env("SCS_TEST_NO_D1") ? 8u : 0u) | (seam_env("SCS_TEST_NO_I1") ? 16u : 0u);   // bit 1: every event-free read with a substitution is redone (redo_read)
     return v;
 }
-void launch_indels(hipStream_t s, const PairRec* pairs, uint32_t np, int paired, DevTables tb, RngKey key, uint32_t slot, uint32_t* ev_hdr, uint4* ev_dat,
-                   uint32_t* sizes1, uint32_t* sizes2, uint32_t* d1f1, uint32_t* d1f2, uint32_t* flags) {
+void launch_indels(hipStream_t s, const ReadsJob& J, const PairRec* pairs, uint32_t np, const BatchSet& B) {
     if (np == 0) return;
-    const uint32_t nreads = paired ? 2 * np : np;
-    (void)slot;                                                                    // the FASTQ record takes whatever length the read has (header field: 16 bits)
-    hipLaunchKernelGGL(k_indels, dim3(cdiv(nreads, 256)), dim3(256), 0, s, pairs, np, paired, tb, key, 65535u, reads_force_replay() | (tb.L > 1008 ? 4u : 0u) /* the uniform walk gathers a read with at most 64 lanes */, ev_hdr, ev_dat, sizes1, sizes2, d1f1, d1f2, flags);
+    const DevTables& tb = J.tb; const uint32_t nreads = J.paired ? 2 * np : np;
+    // (J.slot is not used here: the FASTQ record takes whatever length the read has (header field: 16 bits))
+    hipLaunchKernelGGL(k_indels, dim3(cdiv(nreads, 256)), dim3(256), 0, s, pairs, np, J.paired, tb, J.key, 65535u, reads_force_replay() | (tb.L > 1008 ? 4u : 0u) /* the uniform walk gathers a read with at most 64 lanes */, B.ev_hdr, B.ev_dat, B.sizes[0], B.sizes[1], B.d1f[0], B.d1f[1], J.flags);
 }
 // event-free reads and the rest as two launches over their lists (k_read_lists); the grid of a launch covers the longer of
 // the two mates' lists
-void launch_reads(hipStream_t s, const uint8_t* g, const uint32_t* g2, DevErrPool spool, DevErrPool fpool,
-                  const PairRec* pairs, uint32_t np, uint32_t amp_index_base, DevTables tb, const DevTables* d_tb, RngKey key, int paired, uint32_t slot,
-                  const uint32_t* ev_hdr, const uint4* ev_dat, const uint64_t* off1, const uint64_t* off2, char* out1, char* out2, uint32_t* flags,
-                  uint64_t cap1, uint64_t cap2, const uint32_t* slist1, const uint32_t* slist2, const uint32_t* clist1, const uint32_t* clist2, uint32_t nc1, uint32_t nc2,
-                  const uint32_t* dlist1, const uint32_t* dlist2, uint32_t nd1, uint32_t nd2, ReadsSide* side) {
+void launch_reads(hipStream_t s, const ReadsJob& J, const PairRec* pairs, uint32_t np, const BatchSet& B, const BatchCounts& n, char* const out[2]) {
     if (np == 0) return;
-    (void)d_tb;
+    const DevTables& tb = J.tb; const int paired = J.paired; const uint32_t *nc = n.n_general, *nd = n.n_one_event; uint64_t cap1 = n.bytes[0], cap2 = n.bytes[1];
     static const bool shrink = seam_env("SCS_TEST_SHRINK_OUT") != nullptr;               // tests: provoke the record-bound guard
     if (shrink) { cap1 /= 2; cap2 /= 2; }
-    const uint32_t ns1 = np - nc1 - nd1, ns2 = paired ? np - nc2 - nd2 : 0u;
-    uint32_t gs = cdiv(std::max(ns1, ns2), RB), gd = cdiv(std::max(nd1, paired ? nd2 : 0u), RB);
-    const uint32_t gc = cdiv(std::max(nc1, paired ? nc2 : 0u), RB);
+    const uint32_t ns1 = np - nc[0] - nd[0], ns2 = paired ? np - nc[1] - nd[1] : 0u;
+    uint32_t gs = cdiv(std::max(ns1, ns2), RB), gd = cdiv(std::max(nd[0], paired ? nd[1] : 0u), RB);
+    const uint32_t gc = cdiv(std::max(nc[0], paired ? nc[1] : 0u), RB);
     if (tb.L > 1008) { gs = 0; gd = 0; }                                           // reads this long all sit in the general list (launch_indels); what is left in the others are holes: nothing to write
     // The three class kernels write disjoint records: the two small ones go to side streams and run BESIDE the big one (each alone
     // leaves the chip half empty through its first and last wave of workgroups); the caller's stream waits for both.
@@ -1338,9 +1333,9 @@ void launch_reads(hipStream_t s, const uint8_t* g, const uint32_t* g2, DevErrPoo
     if (!split_env && !serial_env) {
         // ONE launch for the three classes (k_reads_all); its LDS is the larger of the uniform walk's and the general variant's
         ReadLists rl{};
-        rl.l[0][0] = clist1; rl.l[0][1] = clist2; rl.n[0][0] = nc1; rl.n[0][1] = paired ? nc2 : 0u; rl.grid[0] = paired ? 2 * gc : gc;
-        rl.l[1][0] = dlist1; rl.l[1][1] = dlist2; rl.n[1][0] = nd1; rl.n[1][1] = paired ? nd2 : 0u; rl.grid[1] = paired ? 2 * gd : gd;
-        rl.l[2][0] = slist1; rl.l[2][1] = slist2; rl.n[2][0] = ns1; rl.n[2][1] = ns2; rl.grid[2] = paired ? 2 * gs : gs;
+        rl.l[0][0] = B.clist[0]; rl.l[0][1] = B.clist[1]; rl.n[0][0] = nc[0]; rl.n[0][1] = paired ? nc[1] : 0u; rl.grid[0] = paired ? 2 * gc : gc;
+        rl.l[1][0] = B.dlist[0]; rl.l[1][1] = B.dlist[1]; rl.n[1][0] = nd[0]; rl.n[1][1] = paired ? nd[1] : 0u; rl.grid[1] = paired ? 2 * gd : gd;
+        rl.l[2][0] = B.slist[0]; rl.l[2][1] = B.slist[1]; rl.n[2][0] = ns1; rl.n[2][1] = ns2; rl.grid[2] = paired ? 2 * gs : gs;
         const uint32_t grid = rl.grid[0] + rl.grid[1] + rl.grid[2];
         if (!grid) return;
         const size_t lds = std::max(reads_lds_bytes(tb, true), reads_lds_bytes(tb, false));
@@ -1350,17 +1345,16 @@ void launch_reads(hipStream_t s, const uint8_t* g, const uint32_t* g2, DevErrPoo
         const uint32_t cap = (uint32_t)(paired ? 2ull * np : np);
 #define SCS_LAUNCH_ALL(QKV, SLOT) do { \
             if (opted[SLOT] != lds) { note_launch(hipFuncSetAttribute((const void*)k_reads_all<QKV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); opted[SLOT] = lds; } \
-            hipLaunchKernelGGL((k_reads_all<QKV>), dim3(grid), dim3(RB), lds, s, g, reinterpret_cast<const uint8_t*>(g2), spool, fpool, pairs, np, paired, tb, key, slot, cap, reads_force_replay(), \
-                               ev_hdr, ev_dat, off1, off2, out1, out2, amp_index_base, flags, cap1, cap2, rl); } while (0)
+            hipLaunchKernelGGL((k_reads_all<QKV>), dim3(grid), dim3(RB), lds, s, J.g, reinterpret_cast<const uint8_t*>(J.g2), J.spool, J.fpool, pairs, np, paired, tb, J.key, J.slot, cap, reads_force_replay(), \
+                               B.ev_hdr, B.ev_dat, B.off[0], B.off[1], out[0], out[1], J.amp_index_base, J.flags, cap1, cap2, rl); } while (0)
         if (tb.qual_k == 16) SCS_LAUNCH_ALL(16, 0); else if (tb.qual_k == 64) SCS_LAUNCH_ALL(64, 1); else SCS_LAUNCH_ALL(128, 2);
 #undef SCS_LAUNCH_ALL
         return;
     }
     // SCS_READS_SPLIT: the three classes as three launches on three streams (round 2's form); SCS_READS_SERIAL: one after the other
     // (side: the caller's two side streams and fork / join events -- they belong to its ctx, created on first use, destroyed with it)
-    static const bool dummy_serial_env = false; (void)dummy_serial_env;
-    const bool serial = serial_env || !side;
-    ReadsSide none; ReadsSide& sd = side ? *side : none;
+    const bool serial = serial_env || !J.side;
+    ReadsSide none; ReadsSide& sd = J.side ? *J.side : none;
     if (!serial && !sd.fork) {
         note_launch(hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming));
         for (int k = 0; k < 2; ++k) { note_launch(hipStreamCreateWithFlags(&sd.st[k], hipStreamNonBlocking)); note_launch(hipEventCreateWithFlags(&sd.join[k], hipEventDisableTiming)); }
@@ -1368,18 +1362,18 @@ void launch_reads(hipStream_t s, const uint8_t* g, const uint32_t* g2, DevErrPoo
     hipStream_t s_main = s;
     hipStream_t s_c = serial ? s : sd.st[0], s_d = serial ? s : sd.st[1];
     if (!serial && (gc || gd)) { note_launch(hipEventRecord(sd.fork, s_main)); if (gc) note_launch(hipStreamWaitEvent(s_c, sd.fork, 0)); if (gd) note_launch(hipStreamWaitEvent(s_d, sd.fork, 0)); }
-    if (gd) launch_reads_kernel<true, 3>(s_d, dim3(paired ? 2 * gd : gd), tb, g, spool, fpool, pairs, np, paired,
-                              reinterpret_cast<const uint8_t*>(g2), (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, tb, key, slot,
-                              (uint32_t)(paired ? 2ull * np : np), reads_force_replay(), ev_hdr, ev_dat, off1, off2, out1, out2, amp_index_base,
-                              (char*)nullptr, (char*)nullptr, (uint32_t*)nullptr, flags, cap1, cap2, dlist1, dlist2, nd1, paired ? nd2 : 0u);
-    if (gs) launch_reads_kernel<true, 1>(s, dim3(paired ? 2 * gs : gs), tb, g, spool, fpool, pairs, np, paired,
-                              reinterpret_cast<const uint8_t*>(g2), (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, tb, key, slot,
-                              (uint32_t)(paired ? 2ull * np : np), reads_force_replay(), ev_hdr, ev_dat, off1, off2, out1, out2, amp_index_base,
-                              (char*)nullptr, (char*)nullptr, (uint32_t*)nullptr, flags, cap1, cap2, slist1, slist2, ns1, ns2);
-    if (gc) launch_reads_kernel<true, 2>(s_c, dim3(paired ? 2 * gc : gc), tb, g, spool, fpool, pairs, np, paired,
-                              (const uint8_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, tb, key, slot,
-                              (uint32_t)(paired ? 2ull * np : np), reads_force_replay(), ev_hdr, ev_dat, off1, off2, out1, out2, amp_index_base,
-                              (char*)nullptr, (char*)nullptr, (uint32_t*)nullptr, flags, cap1, cap2, clist1, clist2, nc1, paired ? nc2 : 0u);
+    if (gd) launch_reads_kernel<true, 3>(s_d, dim3(paired ? 2 * gd : gd), tb, J.g, J.spool, J.fpool, pairs, np, paired,
+                              reinterpret_cast<const uint8_t*>(J.g2), (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, tb, J.key, J.slot,
+                              (uint32_t)(paired ? 2ull * np : np), reads_force_replay(), B.ev_hdr, B.ev_dat, B.off[0], B.off[1], out[0], out[1], J.amp_index_base,
+                              (char*)nullptr, (char*)nullptr, (uint32_t*)nullptr, J.flags, cap1, cap2, B.dlist[0], B.dlist[1], nd[0], paired ? nd[1] : 0u);
+    if (gs) launch_reads_kernel<true, 1>(s, dim3(paired ? 2 * gs : gs), tb, J.g, J.spool, J.fpool, pairs, np, paired,
+                              reinterpret_cast<const uint8_t*>(J.g2), (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, tb, J.key, J.slot,
+                              (uint32_t)(paired ? 2ull * np : np), reads_force_replay(), B.ev_hdr, B.ev_dat, B.off[0], B.off[1], out[0], out[1], J.amp_index_base,
+                              (char*)nullptr, (char*)nullptr, (uint32_t*)nullptr, J.flags, cap1, cap2, B.slist[0], B.slist[1], ns1, ns2);
+    if (gc) launch_reads_kernel<true, 2>(s_c, dim3(paired ? 2 * gc : gc), tb, J.g, J.spool, J.fpool, pairs, np, paired,
+                              (const uint8_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, tb, J.key, J.slot,
+                              (uint32_t)(paired ? 2ull * np : np), reads_force_replay(), B.ev_hdr, B.ev_dat, B.off[0], B.off[1], out[0], out[1], J.amp_index_base,
+                              (char*)nullptr, (char*)nullptr, (uint32_t*)nullptr, J.flags, cap1, cap2, B.clist[0], B.clist[1], nc[0], paired ? nc[1] : 0u);
     if (!serial) {
         if (gc) { note_launch(hipEventRecord(sd.join[0], s_c)); note_launch(hipStreamWaitEvent(s_main, sd.join[0], 0)); }
         if (gd) { note_launch(hipEventRecord(sd.join[1], s_d)); note_launch(hipStreamWaitEvent(s_main, sd.join[1], 0)); }
@@ -1397,13 +1391,11 @@ __global__ void k_read_lists(uint32_t np, int paired, const uint32_t* __restrict
     { const uint32_t c = (uint32_t)(off1[pi] >> OFF_BITS), d = d1p1[pi]; if (sizes1[pi] >> 31) clist1[c] = pi; else if (d1f1[pi]) dlist1[d] = pi; else slist1[pi - c - d] = pi; }
     if (paired) { const uint32_t c = (uint32_t)(off2[pi] >> OFF_BITS), d = d1p2[pi]; if (sizes2[pi] >> 31) clist2[c] = pi; else if (d1f2[pi]) dlist2[d] = pi; else slist2[pi - c - d] = pi; }
 }
-void launch_read_lists(hipStream_t s, uint32_t np, int paired, const uint32_t* sizes1, const uint64_t* off1, const uint32_t* d1f1, uint32_t* d1p1,
-                       const uint32_t* sizes2, const uint64_t* off2, const uint32_t* d1f2, uint32_t* d1p2,
-                       uint32_t* slist1, uint32_t* slist2, uint32_t* clist1, uint32_t* clist2, uint32_t* dlist1, uint32_t* dlist2, void* temp, size_t temp_bytes) {
+void launch_read_lists(hipStream_t s, uint32_t np, int paired, const BatchSet& B, void* temp, size_t temp_bytes) {
     if (np == 0) return;
-    exclusive_scan_u32(s, d1f1, d1p1, np, temp, temp_bytes);
-    if (paired) exclusive_scan_u32(s, d1f2, d1p2, np, temp, temp_bytes);
-    hipLaunchKernelGGL(k_read_lists, dim3(cdiv(np, 256)), dim3(256), 0, s, np, paired, sizes1, off1, d1f1, d1p1, sizes2, off2, d1f2, d1p2, slist1, slist2, clist1, clist2, dlist1, dlist2);
+    for (int m = 0; m < (paired ? 2 : 1); ++m) exclusive_scan_u32(s, B.d1f[m], B.d1p[m], np, temp, temp_bytes);
+    hipLaunchKernelGGL(k_read_lists, dim3(cdiv(np, 256)), dim3(256), 0, s, np, paired, B.sizes[0], B.off[0], B.d1f[0], B.d1p[0], B.sizes[1], B.off[1], B.d1f[1], B.d1p[1],
+                       B.slist[0], B.slist[1], B.clist[0], B.clist[1], B.dlist[0], B.dlist[1]);
 }
 void launch_predict_windows(hipStream_t s, const uint8_t* windows, uint32_t n_reads, const uint64_t* uids, const uint32_t* atts,
                             const uint8_t* is_read1, DevTables tb, const DevTables* d_tb, RngKey key, uint32_t slot, char* slot_b, char* slot_q, uint32_t* lens, uint32_t* flags) {

@@ -165,6 +165,18 @@ int scs_bgzf_probe(const void* text, uint64_t nbytes, uint32_t lds_out_cap, void
     if (out) { if (z.size() > cap) return SCS_EOVERFLOW; memcpy(out, z.data(), z.size()); }
     return SCS_OK;
 }
+// host-only test seam: the batches scs_yield_reads would cut `pairs` pairs into, and the order it would make them in (plan_batches)
+int scs_batch_plan_probe(uint64_t pairs, uint32_t read_length, int to_sink, int writers, int regions, int batch_shift, uint64_t* batch, uint32_t* nbatch,
+                         uint32_t* order, uint32_t* region_of, uint32_t cap) {
+    if (!batch || !nbatch || batch_shift < 0 || batch_shift > 40) return SCS_EINVAL;
+    const BatchPlan pl = plan_batches(pairs, read_length, to_sink != 0, writers, regions, batch_shift);
+    *batch = pl.batch; *nbatch = pl.nbatch;
+    if (!order && !region_of) return SCS_OK;
+    if (pl.nbatch > cap) return SCS_EOVERFLOW;
+    if (order) std::copy(pl.order.begin(), pl.order.end(), order);
+    if (region_of) std::copy(pl.region_of.begin(), pl.region_of.end(), region_of);
+    return SCS_OK;
+}
 namespace {
 struct ProbeMem {                                         // plain hipMalloc blocks of a device probe, freed on every way out (no seam: not a DevBuf)
     std::vector<void*> blocks;

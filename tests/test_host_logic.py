@@ -585,3 +585,54 @@ def test_gz_input_is_inflated_beside_itself_whatever_its_name(golden_inputs, tmp
     assert not os.path.exists("pwned") and not (tmp_path / "pwned").exists()
     with pytest.raises(Exception):
         scssim_amd.fasta_probe(str(d / "absent.fa.gz"))
+
+
+# (writers, regions) of a sink: regions a multiple of writers, and one pair where it is not
+_PLAN_SINKS = [(w, r) for r in (1, 3, 4, 12, 24) for w in (1, 3, 4, 12) if r % w == 0] + [(4, 6)]
+
+
+@pytest.mark.parametrize("writers,regions", _PLAN_SINKS)
+def test_batch_plan_order(writers, regions):
+    """The order a yield makes its batches in (plan_batches through scs_batch_plan_probe): a permutation; region r owns the contiguous
+    batches [nbatch r / regions, nbatch (r + 1) / regions) and gets them in ascending order; a generation (`writers` regions) is over
+    before the next begins; within one, every round visits the regions that still have batches, in ascending order."""
+    shift, per = 6, 64
+    for nbatch_want in sorted({0, 1, regions - 1, regions, 10 * regions + 3}):
+        for pairs in sorted({max(0, per * nbatch_want - 5), 1 if nbatch_want == 1 else per * nbatch_want}):
+            batch, order, region_of = scssim_amd.batch_plan_probe(pairs, 150, True, writers, regions, shift)
+            nbatch = len(order)
+            assert batch == min(max(pairs, 1), per) and nbatch == (pairs + batch - 1) // batch == len(region_of)
+            assert sorted(order) == list(range(nbatch))
+            own = {r: [b for b, q in zip(order, region_of) if q == r] for r in range(regions)}
+            assert set(region_of) <= set(range(regions))
+            for r in range(regions):                                  # (an empty region: nothing)
+                assert own[r] == list(range(nbatch * r // regions, nbatch * (r + 1) // regions)), (pairs, r)
+            gens = [q // writers for q in region_of]
+            assert gens == sorted(gens)
+            for g in range((regions + writers - 1) // writers):
+                seq = [q for q in region_of if q // writers == g]
+                left = {r: len(own[r]) for r in range(g * writers, min(regions, (g + 1) * writers))}
+                while seq:
+                    live = [r for r in sorted(left) if left[r]]
+                    assert live and seq[:len(live)] == live, (pairs, g)
+                    seq = seq[len(live):]
+                    for r in live:
+                        left[r] -= 1
+                assert not any(left.values())
+
+
+def test_batch_plan_sizes():
+    """Pairs per batch, worked out by hand from the rules: 2^23 with the text staying in HBM; 2^19 towards a sink with at most 4 writers;
+    else 2^18 doubled while two batches fit a part file (2 batch <= P / (2 regions)) up to 2^21, then halved down to 2^18 while
+    (writers + 2) slots of batch (4 L + 64) bytes exceed 24 GiB; a batch shift overrides all of it; never more than the pairs there are."""
+    size = lambda *a: scssim_amd.batch_plan_probe(*a)[0]
+    assert size(10 ** 9, 150, False, 1, 1, 0) == 1 << 23
+    assert size(10 ** 9, 150, True, 3, 3, 0) == 1 << 19
+    assert size(8 * 10 ** 8, 150, True, 12, 12, 0) == 1 << 21     # 8e8 / 24 = 33.3 M >= 2^22; 14 x 2^21 x 664 B = 19.5 GB
+    assert size(4 * 10 ** 9, 150, True, 64, 64, 0) == 1 << 19     # 66 x 2^21 x 664 B = 91.9 GB, x 2^20 = 46 GB, x 2^19 = 23 GB < 24 GiB
+    assert size(5 * 10 ** 6, 150, True, 12, 12, 0) == 1 << 18     # 5e6 / 24 = 208 k < 2^19: the floor
+    for sink in (False, True):
+        batch, order, region_of = scssim_amd.batch_plan_probe(1000, 150, sink, 1, 1, 6)
+        assert batch == 64 and order == list(range(16)) and region_of == [0] * 16
+        assert 1000 - (len(order) - 1) * batch == 40                  # what is left for the last batch, from the probe's batch and nbatch
+    assert scssim_amd.batch_plan_probe(0, 150, False)[1:] == ([], []) and scssim_amd.batch_plan_probe(1, 150, True, 4, 4)[0] == 1
