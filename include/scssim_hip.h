@@ -239,6 +239,43 @@ int         scs_truth_bytes(const scs_ctx* ctx, uint64_t* bytes);
  * GPU work.  scs_truth_bytes then reports the BAM file's size (compressed; header and end-of-file block included), and
  * scs_kernel_time(which = 6) the BAM passes with their BGZF launches. */
 int         scs_set_truth_bam(scs_ctx* ctx, const char* path);
+/* ---- depth track: binned read and base counts of the job, made on the GPU ----------------------------------------------
+ * scs_set_depth(ctx, bin_width): the following yield calls also count, per bin of bin_width >= 1 bases of the staged genome, the
+ * reads that start in the bin and the bases aligned in it (0: off, the default -- no buffer exists, no depth code runs).  Record r
+ * of len_r bases has ceil(len_r / bin_width) bins, bin k covering record coordinates [k bin_width, min((k + 1) bin_width, len_r));
+ * no bin straddles two records; bins are numbered record by record in staging order.  More than 2^27 bins (two uint64 counters
+ * each: 2 GB) fail the yield call with SCS_EINVAL before any GPU work; the message names the smallest admissible width.
+ * Both counters follow the alignment the truth SAM writes: `reads` = FASTQ records whose leftmost aligned genome base (POS - 1)
+ * lies in the bin; `bases` = (record, genome base) pairs aligned by an M operation with the base in the bin -- deleted and
+ * inserted bases count nothing.  Reads without a FASTQ record count nothing; both mates of a pair count.  So the sum of `reads`
+ * is scs_stats.reads_written.  The counters are sums of integers: they do not depend on batch cuts, the sink, its writers or
+ * whether the text leaves the GPU.  Zeroed at the start of every yield call, they hold that call's job afterwards.
+ * Applies to every yield entry point and sink (scs_yield_reads with any sink or NULL, scs_yield_reads_files(_ex) with any
+ * writers / generations / flags, scs_yield_reads_device, scs_run_genreads), beside either truth output.  A sharded ctx
+ * (shard_count > 1) fails the yield call with SCS_EINVAL; scs_set_depth(ctx, 0) makes it usable again.
+ * scs_depth_bins: the layout for the staged genome (SCS_EINVAL: depth off, no genome staged, or too many bins).
+ * scs_depth_record_bins: bin_off[r] = first bin of staged record r, records + 1 entries (SCS_EOVERFLOW: cap is smaller).
+ * scs_download_depth: the counters of the last yield call, n_bins entries each; either pointer may be NULL; SCS_EINVAL before a
+ * yield call with depth on has finished, SCS_EOVERFLOW when cap < n_bins; synchronises the ctx stream itself.
+ * scs_write_depth: the same as tab-separated text written by the host: the line "#record\tstart\tend\treads\tbases", then one
+ * line per bin, start 0-based and end exclusive (BED coordinates), record names as scs_fasta_probe reports them.
+ * scs_kernel_time(which = 7) is the depth kernel: one event pair per batch, units = pairs. */
+int         scs_set_depth(scs_ctx* ctx, uint32_t bin_width);
+int         scs_depth_bins(const scs_ctx* ctx, uint64_t* n_bins, uint32_t* bin_width);
+int         scs_depth_record_bins(const scs_ctx* ctx, uint64_t* bin_off, uint64_t cap);
+int         scs_download_depth(scs_ctx* ctx, uint64_t* reads, uint64_t* bases, uint64_t cap);
+int         scs_write_depth(scs_ctx* ctx, const char* path);
+/* Host-only test seams of the depth track (no GPU, no ctx).  scs_depth_layout_probe: the layout function the ctx runs, the 2^27
+ * refusal included (SCS_EINVAL; the text in scs_last_error(NULL)): bin_off[r] = first bin of record r (n_records + 1 entries; may
+ * be NULL), *n_bins their total.  It allocates nothing that grows with the number of bins.
+ * scs_depth_read_probe: one read through the function the kernel runs.  n, pos0, reverse, events, nev as for
+ * scs_truth_record_probe (pos0 = 0-based record coordinate of window base 0); rec_len = bases of the record.  *reads_bin = the bin
+ * (inside the record) that receives the `reads` increment; bins[i] / bases[i], i < *n_out: the `bases` increments in ascending
+ * bin order, each bin once.  SCS_EINVAL: not a valid alignment, or not inside the record; SCS_EOVERFLOW: cap entries are too few
+ * (*n_out is set). */
+int         scs_depth_layout_probe(const uint64_t* rec_lens, int n_records, uint32_t bin_width, uint64_t* bin_off, uint64_t* n_bins);
+int         scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, uint32_t bin_width,
+                                 uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out);
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);
@@ -364,10 +401,11 @@ int         scs_fasta_write_index(const char* fasta_path, char* errbuf, size_t e
 /* Per-kernel timing (HIP events recorded on the ctx stream around every launch, accumulated over the
  * last scs_amplify / scs_yield_reads call): name, launches, total milliseconds, and the units the
  * launches processed (amplicons created for the errscan kernels, read pairs for k_reads/k_indels,
- * templates for the two k_attach instances).  which = 0..6: k_errs<semi->full>, k_errs<frag->semi>, k_reads,
- * k_attach<semi>, k_indels, k_attach<frag>, k_truth (the truth SAM's sizing + scan and emit passes, two event pairs per batch). */
+ * templates for the two k_attach instances).  which = 0..7: k_errs<semi->full>, k_errs<frag->semi>, k_reads,
+ * k_attach<semi>, k_indels, k_attach<frag>, k_truth (the truth SAM's sizing + scan and emit passes, two event pairs per batch),
+ * k_depth (the depth track's pass, one event pair per batch, units = pairs). */
 int         scs_kernel_time(const scs_ctx* ctx, int which, const char** name, uint64_t* launches, double* ms, uint64_t* units);
-/* Which of the seven kernels get their HIP event pairs: bit `which` of mask (default: all), and on which calls: every
+/* Which of the eight kernels get their HIP event pairs: bit `which` of mask (default: all), and on which calls: every
  * `every`-th scs_amplify / scs_yield_reads call counted from this call (default 1 = all).  Every event record is a
  * packet on the stream (about 6 us each on the latency-bound 1 Mb configuration), so a measurement run times only the
  * kernel of interest, on a sample of the steps.  scs_kernel_time reports an untimed call as 0 launches / 0 units. */

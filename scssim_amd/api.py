@@ -328,6 +328,41 @@ def truth_record_probe(seq, qual, genome, pos0, n, events=(), reverse=False, gen
     return _truth_probe("scs_truth_record_probe", seq, qual, genome, pos0, n, events, reverse, genome_start, rname, amp, cnt, paired, is_read2, mate).decode()
 
 
+def depth_layout_probe(rec_lens, bin_width):
+    """Host-only: (bin_off, n_bins) of the depth track's bins for records of these lengths, through the layout function the
+    library runs: bin_off[r] = first bin of record r (len(rec_lens) + 1 entries, uint64).  More than 2^27 bins: ScsError
+    (SCS_EINVAL) naming the smallest admissible width."""
+    import numpy as np
+    L = load_library()
+    L.scs_depth_layout_probe.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
+    lens = np.ascontiguousarray(rec_lens, np.uint64)
+    off, n = np.zeros(lens.size + 1, np.uint64), C.c_uint64()
+    rc = L.scs_depth_layout_probe(lens.ctypes.data, lens.size, int(bin_width), off.ctypes.data, C.byref(n))
+    if rc:
+        raise ScsError(rc, (L.scs_last_error(None) or b"").decode())
+    return off, n.value
+
+
+def depth_read_probe(pos0, n, events=(), reverse=False, rec_len=1 << 40, bin_width=1000):
+    """Host-only: what one read adds to the depth track, through the function the depth kernel runs.  pos0, n, events, reverse
+    as for truth_record_probe; rec_len = bases of its record.  Returns (bin of the `reads` increment, [(bin, bases), ...] in
+    ascending bin order), bins counted inside the record."""
+    L = load_library()
+    L.scs_depth_read_probe.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32,
+                                       C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    ev = (C.c_int32 * max(1, 3 * len(events)))(*[int(v) for e in events for v in e])
+    first, k = C.c_uint64(), C.c_int()
+    args = (int(n), int(pos0), int(bool(reverse)), ev, len(events), int(rec_len), int(bin_width), C.byref(first))
+    rc = L.scs_depth_read_probe(*args, None, None, 0, C.byref(k))
+    if rc not in (SCS_OK, SCS_EOVERFLOW):
+        raise ScsError(rc, "scs_depth_read_probe: not a valid alignment inside the record")
+    bins, bases = (C.c_uint64 * max(1, k.value))(), (C.c_uint32 * max(1, k.value))()
+    rc = L.scs_depth_read_probe(*args, bins, bases, k.value, C.byref(k))
+    if rc:
+        raise ScsError(rc, "scs_depth_read_probe")
+    return first.value, [(bins[i], bases[i]) for i in range(k.value)]
+
+
 def fasta_probe(path):
     """Host-only: (names, total bases, FNV-1a checksum of the upper-cased sequence) as the library stages the file."""
     L = load_library()
@@ -571,6 +606,37 @@ class GenReads:
         self._ck(self._L.scs_truth_bytes(self._ctx, C.byref(n)))
         return n.value
 
+    def set_depth(self, bin_width):
+        """The following yield calls also count, per bin of bin_width bases of the staged records, the reads that start in the bin
+        and the bases aligned in it, on the GPU (0: off).  Any sink, any writers, the text left in HBM; not a sharded job."""
+        self._L.scs_set_depth.argtypes = [C.c_void_p, C.c_uint32]
+        self._ck(self._L.scs_set_depth(self._ctx, int(bin_width)))
+
+    def depth_bins(self):
+        """(number of bins, bin width) of the depth track for the staged genome."""
+        self._L.scs_depth_bins.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        n, w = C.c_uint64(), C.c_uint32()
+        self._ck(self._L.scs_depth_bins(self._ctx, C.byref(n), C.byref(w)))
+        return n.value, w.value
+
+    def depth(self):
+        """(reads, bases, bin_off) of the last yield call: the two counters per bin (uint64) and the first bin of every staged
+        record (records + 1 entries)."""
+        np = self._np
+        n, w = self.depth_bins()
+        reads, bases = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        self._L.scs_download_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        self._ck(self._L.scs_download_depth(self._ctx, reads.ctypes.data, bases.ctypes.data, n))
+        bin_off = np.zeros(self.stats()["records"] + 1, np.uint64)
+        self._L.scs_depth_record_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        self._ck(self._L.scs_depth_record_bins(self._ctx, bin_off.ctypes.data, bin_off.size))
+        return reads, bases, bin_off
+
+    def write_depth(self, path):
+        """The depth track of the last yield call as tab-separated text: #record, start, end (BED coordinates), reads, bases."""
+        self._L.scs_write_depth.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_write_depth(self._ctx, os.fsencode(path)))
+
     def download_frags(self):
         """The fragments of create_frags: genome offset (records concatenated in staging order), length, strand (+1 / -1)."""
         np = self._np
@@ -613,10 +679,10 @@ class GenReads:
             out[name.value.decode()] = dict(launches=n.value, ms=ms.value, units=units.value)
         return out
 
-    KERNELS = ("k_errs<semi->full>", "k_errs<frag->semi>", "k_reads", "k_attach<semi>", "k_indels", "k_attach<frag>", "k_truth")
+    KERNELS = ("k_errs<semi->full>", "k_errs<frag->semi>", "k_reads", "k_attach<semi>", "k_indels", "k_attach<frag>", "k_truth", "k_depth")
 
     def set_kernel_timing(self, names=None, every=1):
-        """Keep HIP event pairs only around the named kernels (None = all seven), on every `every`-th amplify / yield call.
+        """Keep HIP event pairs only around the named kernels (None = all eight), on every `every`-th amplify / yield call.
         Every event record is a packet on the stream (about 6 us each on the latency-bound 1 Mb job)."""
         mask = (1 << len(self.KERNELS)) - 1 if names is None else sum(1 << self.KERNELS.index(n) for n in names)
         self._ck(self._L.scs_set_kernel_timing(self._ctx, mask, every))

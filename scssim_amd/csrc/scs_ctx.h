@@ -11,6 +11,7 @@
 #include "scs_comm.h"
 #include "scs_bgzf.h"
 #include "scs_truth.h"
+#include "scs_depth.h"
 
 #include <atomic>
 #include <fcntl.h>
@@ -190,7 +191,7 @@ struct KernelTimer {         // HIP events on the ctx stream around the launches
     }
     void reset() { ms = 0; launches = 0; units = 0; used = 0; }
 };
-enum { TM_ERRSCAN, TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
+enum { TM_ERRSCAN, TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
 struct SinkPipe;             // scs_sink.h
 struct SinkPipeDelete { void operator()(SinkPipe* p) const; };
@@ -252,6 +253,10 @@ struct scs_ctx {
     // truth BAM (scs_set_truth_bam): truth_path names a BAM; t_out then holds the batch's binary records, which become BGZF blocks in
     // z[2].out; the blocks' total reaches the host through h_z[slot][2] behind ev_z[slot]
     bool truth_bam = false;
+    // depth track (scs_set_depth): the bin width (0: off -- no buffer below exists, no depth code runs), the counters of the last
+    // yield call (reads[n_bins] then bases[n_bins], zeroed on the ctx stream at the start of every call; depth_valid: a call with
+    // depth on has finished) and the kernel's record table (rec_off[nr + 1] then bin_off[nr + 1])
+    uint32_t depth_width = 0; uint64_t depth_bins = 0; bool depth_valid = false; DevBuf dp_cnt, dp_tab;
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)
@@ -299,7 +304,7 @@ struct scs_ctx {
         HIP_OK(hipMemcpyAsync(d_recv, all.data(), all.size(), hipMemcpyHostToDevice, stream)); HIP_OK(hipStreamSynchronize(stream));
     }
     scs_stats st{};
-    KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}};
+    KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}, {"k_depth"}};
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
@@ -352,6 +357,9 @@ BatchPlan plan_batches(uint64_t P, uint32_t read_length, bool to_sink, int write
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out);
 // truth SAM: refuses (SCS_EINVAL) the targets it does not apply to; device: scs_yield_reads_device, writers: the file sink's
 void truth_check(scs_ctx* c, bool device, int writers);
+// depth track: refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the staged records' bins (SCS_EINVAL beyond DEPTH_MAX_BINS)
+void depth_check(scs_ctx* c);
+uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);
 std::vector<int> gpu_local_cpus(int device);   // scs_sink.cpp
 
 template <class F>

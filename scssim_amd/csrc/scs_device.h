@@ -105,7 +105,7 @@ struct AllocPlan {
 struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned long long go[ALLOC_SLOTS]; };
 
 // error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32 };
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -236,13 +236,16 @@ void exclusive_scan_sizes(hipStream_t s, const uint32_t* in, uint64_t* out, size
 void exclusive_scan_u32_to_u64(hipStream_t s, const uint32_t* in, uint64_t* out, size_t n, void* temp, size_t temp_bytes);
 
 // ---- truth SAM / BAM of a batch (scs_k_truth.hip): sizing pass -> 64-bit offsets -> emit pass, after the batch's k_reads
-struct TruthArgs {
+// what placing a read needs (read_place, scs_place.h): the batch's pairs and its indel pass, the model, the flags word
+struct PlaceArgs {
     const PairRec* pairs; uint32_t np; int paired;
     const uint32_t* ev_hdr; const uint4* ev_dat;           // the batch's indel pass
+    DevTables tb; RngKey key; uint32_t slot; uint32_t* flags;
+};
+struct TruthArgs : PlaceArgs {
     const uint64_t* off1; const uint64_t* off2; const char* fq1; const char* fq2;   // its FASTQ text and record offsets (OFF_MASK)
     const uint8_t* g;                                      // the byte genome
     const uint64_t* rec_off; const uint32_t* name_off; const char* names; uint32_t n_rec;   // record starts (n_rec + 1), names
-    DevTables tb; RngKey key; uint32_t slot; uint32_t* flags;
 };
 void launch_truth_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);                 // SAM bytes per pair (both mates); offsets: exclusive_scan_u32_to_u64
 uint32_t truth_pairs_per_block(uint64_t fq_bytes, uint32_t np);                             // the emit pass' LDS run, from the batch's FASTQ bytes
@@ -251,5 +254,14 @@ void launch_truth_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, 
 void launch_truth_bam_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);
 uint32_t truth_bam_pairs_per_block(uint64_t fq_bytes, uint32_t np);
 void launch_truth_bam_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, uint32_t lds, char* out);
+
+// ---- depth track of a batch (scs_k_depth.hip; scs_set_depth): per bin the reads that start in it and the bases aligned in it,
+// summed per workgroup in an LDS table of `slots` entries (a power of two <= DEPTH_LDS_SLOTS; 0: every add goes to memory)
+struct DepthArgs : PlaceArgs {
+    const uint64_t* rec_off; const uint64_t* bin_off; uint32_t n_rec;   // record starts and first bins (n_rec + 1 each)
+    uint32_t bin_width, slots;
+    unsigned long long* reads; unsigned long long* bases;  // the counters, one per bin each
+};
+void launch_depth(hipStream_t s, const DepthArgs& a);
 
 }  // namespace scs

@@ -9,8 +9,7 @@
 // k_truth_bam_emit); its records then become BGZF blocks through the kernels of scs_bgzf.hip.
 #include "scs_device.h"
 #include "scs_kernels_common.h"
-#include "scs_indel.h"
-#include "scs_truth.h"
+#include "scs_place.h"
 
 namespace scs {
 
@@ -28,32 +27,11 @@ struct DevSrc {                                            // a read's FASTQ bas
 };
 struct PtrOut { char* p; __device__ void put(char ch) { *p++ = ch; } };
 
-// read rd of pair pi: its events into ev, its placement, its FASTQ text.  false: it has no record (a hole, or a read the indel
-// pass flagged), or it cannot be made right (FLAG_TRUTH)
+// read rd of pair pi: its events into ev and its placement (read_place, scs_place.h), then its FASTQ text.  false: it has no record
+// (a hole, or a read the indel pass flagged), or it cannot be made right (FLAG_TRUTH)
 __device__ bool truth_load(const TruthArgs& A, const PairRec& pr, uint32_t pi, uint32_t rd, uint32_t* ev, TruthAln& a, DevSrc& src) {
-    const uint32_t r = A.paired ? 2u * pi + rd : pi, hdr = A.ev_hdr[r];
-    const int n_out = (int)(hdr & 0xFFFFu);
-    if (n_out == 0) return false;
-    int nev = (int)((hdr >> 16) & 0xFFu);
-    if ((hdr >> 24) & 1u) {                                // replayed read: its events again, drawn by the indel pass' own code
-        bool over = false;
-        const IndelPass ip = indel_pass<true>(A.tb, A.key, rd | (pr.att << 1), pr.uid, 0u, A.slot, A.flags, [&](int i, uint32_t pos, uint32_t del, uint32_t len) {
-            if (i < TRUTH_EVCAP) ev[i] = tev_pack(pos, del, len); else over = true;
-        });
-        if (over && ip.nev > 0) { atomicOr(A.flags, (uint32_t)FLAG_TRUTH); return false; }
-        nev = ip.nev;
-    } else if (nev > 0) {
-        const uint4 d = A.ev_dat[r]; const uint32_t w[4] = {d.x, d.y, d.z, d.w};
-        for (int i = 0; i < nev; ++i) { const uint32_t v = (w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu; ev[i] = tev_pack(ev_pos(v), ev_del(v), ev_len(v)); }
-    }
-    // a full amplicon is a forward copy (direction +1, no complement) or a reverse complement (-1, complement) of the genome
-    const uint32_t comp = pr.flags & 1u, back = (pr.flags >> 1) & 1u;
-    if (comp != back) { atomicOr(A.flags, (uint32_t)FLAG_TRUTH); return false; }
-    const int64_t dir = back ? -1 : 1;
-    a.g0 = rd == 0 ? pr.base + dir * (int64_t)pr.pos : pr.base + dir * (int64_t)(pr.pos + pr.isz - 1);   // read 2 = revcomp of the far end
-    a.rev = rd == 0 ? (int)back : (int)(back ^ 1u);
-    a.n = A.tb.L; a.nev = nev; a.ev = ev;
-    if (!truth_place(a) || a.qlen != n_out) { atomicOr(A.flags, (uint32_t)FLAG_TRUTH); return false; }
+    int n_out;
+    if (!read_place(A, pr, pi, rd, ev, a, n_out, (uint32_t)FLAG_TRUTH)) return false;
     const char* rec = (rd ? A.fq2 : A.fq1) + ((rd ? A.off2 : A.off1)[pi] & OFF_MASK);
     src.s = rec + 1u + t_digits(pr.amp) + 1u + t_digits(pr.att + 1u) + (A.paired ? 2u : 0u) + 1u;   // "@amp#cnt[/r]\n"
     src.q = src.s + n_out + 3; src.g = A.g;

@@ -3,6 +3,7 @@
 // One scs_ctx = one HIP device + one stream; all amplicon state lives in HBM as flat SoA arrays (scs_ctx.h).
 // Reference call sequence reproduced: src/scssim.cpp:46-67 (genreads branch of main()).
 #include "scs_ctx.h"
+#include <cerrno>
 
 namespace scs {
 
@@ -45,6 +46,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_INTERNAL) m += " internal";
         if (f & FLAG_KEYSPACE) m += " primer budget of a fragment beyond 2^20 (-p / -r far outside the reference's ranges)";
         if (f & FLAG_TRUTH) m += " truth SAM / BAM (a read with more than 32 indel events, pair flags that are not a strand, or a pair whose BAM records outgrow the emit pass' LDS)";
+        if (f & FLAG_DEPTH) m += " depth track (a read with more than 32 indel events, pair flags that are not a strand, or a read placed outside its record)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }
@@ -192,7 +194,7 @@ int scs_allocate_reads(scs_ctx* c, uint64_t reads) { return guarded(c, [&] { do_
 static int discard_sink(void*, const char*, size_t, const char*, size_t) { return 0; }
 int scs_yield_reads(scs_ctx* c, scs_sink_fn sink, void* user) {
     return guarded(c, [&] {
-        truth_check(c, false, 1);
+        truth_check(c, false, 1); depth_check(c);
         // with truth on, a NULL sink still takes the sink path: the SAM needs its writer; the FASTQ text stays on the device
         double t = now_s(); CallbackSink cb(sink ? sink : discard_sink, user);
         OutTarget tg{false, nullptr, nullptr, 0, 0, (sink || !c->truth_path.empty()) ? &cb : nullptr}; tg.discard = !sink;
@@ -202,7 +204,7 @@ int scs_yield_reads(scs_ctx* c, scs_sink_fn sink, void* user) {
 int scs_yield_reads_device(scs_ctx* c, void* d1, size_t cap1, void* d2, size_t cap2, uint64_t* n1, uint64_t* n2, uint64_t* pairs) {
     return guarded(c, [&] {
         if (!d1 || (c->cfg.paired && !d2)) throw ScsError(SCS_EINVAL, "scs_yield_reads_device: null output buffer");
-        truth_check(c, true, 1);
+        truth_check(c, true, 1); depth_check(c);
         double t = now_s(); OutTarget tg{true, (char*)d1, (char*)d2, cap1, cap2, nullptr}; do_yield(c, tg, n1, n2, pairs); c->st.t_stage[5] = now_s() - t;
     });
 }
@@ -215,7 +217,7 @@ int scs_yield_reads_files_ex(scs_ctx* c, const char* prefix, int writers, int ge
         if (flags & ~(SCS_SINK_BGZF | SCS_SINK_IN_PLACE)) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: unknown sink flag");
         if (!prefix || !*prefix) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: no output prefix");
         if (writers > 64 || generations > 64 || (int64_t)std::max(1, writers) * std::max(1, generations) > 99) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: at most 64 writers and 99 parts");
-        truth_check(c, false, writers);
+        truth_check(c, false, writers); depth_check(c);
         const bool pe = c->cfg.paired != 0, shard = c->cfg.shard_count > 1; const std::string pre = prefix;
         const std::string base = shard ? shard_base(pre, c->cfg.shard_rank) : pre;
         FastqParts files; std::string err;
@@ -314,6 +316,63 @@ static int set_truth(scs_ctx* c, const char* path, bool bam) {
 int scs_set_truth_sam(scs_ctx* c, const char* path) { return set_truth(c, path, false); }
 int scs_set_truth_bam(scs_ctx* c, const char* path) { return set_truth(c, path, true); }
 int scs_truth_bytes(const scs_ctx* c, uint64_t* bytes) { if (!c || !bytes) return SCS_EINVAL; *bytes = c->truth_bytes; return SCS_OK; }
+// ---- depth track
+int scs_set_depth(scs_ctx* c, uint32_t bin_width) {
+    return guarded(c, [&] {
+        if (bin_width == c->depth_width) return;
+        HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's counters go: nothing may still read them
+        c->dp_cnt.release(); c->dp_tab.release(); c->depth_valid = false; c->depth_bins = 0; c->depth_width = bin_width;
+    });
+}
+int scs_depth_bins(const scs_ctx* c, uint64_t* n_bins, uint32_t* bin_width) {
+    if (!c) return SCS_EINVAL;
+    scs_ctx* m = const_cast<scs_ctx*>(c);                                          // (the error text is the only thing written)
+    try {
+        if (!c->depth_width) throw ScsError(SCS_EINVAL, "scs_depth_bins: the depth track is off (scs_set_depth)");
+        if (!c->have_genome) throw ScsError(SCS_EINVAL, "scs_depth_bins: no genome is staged");
+        const uint64_t nb = depth_ctx_layout(c, nullptr);
+        if (n_bins) *n_bins = nb; if (bin_width) *bin_width = c->depth_width;
+        return SCS_OK;
+    } catch (const ScsError& e) { m->err = e.what(); return e.code; }
+}
+int scs_depth_record_bins(const scs_ctx* c, uint64_t* bin_off, uint64_t cap) {
+    if (!c || !bin_off) return SCS_EINVAL;
+    scs_ctx* m = const_cast<scs_ctx*>(c);
+    try {
+        if (!c->depth_width || !c->have_genome) throw ScsError(SCS_EINVAL, "scs_depth_record_bins: the depth track is off (scs_set_depth), or no genome is staged");
+        if (cap < c->rec_len.size() + 1) throw ScsError(SCS_EOVERFLOW, "scs_depth_record_bins: records + 1 entries are needed");
+        std::vector<uint64_t> off; (void)depth_ctx_layout(c, &off);
+        std::copy(off.begin(), off.end(), bin_off);
+        return SCS_OK;
+    } catch (const ScsError& e) { m->err = e.what(); return e.code; }
+}
+int scs_download_depth(scs_ctx* c, uint64_t* reads, uint64_t* bases, uint64_t cap) {
+    return guarded(c, [&] {
+        if (!c->depth_width || !c->depth_valid) throw ScsError(SCS_EINVAL, "scs_download_depth: no yield call with the depth track on (scs_set_depth) has finished");
+        const uint64_t nb = c->depth_bins;
+        if (cap < nb) throw ScsError(SCS_EOVERFLOW, "scs_download_depth: " + std::to_string(nb) + " bins, room for " + std::to_string(cap));
+        if (reads && nb) HIP_OK(hipMemcpyAsync(reads, c->dp_cnt.p, nb * 8, hipMemcpyDeviceToHost, c->stream));
+        if (bases && nb) HIP_OK(hipMemcpyAsync(bases, c->dp_cnt.as<uint64_t>() + nb, nb * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    });
+}
+int scs_write_depth(scs_ctx* c, const char* path) {
+    return guarded(c, [&] {
+        if (!path || !*path) throw ScsError(SCS_EINVAL, "scs_write_depth: no path");
+        if (!c->depth_width || !c->depth_valid) throw ScsError(SCS_EINVAL, "scs_write_depth: no yield call with the depth track on (scs_set_depth) has finished");
+        const uint64_t nb = c->depth_bins, w = c->depth_width; std::vector<uint64_t> cnt(std::max<uint64_t>(2 * nb, 1));
+        if (nb) HIP_OK(hipMemcpyAsync(cnt.data(), c->dp_cnt.p, nb * 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        FILE* o = fopen(path, "w");
+        if (!o) throw ScsError(SCS_EIO, std::string("scs_write_depth: can not open ") + path + ": " + strerror(errno));
+        bool okw = fputs("#record\tstart\tend\treads\tbases\n", o) != EOF; uint64_t b = 0;
+        for (size_t r = 0; r < c->rec_len.size() && okw; ++r)
+            for (uint64_t x = 0; x < c->rec_len[r] && okw; x += w, ++b)
+                okw = fprintf(o, "%s\t%llu\t%llu\t%llu\t%llu\n", c->recs[r].name.c_str(), (unsigned long long)x, (unsigned long long)std::min<uint64_t>(x + w, c->rec_len[r]),
+                              (unsigned long long)cnt[b], (unsigned long long)cnt[nb + b]) > 0;
+        if (fclose(o) != 0 || !okw || b != nb) throw ScsError(SCS_EIO, std::string("scs_write_depth: writing ") + path + " failed");
+    });
+}
 int scs_download_frags(scs_ctx* c, uint64_t* goff, uint32_t* len, int8_t* strand) {
     return guarded(c, [&] {
         if (!c->have_frags) throw ScsError(SCS_EINVAL, "scs_download_frags: call scs_create_frags first");

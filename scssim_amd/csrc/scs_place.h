@@ -1,0 +1,40 @@
+// scs_place.h -- where a read of a batch lies on the genome: its indel events (the indel pass' packed ones, or drawn again for a
+// replayed read) and its placement (truth_place, scs_truth.h).  The one definition behind the truth passes (scs_k_truth.hip),
+// which go on to the read's FASTQ text, and the depth pass (scs_k_depth.hip), which needs nothing else.
+// Needs scs_device.h and scs_kernels_common.h before it.
+#pragma once
+#include "scs_indel.h"
+#include "scs_truth.h"
+
+namespace scs {
+
+// read rd of pair pi: its events into ev (TRUTH_EVCAP entries), its placement into a, its length into n_out.  false: it has no
+// record (a read the indel pass flagged), or it cannot be placed right (`flag` is raised: FLAG_TRUTH / FLAG_DEPTH)
+__device__ __forceinline__ bool read_place(const PlaceArgs& A, const PairRec& pr, uint32_t pi, uint32_t rd, uint32_t* ev, TruthAln& a, int& n_out, uint32_t flag) {
+    const uint32_t r = A.paired ? 2u * pi + rd : pi, hdr = A.ev_hdr[r];
+    n_out = (int)(hdr & 0xFFFFu);
+    if (n_out == 0) return false;
+    int nev = (int)((hdr >> 16) & 0xFFu);
+    if ((hdr >> 24) & 1u) {                                // replayed read: its events again, drawn by the indel pass' own code
+        bool over = false;
+        const IndelPass ip = indel_pass<true>(A.tb, A.key, rd | (pr.att << 1), pr.uid, 0u, A.slot, A.flags, [&](int i, uint32_t pos, uint32_t del, uint32_t len) {
+            if (i < TRUTH_EVCAP) ev[i] = tev_pack(pos, del, len); else over = true;
+        });
+        if (over && ip.nev > 0) { atomicOr(A.flags, flag); return false; }
+        nev = ip.nev;
+    } else if (nev > 0) {
+        const uint4 d = A.ev_dat[r]; const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+        for (int i = 0; i < nev; ++i) { const uint32_t v = (w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu; ev[i] = tev_pack(ev_pos(v), ev_del(v), ev_len(v)); }
+    }
+    // a full amplicon is a forward copy (direction +1, no complement) or a reverse complement (-1, complement) of the genome
+    const uint32_t comp = pr.flags & 1u, back = (pr.flags >> 1) & 1u;
+    if (comp != back) { atomicOr(A.flags, flag); return false; }
+    const int64_t dir = back ? -1 : 1;
+    a.g0 = rd == 0 ? pr.base + dir * (int64_t)pr.pos : pr.base + dir * (int64_t)(pr.pos + pr.isz - 1);   // read 2 = revcomp of the far end
+    a.rev = rd == 0 ? (int)back : (int)(back ^ 1u);
+    a.n = A.tb.L; a.nev = nev; a.ev = ev;
+    if (!truth_place(a) || a.qlen != n_out) { atomicOr(A.flags, flag); return false; }
+    return true;
+}
+
+}  // namespace scs

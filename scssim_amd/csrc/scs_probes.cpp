@@ -68,6 +68,35 @@ int scs_truth_bam_record_probe(int paired, int is_read2, uint32_t amp, uint32_t 
                        seq, qual, len, genome, genome_start, genome_len, out, cap, n_out);
 }
 
+// host-only: the depth track's bin layout through the function the ctx runs (depth_layout, scs_depth.h); nothing of the bins' size is allocated
+int scs_depth_layout_probe(const uint64_t* rec_lens, int n_records, uint32_t bin_width, uint64_t* bin_off, uint64_t* n_bins) {
+    if (n_records < 0 || (n_records && !rec_lens)) return SCS_EINVAL;
+    uint32_t min_w = 0;
+    if (depth_layout(rec_lens, (size_t)n_records, bin_width, bin_off, n_bins, &min_w)) return SCS_OK;
+    create_error() = bin_width ? "scs_depth_layout_probe: more than 2^27 bins; " + (min_w ? "the smallest bin width these records admit is " + std::to_string(min_w) : std::string("no bin width below 2^32 is enough"))
+                               : std::string("scs_depth_layout_probe: bin_width is 0");
+    return SCS_EINVAL;
+}
+// host-only: one read through the function the depth kernel runs (depth_read, scs_depth.h) after the truth passes' placement
+int scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, uint32_t bin_width,
+                         uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out) {
+    if (!n_out || n <= 0 || nev < 0 || (nev && !events) || bin_width == 0 || cap < 0 || (cap && (!bins || !bases))) return SCS_EINVAL;
+    std::vector<uint32_t> ev;
+    for (int i = 0; i < nev; ++i) {
+        if (events[3 * i] < 0 || events[3 * i] > 0xFFFF || events[3 * i + 2] <= 0 || events[3 * i + 2] > 0x7FFF) return SCS_EINVAL;
+        ev.push_back(tev_pack((uint32_t)events[3 * i], events[3 * i + 1] ? 1u : 0u, (uint32_t)events[3 * i + 2]));
+    }
+    TruthAln a{pos0, reverse ? 1 : 0, n, nev, ev.data(), 0, 0, 0};
+    if (!truth_place(a) || a.lo < 0 || a.hi >= (int64_t)rec_len) return SCS_EINVAL;
+    std::vector<std::pair<uint64_t, uint32_t>> runs; uint64_t first = 0;
+    depth_read(a, 0, bin_width, [&](uint64_t b) { first = b; }, [&](uint64_t b, uint32_t k) { runs.push_back({b, k}); });
+    if (reads_bin) *reads_bin = first;
+    *n_out = (int)runs.size();
+    if ((int)runs.size() > cap) return SCS_EOVERFLOW;
+    for (size_t i = 0; i < runs.size(); ++i) { bins[i] = runs[i].first; bases[i] = runs[i].second; }
+    return SCS_OK;
+}
+
 int scs_predict_batch(scs_ctx* c, const uint8_t* windows, size_t n_reads, const uint64_t* uids, const uint32_t* attempts, const uint8_t* is_read1,
                       char* out_bases, char* out_quals, int32_t* out_len, int out_stride) {
     return guarded(c, [&] {

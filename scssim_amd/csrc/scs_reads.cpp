@@ -167,12 +167,12 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf; const std::string tname = bam ? "truth BAM" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0; const std::string tname = bam ? "truth BAM" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, truth_sum = 0, bi = 0;            // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
     FdGuard truth_fd;                                                              // (closed after the pipe's writers have ended: declared first)
-    PipeGuard guard{nullptr}; TruthArgs ta{};
+    PipeGuard guard{nullptr}; TruthArgs ta{}; DepthArgs da{};
     // shard index: the pair index at which each list segment starts (pair_off at the segment's first amplicon); the byte offset of
     // that record = the bytes of the batches before its batch (known once every batch is made) + its offset inside the batch
     std::vector<uint64_t> bpair, bb[2]; std::vector<SegAt> seg_at;
@@ -208,6 +208,20 @@ struct Yield {               // the state of one do_yield call
         ta.g = c->genome.as<uint8_t>(); ta.rec_off = (const uint64_t*)tb; ta.name_off = (const uint32_t*)(tb + o_name); ta.names = (const char*)(tb + o_text); ta.n_rec = nr;
         ta.paired = paired; ta.tb = c->dtb; ta.key = c->key; ta.slot = slot; ta.flags = c->flags.as<uint32_t>();
     }
+    void depth_open() {
+        // the kernel's record table (record starts, first bins) and this call's counters, zeroed on the ctx stream
+        static const uint32_t slots = seam_env("SCS_TEST_DEPTH_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_DEPTH_SLOTS")) : DEPTH_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
+        const uint32_t nr = (uint32_t)c->recs.size(); std::vector<uint64_t> tab(2 * ((size_t)nr + 1), 0), boff;
+        const uint64_t nb = c->depth_bins = depth_ctx_layout(c, &boff);
+        for (uint32_t r = 0; r < nr; ++r) { tab[r] = c->rec_off[r]; tab[r + 1] = c->rec_off[r] + c->rec_len[r]; }
+        std::copy(boff.begin(), boff.end(), tab.begin() + nr + 1);
+        upload(c->dp_tab, tab, s);
+        c->dp_cnt.reserve(std::max<size_t>((size_t)nb * 16, 16), s); HIP_OK(hipMemsetAsync(c->dp_cnt.p, 0, std::max<size_t>((size_t)nb * 16, 16), s));
+        HIP_OK(hipStreamSynchronize(s));                                           // (the host table goes)
+        da.rec_off = c->dp_tab.as<uint64_t>(); da.bin_off = da.rec_off + nr + 1; da.n_rec = nr; da.bin_width = c->depth_width; da.slots = slots;
+        da.reads = c->dp_cnt.as<unsigned long long>(); da.bases = da.reads + nb;
+        da.paired = paired; da.tb = c->dtb; da.key = c->key; da.slot = slot; da.flags = c->flags.as<uint32_t>();
+    }
     void setup() {           // the batches' bounds; the truth file; the pipe's writers; the BGZF totals' pinned words and events, the BGZF kernels' CRC tables; the batches' two buffer sets; the pre-pass' stream; the shard index
         // The pairs are planned (k_plan_pairs: insert sizes, positions, the amplicon resolved to an index map) batch by batch, at the
         // head of each batch's pre-pass: bounds[b] = the amplicon that holds the batch's first pair.
@@ -218,6 +232,7 @@ struct Yield {               // the state of one do_yield call
             HIP_OK(hipMemcpyAsync(bounds.data(), c->d_bounds.p, ((size_t)plan.nbatch + 1) * 4, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s));
         }
         if (truth) truth_open();
+        if (depth) depth_open();
         if (to_sink) {
             if (!c->pipe) c->pipe.reset(new SinkPipe);
             c->copy_stream.ensure(hipStreamNonBlocking); for (int k = 0; k < 2; ++k) { c->ev_made[k].ensure(hipEventDisableTiming); c->ev_d2h[k].ensure(hipEventDisableTiming); }
@@ -362,6 +377,13 @@ struct Yield {               // the state of one do_yield call
         }
         c->tm[TM_TRUTH].end(s); c->tm[TM_TRUTH].add_units(np);
     }
+    void depth_batch(const Batch& b) {
+        // the batch's reads into the depth counters, from its pair records and indel events alone.  Before ev_free, as truth_batch
+        da.pairs = b.pr; da.np = b.np; da.ev_hdr = b.B->ev_hdr; da.ev_dat = b.B->ev_dat;
+        c->tm[TM_DEPTH].begin(s);
+        launch_depth(s, da);
+        c->tm[TM_DEPTH].end(s); c->tm[TM_DEPTH].add_units(b.np);
+    }
     void ship(Ship sh) {                                                           // D2H on the copy stream into a free pinned slot, then to the region's writer
         if (bgzf || (bam && sh.p[2])) HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl]));   // the blocks' totals have arrived
         if (bgzf) { sh.n[0] = c->h_z[sh.dsl * 3]; sh.n[1] = c->h_z[sh.dsl * 3 + 1]; }
@@ -412,7 +434,8 @@ struct Yield {               // the state of one do_yield call
         mail_wait(c); flags_eval(c);
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];
-        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect();
+        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect(); c->tm[TM_DEPTH].collect();
+        c->depth_valid = depth;
         c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
         for (int m = 0; m < 2; ++m) { c->st.fastq_bytes[m] = tot[m]; c->st.sink_bytes[m] = to_sink ? sunk[m] : 0; }
         // 1526 B per created amplicon + per pair (insert size + FASTQ bytes of both records)
@@ -430,7 +453,9 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     Yield y{c, tg}; const hipStream_t s = y.s; const uint64_t P = y.P;
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
-    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset();
+    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset(); c->tm[TM_DEPTH].reset();
+    c->depth_valid = false;
+    if (c->depth_width) (void)depth_ctx_layout(c, nullptr);   // more than 2^27 bins: refused before any GPU work
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
     // (Profile.cpp:1482-1485 -> Config.cpp:85-93) -- after the amplification, with the output files opened and empty.  Same here, as an error code.
@@ -455,6 +480,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         y.index_batch(b);
         y.base_pass(b);
         if (y.truth) y.truth_batch(b);
+        if (y.depth) y.depth_batch(b);
         if (y.ps != s) { HIP_OK(hipEventRecord(c->ev_free[b.k], s)); y.free_rec[b.k] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
         if (y.to_sink) y.sink_batch(b);                                            // BGZF where asked; then to the region's writer (with BGZF: the batch before)
@@ -470,6 +496,18 @@ void truth_check(scs_ctx* c, bool device, int writers) {
     if (device) throw ScsError(SCS_EINVAL, what + ": not available with scs_yield_reads_device; turn it off with " + fn + "(ctx, NULL)");
     if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, what + ": not available for a sharded job (shard_count > 1)");
     if (writers > 1) throw ScsError(SCS_EINVAL, what + ": needs writers <= 1 (part files are made out of record order)");
+}
+
+void depth_check(scs_ctx* c) {
+    if (!c->depth_width) return;
+    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, "depth track (scs_set_depth): not available for a sharded job (shard_count > 1); turn it off with scs_set_depth(ctx, 0)");
+}
+uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off) {
+    const size_t nr = c->rec_len.size(); uint64_t nb = 0; uint32_t min_w = 0;
+    if (bin_off) bin_off->assign(nr + 1, 0);
+    if (depth_layout(c->rec_len.data(), nr, c->depth_width, bin_off ? bin_off->data() : nullptr, &nb, &min_w)) return nb;
+    throw ScsError(SCS_EINVAL, "depth track (scs_set_depth): bins of " + std::to_string(c->depth_width) + " bases give more than 2^27 bins for the staged genome; " +
+                   (min_w ? "the smallest bin width it admits is " + std::to_string(min_w) : std::string("no bin width below 2^32 is enough")));
 }
 
 }  // namespace scs
