@@ -276,6 +276,44 @@ int         scs_write_depth(scs_ctx* ctx, const char* path);
 int         scs_depth_layout_probe(const uint64_t* rec_lens, int n_records, uint32_t bin_width, uint64_t* bin_off, uint64_t* n_bins);
 int         scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, uint32_t bin_width,
                                  uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out);
+/* ---- amplicon table: the amplified pool the reads were drawn from, made on the GPU ---------------------------------------
+ * One entry per FULL amplicon, in list order: entry i is the amplicon whose index the FASTQ / SAM record names print.
+ *   rec          the staged record the amplicon lies in (a fragment never straddles records)
+ *   start, end   0-based, end-exclusive record coordinates of the genome interval it copies; end - start = its length
+ *   strand       '+' (+1) when its sequence is a forward copy of the genome, '-' (-1) when it is the reverse complement
+ *   semi         index of its parent semi amplicon;  reads: the read number scs_allocate_reads gave it
+ *   edits        every base where it differs from the genome it copies: the polymerase errors of its semi amplicon that fall
+ *                inside it, then its own (which win at a shared base); a base the second error restores is no edit.  Each is
+ *                stated genome-forward -- record coordinate, the genome's base (N for a non-ACGT one), the amplicon's base
+ *                complemented on '-' -- in ascending coordinate order, each coordinate once, at any count (never truncated).
+ * An edit is shared by every read of the amplicon that covers it (a semi's by the reads of all its fulls): what tells an
+ * amplification artefact from a sequencing error, which the truth SAM's NM / MD count alike.
+ * Both calls need scs_allocate_reads to have run (SCS_EINVAL before, the message names it) and refuse a sharded ctx (shard_count > 1)
+ * with SCS_EINVAL.  A lineage that cannot be placed fails the call with SCS_EOVERFLOW ("amplicon table"), never a wrong line.  They
+ * work a chunk of amplicons at a time: no buffer is sized by the job, and every buffer is released when the call returns.
+ * scs_amplicon_places: the binary form, arrays of scs_stats.full_amplicons entries (strand +1 / -1, start a record coordinate,
+ * len = end - start); any pointer may be NULL; SCS_EOVERFLOW when cap is smaller than the number of full amplicons; synchronises
+ * the ctx stream itself.
+ * scs_write_amplicons: the table as text, made on the GPU: the line "#record\tstart\tend\tamplicon\tstrand\treads\tsemi\tedits",
+ * then one line per amplicon -- the record's name (as scs_fasta_probe reports it), BED coordinates, and edits as pos:R>A joined by
+ * commas, "." when there are none.  flags & 1: BGZF, compressed on the GPU, the file ending with the end-of-file block.  *bytes
+ * (may be NULL) receives the file's size.  SCS_EIO: the file cannot be opened or written; the ctx stays usable.
+ * scs_amplicon_kernel_time: event pairs, milliseconds and amplicons of the last scs_write_amplicons call's kernels (not a slot
+ * of scs_kernel_time). */
+int         scs_amplicon_places(scs_ctx* ctx, uint32_t* rec, uint64_t* start, uint32_t* len, int8_t* strand, uint32_t* n_edits, uint64_t cap);
+int         scs_write_amplicons(scs_ctx* ctx, const char* path, int flags, uint64_t* bytes);
+int         scs_amplicon_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+/* Host-only test seam of the amplicon table (no GPU, no ctx): one amplicon's line through the functions its kernels run.  The
+ * lineage: the fragment's genome offset / length / strand (scs_download_frags), the semi's and the full's start and length with
+ * their error lists as (pos << 3) | alt entries (scs_download_amplicons' form; more than four go through an overflow pool as on
+ * the device); genome = the bases from genome index genome_start on (genome_len of them, covering the amplicon); the record's
+ * first genome index, length and name; the line's index, reads and semi fields.  out receives the line with its newline (NULL:
+ * only *n_out).  SCS_EINVAL: a lineage that does not fit its parents, its record or the genome given; SCS_EOVERFLOW: cap too small. */
+int         scs_amplicon_line_probe(uint64_t frag_goff, uint32_t frag_len, int frag_strand, uint32_t semi_spos, uint32_t semi_len,
+                                    const uint32_t* semi_errs, uint32_t n_semi_errs, uint32_t full_spos, uint32_t full_len,
+                                    const uint32_t* full_errs, uint32_t n_full_errs, const char* genome, uint64_t genome_start, uint64_t genome_len,
+                                    uint64_t rec_off, uint64_t rec_len, const char* rec_name, uint32_t index, uint32_t reads, uint32_t semi,
+                                    char* out, size_t cap, size_t* n_out);
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);

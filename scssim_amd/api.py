@@ -363,6 +363,31 @@ def depth_read_probe(pos0, n, events=(), reverse=False, rec_len=1 << 40, bin_wid
     return first.value, [(bins[i], bases[i]) for i in range(k.value)]
 
 
+def amplicon_line_probe(frag, semi, full, genome, genome_start=0, rec_off=0, rec_len=None, rec_name="chr", index=0, reads=0, semi_index=0):
+    """Host-only: one line of the amplicon table through the functions its kernels run.  frag = (genome offset, length, strand);
+    semi / full = (spos, length, [(pos, alt), ...]) with alt a base code 0..3; genome = the bases from genome index genome_start on;
+    rec_off / rec_len = the record's first genome index and length.  ScsError (SCS_EINVAL): a lineage that does not fit."""
+    import numpy as np
+    L = load_library()
+    L.scs_amplicon_line_probe.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    genome = genome.encode() if isinstance(genome, str) else bytes(genome)
+    e1 = np.array([(p << 3) | a for p, a in semi[2]] or [0], np.uint32)
+    e2 = np.array([(p << 3) | a for p, a in full[2]] or [0], np.uint32)
+    args = [int(frag[0]), int(frag[1]), int(frag[2]), int(semi[0]), int(semi[1]), e1.ctypes.data, len(semi[2]), int(full[0]), int(full[1]), e2.ctypes.data, len(full[2]),
+            genome, int(genome_start), len(genome), int(rec_off), int(len(genome) if rec_len is None else rec_len), rec_name.encode(), int(index), int(reads), int(semi_index)]
+    n = C.c_size_t()
+    rc = L.scs_amplicon_line_probe(*args, None, 0, C.byref(n))
+    if rc:
+        raise ScsError(rc, "scs_amplicon_line_probe: the lineage does not fit its parents, its record or the genome given")
+    out = C.create_string_buffer(max(1, n.value))
+    rc = L.scs_amplicon_line_probe(*args, out, n.value, C.byref(n))
+    if rc:
+        raise ScsError(rc, "scs_amplicon_line_probe")
+    return out.raw[:n.value].decode()
+
+
 def fasta_probe(path):
     """Host-only: (names, total bases, FNV-1a checksum of the upper-cased sequence) as the library stages the file."""
     L = load_library()
@@ -636,6 +661,32 @@ class GenReads:
         """The depth track of the last yield call as tab-separated text: #record, start, end (BED coordinates), reads, bases."""
         self._L.scs_write_depth.argtypes = [C.c_void_p, C.c_char_p]
         self._ck(self._L.scs_write_depth(self._ctx, os.fsencode(path)))
+
+    def amplicon_places(self):
+        """The amplified pool after allocate_reads, one entry per full amplicon in list order (the index the read names print): dict
+        of numpy arrays rec (staged record), start (0-based record coordinate), len, strand (+1 / -1), n_edits (bases where the
+        amplicon differs from the genome it copies).  Made on the GPU; not a sharded job."""
+        np = self._np
+        n = self.stats()["full_amplicons"]
+        a = dict(rec=np.zeros(n, np.uint32), start=np.zeros(n, np.uint64), len=np.zeros(n, np.uint32), strand=np.zeros(n, np.int8), n_edits=np.zeros(n, np.uint32))
+        self._L.scs_amplicon_places.argtypes = [C.c_void_p] * 6 + [C.c_uint64]
+        self._ck(self._L.scs_amplicon_places(self._ctx, *[a[k].ctypes.data for k in ("rec", "start", "len", "strand", "n_edits")], n))
+        return a
+
+    def write_amplicons(self, path, bgzf=False):
+        """The same table as tab-separated text made on the GPU: #record, start, end (BED), amplicon, strand, reads, semi, edits
+        (pos:R>A joined by commas, or "."); bgzf: BGZF blocks compressed on the GPU.  Returns the file's size in bytes."""
+        self._L.scs_write_amplicons.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+        n = C.c_uint64()
+        self._ck(self._L.scs_write_amplicons(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n)))
+        return n.value
+
+    def amplicon_kernel_time(self):
+        """Event pairs, milliseconds and amplicons of the last write_amplicons call's kernels."""
+        self._L.scs_amplicon_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(self._L.scs_amplicon_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def download_frags(self):
         """The fragments of create_frags: genome offset (records concatenated in staging order), length, strand (+1 / -1)."""

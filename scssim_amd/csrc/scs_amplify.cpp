@@ -141,6 +141,17 @@ static void attach_pass(scs_ctx* c, bool from_frag, const AmplifyParams& p, uint
     }
 }
 
+// mean number of overflow-pool entries of an amplicon with n error trials: sum of k P(K = k) over k > 4, K ~ Binomial(n, ber)
+// capped at BINOM_KMAX as the count's thresholds cap it (binom_table)
+static double pool_entries_per_amplicon(double ber, int n) {
+    if (ber <= 0 || n <= 0) return 0;
+    if (ber >= 1) return BINOM_KMAX;
+    const double q = 1 - ber, ratio = ber / q;
+    double pmf = std::pow(q, n), cdf = 0, e = 0;
+    for (int k = 0; k < BINOM_KMAX; ++k) { cdf += pmf; if (k > 4) e += k * pmf; pmf = pmf * (double)(n - k) / (double)(k + 1) * ratio; }
+    return e + BINOM_KMAX * std::max(0.0, 1 - cdf);
+}
+
 // ---------------------------------------------------------------- one amplification pass (a4 / a5)
 // rb_slot: where the number of amplicons created is read back to (pinned host memory, stream-ordered).
 static void join_errs(scs_ctx* c) { if (c->errs_pending) { HIP_OK(hipStreamWaitEvent(c->stream, c->ev_errs, 0)); c->errs_pending = false; } }
@@ -160,7 +171,11 @@ void launch_pass(scs_ctx* c, bool from_frag, uint32_t pass, int rb_slot) {
         slots.reserve((size_t)n_slots * 4, s); slot_tmpl.reserve((size_t)n_slots * 4, s);   // k_attach marks its own slots unused first
         c->scan_tmp.reserve(scan_temp_bytes(nt), s);
         out.reserve((uint64_t)out.n + n_slots, s);
-        out.reserve_pool(std::max<uint32_t>(1u << 16, (uint32_t)std::min<uint64_t>(((uint64_t)out.n + n_slots) / 256 + 4096, 0xFFFFFFF0ull)), s);
+        // the overflow pool holds the lists of more than four errors.  Its size follows the error rate: per amplicon the mean number of
+        // pool entries at the longest amplicon (pool_entries_per_amplicon), half as much again, never less than one entry in 256
+        const uint64_t total = (uint64_t)out.n + n_slots;
+        const uint64_t by_rate = (uint64_t)((double)total * std::min(1.5 * pool_entries_per_amplicon(c->cfg.ber, c->cfg.amplicon_max_len - 8), (double)BINOM_KMAX)) + 4096;
+        out.reserve_pool(std::max<uint32_t>(1u << 16, (uint32_t)std::min<uint64_t>(std::max(total / 256 + 4096, by_rate), 0xFFFFFFF0ull)), s);
     }
     KernelTimer& tma = from_frag ? c->tm[TM_ATTACH_F] : c->tm[TM_ATTACH];
     if (some) tma.begin(s);

@@ -257,6 +257,11 @@ struct scs_ctx {
     // yield call (reads[n_bins] then bases[n_bins], zeroed on the ctx stream at the start of every call; depth_valid: a call with
     // depth on has finished) and the kernel's record table (rec_off[nr + 1] then bin_off[nr + 1])
     uint32_t depth_width = 0; uint64_t depth_bins = 0; bool depth_valid = false; DevBuf dp_cnt, dp_tab;
+    // amplicon table (scs_amplicon_places / scs_write_amplicons; scs_amplicons.cpp): the kernels' record table, a chunk's line sizes and
+    // 64-bit offsets, the binary form's arrays, two text buffers (and the BGZF lane over them) with their pinned twins, the chunk's
+    // totals in pinned words behind ev_am_n / ev_am_made.  Every buffer holds one chunk and is released when the call returns
+    DevBuf am_recs, am_sizes, am_offs, am_scan, am_bin, am_out[2]; BgzfLane am_z; Pinned<char> h_am[2]; Pinned<uint64_t> h_am_n; Event ev_am_n, ev_am_made[2], ev_am_d2h[2];
+    KernelTimer tm_amp{"k_amplicons"};                    // the last scs_write_amplicons call's kernels (scs_amplicon_kernel_time; not one of tm[])
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)

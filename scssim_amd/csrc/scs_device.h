@@ -104,8 +104,9 @@ struct AllocPlan {
 // local amplicon index -> index in the whole job's list (the number printed in the record name); n == 0: identity
 struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned long long go[ALLOC_SLOTS]; };
 
-// error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64 };
+// error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right,
+// 6 the same for the depth track, 7 for the amplicon table
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -263,5 +264,19 @@ struct DepthArgs : PlaceArgs {
     unsigned long long* reads; unsigned long long* bases;  // the counters, one per bin each
 };
 void launch_depth(hipStream_t s, const DepthArgs& a);
+
+// ---- amplicon table (scs_k_amplicons.hip; scs_amplicon_places / scs_write_amplicons): the full amplicons [first, first + n) of
+// the list, each resolved to its record, interval, strand and edits (scs_amp.h).  A chunk at a time: nothing is sized by the job
+struct AmpArgs {
+    DevFrags fr; DevAmps semis, fulls; const uint32_t* spool; const uint32_t* fpool;   // the lineage tables and both error pools
+    const uint8_t* g; const uint32_t* read_numbers;
+    const uint64_t* rec_off; const uint32_t* name_off; const char* names; uint32_t n_rec;   // record starts (n_rec + 1), names (the truth passes' table)
+    uint32_t first, n; uint32_t* flags;
+};
+#define AMP_LDS 16384u                                     // bytes of one workgroup's run of lines in the emit pass
+// the binary form, entry j = amplicon first + j; any pointer may be null
+void launch_amp_place(hipStream_t s, const AmpArgs& a, uint32_t* rec, uint64_t* start, uint32_t* len, int8_t* strand, uint32_t* n_edits);
+void launch_amp_size(hipStream_t s, const AmpArgs& a, uint32_t* sizes);                    // bytes of every line; offsets: exclusive_scan_u32_to_u64
+void launch_amp_emit(hipStream_t s, const AmpArgs& a, const uint64_t* offs, uint32_t lds, char* out);   // lds: the LDS run in bytes (0: AMP_LDS); out 16-byte aligned
 
 }  // namespace scs

@@ -2,6 +2,7 @@
 // planners the product runs (truth SAM, FASTA, simuvars, BGZF, the profile tables), device probes of single kernels (BGZF, the
 // scans, DevBuf, Philox, det_log, Profile::predict), and the census of live device resources.  Nothing here is on a job's path.
 #include "scs_ctx.h"
+#include "scs_amp.h"
 
 // host-only: one read's record through the formatter the truth kernels run (scs_truth.h), as SAM text or as a BAM record
 static int truth_probe(bool bam, int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
@@ -94,6 +95,21 @@ int scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events
     *n_out = (int)runs.size();
     if ((int)runs.size() > cap) return SCS_EOVERFLOW;
     for (size_t i = 0; i < runs.size(); ++i) { bins[i] = runs[i].first; bases[i] = runs[i].second; }
+    return SCS_OK;
+}
+
+// host-only: one amplicon's line of the amplicon table through the functions its kernels run (amp_line_probe, scs_amp.h)
+int scs_amplicon_line_probe(uint64_t frag_goff, uint32_t frag_len, int frag_strand, uint32_t semi_spos, uint32_t semi_len, const uint32_t* semi_errs, uint32_t n_semi_errs,
+                            uint32_t full_spos, uint32_t full_len, const uint32_t* full_errs, uint32_t n_full_errs,
+                            const char* genome, uint64_t genome_start, uint64_t genome_len, uint64_t rec_off, uint64_t rec_len, const char* rec_name,
+                            uint32_t index, uint32_t reads, uint32_t semi, char* out, size_t cap, size_t* n_out) {
+    if (!n_out) return SCS_EINVAL;
+    std::string line;
+    const int rc = amp_line_probe(frag_goff, frag_len, frag_strand, semi_spos, semi_len, semi_errs, n_semi_errs, full_spos, full_len, full_errs, n_full_errs,
+                                  genome, genome_start, genome_len, rec_off, rec_len, rec_name, index, reads, semi, line);
+    if (rc) return rc;
+    *n_out = line.size();
+    if (out) { if (line.size() > cap) return SCS_EOVERFLOW; memcpy(out, line.data(), line.size()); }
     return SCS_OK;
 }
 
