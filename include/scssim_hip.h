@@ -314,6 +314,49 @@ int         scs_amplicon_line_probe(uint64_t frag_goff, uint32_t frag_len, int f
                                     const uint32_t* full_errs, uint32_t n_full_errs, const char* genome, uint64_t genome_start, uint64_t genome_len,
                                     uint64_t rec_off, uint64_t rec_len, const char* rec_name, uint32_t index, uint32_t reads, uint32_t semi,
                                     char* out, size_t cap, size_t* n_out);
+
+/* ---- artefact table: the amplification's errors by genome site, made on the GPU -------------------------------------------
+ * The false-positive truth set of the experiment: one entry per ARTEFACT SITE, a triple (staged record, record coordinate,
+ * alternate base), wherever at least one full amplicon has an edit (the amplicon table's edits above: genome-forward, the semi's
+ * errors then the full's own, which win at a shared base; a restored base is no edit).  Two alternate bases at one coordinate
+ * are two sites.  Per site, exact integers:
+ *   NA   full amplicons that carry this alternate base at this coordinate
+ *   TA   full amplicons whose interval [start, end) contains the coordinate, whatever they carry there
+ *   NR   sum of the read numbers (scs_download_read_numbers) of the NA amplicons;  TR: of the TA amplicons
+ * so 1 <= NA <= TA, NR <= TR, and NR / TR is the artefact's expected allele fraction in the reads.  The sites come in ascending
+ * (record in staging order, coordinate, alternate base A < C < G < T), each once.  min_reads: only sites with NR >= min_reads are
+ * reported (0: every site; most sites of a low-coverage job have NR = 0).
+ * Both calls need scs_allocate_reads to have run and an unsharded ctx (SCS_EINVAL otherwise, as for the amplicon table).  A lineage
+ * that cannot be placed fails the call with SCS_EOVERFLOW ("artefact table"), never a wrong line.  The genome is worked in slabs
+ * of 2^28 genome indices: the call's buffers hold one slab's edit entries and amplicons, not the job's, and every buffer, stream
+ * and event of the call is released when it returns, on every way out.
+ * scs_write_artefacts: VCF 4.2, made on the GPU: ##fileformat=VCFv4.2, ##source=scssim, one ##contig=<ID=NAME,length=LEN> per
+ * staged record (names as scs_fasta_probe reports them), the four ##INFO lines, the #CHROM line, then per site
+ * NAME, POS (coordinate + 1), ".", REF (the genome's base, N for a non-ACGT one), ALT, ".", ".", "NA=..;TA=..;NR=..;TR=..".
+ * flags: 1 = BGZF (header block made on the host, body blocks on the GPU, the 28-byte end-of-file block last: the file is sorted,
+ * so bgzip- and tabix-style tools read it); any other bit is SCS_EINVAL.  A job without a site writes the header (and in BGZF the
+ * end-of-file block).  *sites / *bytes (may be NULL) receive the sites written and the file's size.  SCS_EIO: the file cannot be
+ * opened or written; the ctx stays usable.
+ * scs_artefact_sites: the binary form; ref codes 0..4, alt 0..3, pos 0-based; any array may be NULL; *n is always set to the number
+ * of sites, SCS_EOVERFLOW when cap < *n (cap = 0 asks for the count; the first cap sites are still stored); synchronises the ctx
+ * stream itself.
+ * scs_artefact_kernel_time: event pairs, milliseconds and sites of the last scs_write_artefacts call's kernels, the library sorts
+ * and scans included (not a slot of scs_kernel_time). */
+int         scs_write_artefacts(scs_ctx* ctx, const char* path, int flags, uint32_t min_reads, uint64_t* sites, uint64_t* bytes);
+int         scs_artefact_sites(scs_ctx* ctx, uint32_t min_reads, uint32_t* rec, uint64_t* pos, uint8_t* ref, uint8_t* alt, uint32_t* na, uint32_t* ta,
+                               uint64_t* nr, uint64_t* tr, uint64_t cap, uint64_t* n);
+int         scs_artefact_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+/* Host-only test seam of the artefact table (no GPU, no ctx): the table's body through the functions its kernels run (key packing,
+ * run heads, the cover count by bisection, the record lookup, the line formatter under a counting and a writing sink), with
+ * std::sort where the device has the radix sort.  n_amp amplicon intervals (global genome start, length, reads), n_ed edit
+ * entries (amplicon, global genome index, alternate base code 0..3), the staged records' lengths and names, genome = the bases
+ * of all records concatenated (genome_len = the sum of the lengths).  flags & 1: the header goes in front.  out receives the text
+ * (NULL: only *n_out).  SCS_EINVAL: an amplicon outside its record, an edit outside its amplicon, an alternate base above 3;
+ * SCS_EOVERFLOW: cap too small. */
+int         scs_artefact_probe(const uint64_t* amp_start, const uint32_t* amp_len, const uint32_t* amp_reads, uint64_t n_amp,
+                               const uint32_t* ed_amp, const uint64_t* ed_x, const uint8_t* ed_alt, uint64_t n_ed,
+                               const uint64_t* rec_len, const char* const* rec_names, uint32_t n_rec, const char* genome, uint64_t genome_len,
+                               uint32_t min_reads, int flags, char* out, size_t cap, size_t* n_out);
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);

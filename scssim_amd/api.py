@@ -388,6 +388,37 @@ def amplicon_line_probe(frag, semi, full, genome, genome_start=0, rec_off=0, rec
     return out.raw[:n.value].decode()
 
 
+def artefact_probe(starts, lens, reads, edits, rec_lens, rec_names, genome, min_reads=0, header=False):
+    """Host-only: the artefact table's body (header=True: behind its header) through the functions its kernels run.  starts / lens /
+    reads: the full amplicons' global genome start, length and read number; edits = [(amplicon, global genome index, alt code 0..3),
+    ...]; rec_lens / rec_names: the staged records; genome = their bases, concatenated.  ScsError (SCS_EINVAL): an amplicon outside
+    its record, an edit outside its amplicon."""
+    import numpy as np
+    L = load_library()
+    L.scs_artefact_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint32, C.c_int,
+                                     C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    genome = genome.encode() if isinstance(genome, str) else bytes(genome)
+    n_amp, n_ed = len(starts), len(edits)
+    a_s, a_l, a_r = (np.ascontiguousarray(list(starts) + [0], np.uint64), np.ascontiguousarray(list(lens) + [0], np.uint32), np.ascontiguousarray(list(reads) + [0], np.uint32))
+    e_a = np.ascontiguousarray([e[0] for e in edits] + [0], np.uint32)
+    e_x = np.ascontiguousarray([e[1] for e in edits] + [0], np.uint64)
+    e_b = np.ascontiguousarray([e[2] for e in edits] + [0], np.uint8)
+    r_l = np.ascontiguousarray(list(rec_lens), np.uint64)
+    names = (C.c_char_p * len(rec_names))(*[n.encode() for n in rec_names])
+    args = [a_s.ctypes.data, a_l.ctypes.data, a_r.ctypes.data, n_amp, e_a.ctypes.data, e_x.ctypes.data, e_b.ctypes.data, n_ed,
+            r_l.ctypes.data, names, len(rec_names), genome, len(genome), int(min_reads), 1 if header else 0]
+    n = C.c_size_t()
+    rc = L.scs_artefact_probe(*args, None, 0, C.byref(n))
+    if rc:
+        raise ScsError(rc, "scs_artefact_probe: an amplicon outside its record, an edit outside its amplicon, or a base that is no code 0..3")
+    out = C.create_string_buffer(max(1, n.value))
+    rc = L.scs_artefact_probe(*args, out, n.value, C.byref(n))
+    if rc:
+        raise ScsError(rc, "scs_artefact_probe")
+    return out.raw[:n.value].decode()
+
+
 def fasta_probe(path):
     """Host-only: (names, total bases, FNV-1a checksum of the upper-cased sequence) as the library stages the file."""
     L = load_library()
@@ -686,6 +717,38 @@ class GenReads:
         self._L.scs_amplicon_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
         self._ck(self._L.scs_amplicon_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def write_artefacts(self, path, bgzf=False, min_reads=0):
+        """The amplification's artefacts by genome site as a sorted VCF made on the GPU, after allocate_reads: per (record, coordinate,
+        alternate base) NA / TA (full amplicons that carry it / that cover the site) and NR / TR (the reads allotted to them).
+        min_reads: only sites with NR >= min_reads; bgzf: BGZF blocks compressed on the GPU.  Returns dict(sites=, bytes=)."""
+        self._L.scs_write_artefacts.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        n, b = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.scs_write_artefacts(self._ctx, os.fsencode(path), 1 if bgzf else 0, int(min_reads), C.byref(n), C.byref(b)))
+        return dict(sites=n.value, bytes=b.value)
+
+    def artefact_sites(self, min_reads=0):
+        """The same table as a dict of numpy arrays, one entry per site in file order: rec (staged record), pos (0-based record
+        coordinate), ref (code 0..4), alt (0..3), na, ta, nr, tr."""
+        np = self._np
+        fn = self._L.scs_artefact_sites
+        fn.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        n = C.c_uint64()
+        rc = fn(self._ctx, int(min_reads), *([None] * 8), 0, C.byref(n))
+        if rc and not (rc == SCS_EOVERFLOW and n.value):
+            self._ck(rc)
+        a = dict(rec=np.zeros(n.value, np.uint32), pos=np.zeros(n.value, np.uint64), ref=np.zeros(n.value, np.uint8), alt=np.zeros(n.value, np.uint8),
+                 na=np.zeros(n.value, np.uint32), ta=np.zeros(n.value, np.uint32), nr=np.zeros(n.value, np.uint64), tr=np.zeros(n.value, np.uint64))
+        if n.value:
+            self._ck(fn(self._ctx, int(min_reads), *[a[k].ctypes.data for k in ("rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")], n.value, C.byref(n)))
+        return a
+
+    def artefact_kernel_time(self):
+        """Event pairs, milliseconds and sites of the last write_artefacts call's kernels (the sorts and scans included)."""
+        self._L.scs_artefact_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(self._L.scs_artefact_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
         return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def download_frags(self):

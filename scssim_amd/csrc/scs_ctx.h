@@ -262,6 +262,7 @@ struct scs_ctx {
     // totals in pinned words behind ev_am_n / ev_am_made.  Every buffer holds one chunk and is released when the call returns
     DevBuf am_recs, am_sizes, am_offs, am_scan, am_bin, am_out[2]; BgzfLane am_z; Pinned<char> h_am[2]; Pinned<uint64_t> h_am_n; Event ev_am_n, ev_am_made[2], ev_am_d2h[2];
     KernelTimer tm_amp{"k_amplicons"};                    // the last scs_write_amplicons call's kernels (scs_amplicon_kernel_time; not one of tm[])
+    KernelTimer tm_site{"k_sites"};                       // the last scs_write_artefacts call's kernels (scs_artefact_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)

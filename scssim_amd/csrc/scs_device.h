@@ -105,8 +105,8 @@ struct AllocPlan {
 struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned long long go[ALLOC_SLOTS]; };
 
 // error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right,
-// 6 the same for the depth track, 7 for the amplicon table
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128 };
+// 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -278,5 +278,25 @@ struct AmpArgs {
 void launch_amp_place(hipStream_t s, const AmpArgs& a, uint32_t* rec, uint64_t* start, uint32_t* len, int8_t* strand, uint32_t* n_edits);
 void launch_amp_size(hipStream_t s, const AmpArgs& a, uint32_t* sizes);                    // bytes of every line; offsets: exclusive_scan_u32_to_u64
 void launch_amp_emit(hipStream_t s, const AmpArgs& a, const uint64_t* offs, uint32_t lds, char* out);   // lds: the LDS run in bytes (0: AMP_LDS); out 16-byte aligned
+
+// ---- artefact table (scs_k_sites.hip; scs_write_artefacts / scs_artefact_sites): the amplicons' edits grouped by genome site, a
+// slab of genome indices at a time (scs_site.h).  AmpArgs names the amplicons [first, first + n) as above
+struct SiteRec;
+struct SiteArgs {
+    const uint64_t* keys; const uint32_t* reads; uint64_t n;                       // the slab's sorted edit entries: key, reads of the amplicon
+    const uint64_t* starts; const uint64_t* ps_start; const uint64_t* ends; const uint64_t* ps_end; uint64_t m;   // its amplicons' sorted starts / ends (m each) and the prefix sums of their reads (m + 1)
+    const uint8_t* g; const uint64_t* rec_off; const uint32_t* name_off; const char* names; uint32_t n_rec, min_reads; uint32_t* flags;
+};
+#define SITE_LDS 16384u                                    // bytes of one workgroup's run of lines in the emit pass
+#define SITE_LDS_SLABS 1024u                               // slabs the counting pass sums in LDS (more: every add goes to memory)
+void launch_site_count(hipStream_t s, const AmpArgs& a, uint64_t slab, uint32_t n_slabs, unsigned long long* cnt);   // cnt[2 k] += edit entries in slab k, cnt[2 k + 1] += amplicons that overlap it
+void launch_site_fill(hipStream_t s, const AmpArgs& a, uint64_t x0, uint64_t x1, unsigned long long* cur, uint64_t cap_e, uint64_t cap_a,
+                      uint64_t* keys, uint32_t* kreads, uint64_t* starts, uint64_t* ends, uint32_t* areads);           // appends the slab [x0, x1)'s entries behind cur[0] / cur[1]
+void launch_site_check(hipStream_t s, const unsigned long long* cur, uint64_t n_e, uint64_t n_a, uint32_t* flags);  // FLAG_SITE unless the cursors stand at the counts
+size_t site_sort_temp_bytes(size_t n);
+void launch_site_sort(hipStream_t s, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n, unsigned end_bit, void* temp, size_t temp_bytes);
+void launch_site_reduce(hipStream_t s, const SiteArgs& t, SiteRec* recs, uint32_t* sizes, uint32_t* keep);           // per entry: its site and line size if it opens a run and is reported, else 0 / 0
+void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out);   // lds: the LDS run in bytes (0: SITE_LDS); out 16-byte aligned
+void launch_site_compact(hipStream_t s, const SiteRec* recs, const uint32_t* keep, const uint32_t* pos, uint64_t n, SiteRec* out);
 
 }  // namespace scs

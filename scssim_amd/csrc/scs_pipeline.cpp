@@ -48,6 +48,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_TRUTH) m += " truth SAM / BAM (a read with more than 32 indel events, pair flags that are not a strand, or a pair whose BAM records outgrow the emit pass' LDS)";
         if (f & FLAG_DEPTH) m += " depth track (a read with more than 32 indel events, pair flags that are not a strand, or a read placed outside its record)";
         if (f & FLAG_AMP) m += " amplicon table (a lineage that does not fit its parents, view flags that are not a strand, an amplicon outside its record, or a line the two passes size differently)";
+        if (f & FLAG_SITE) m += " artefact table (an amplicon that cannot be placed, a slab whose entries differ from their count, site counts that contradict each other, or a line the two passes size differently)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }

@@ -3,6 +3,7 @@
 // scans, DevBuf, Philox, det_log, Profile::predict), and the census of live device resources.  Nothing here is on a job's path.
 #include "scs_ctx.h"
 #include "scs_amp.h"
+#include "scs_site.h"
 
 // host-only: one read's record through the formatter the truth kernels run (scs_truth.h), as SAM text or as a BAM record
 static int truth_probe(bool bam, int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
@@ -110,6 +111,23 @@ int scs_amplicon_line_probe(uint64_t frag_goff, uint32_t frag_len, int frag_stra
     if (rc) return rc;
     *n_out = line.size();
     if (out) { if (line.size() > cap) return SCS_EOVERFLOW; memcpy(out, line.data(), line.size()); }
+    return SCS_OK;
+}
+
+// host-only: the artefact table's body (flags & 1: behind its header) through the functions its kernels run (site_probe, scs_site.h)
+int scs_artefact_probe(const uint64_t* amp_start, const uint32_t* amp_len, const uint32_t* amp_reads, uint64_t n_amp,
+                       const uint32_t* ed_amp, const uint64_t* ed_x, const uint8_t* ed_alt, uint64_t n_ed,
+                       const uint64_t* rec_len, const char* const* rec_names, uint32_t n_rec, const char* genome, uint64_t genome_len,
+                       uint32_t min_reads, int flags, char* out, size_t cap, size_t* n_out) {
+    if (!n_out || !rec_names || !n_rec || (flags & ~1)) return SCS_EINVAL;
+    std::vector<std::string> names;
+    for (uint32_t r = 0; r < n_rec; ++r) { if (!rec_names[r]) return SCS_EINVAL; names.push_back(rec_names[r]); }
+    std::string body;
+    const int rc = site_probe(amp_start, amp_len, amp_reads, n_amp, ed_amp, ed_x, ed_alt, n_ed, rec_len, names, genome, genome_len, min_reads, body);
+    if (rc) return rc;
+    if (flags & 1) body = site_header(names, rec_len) + body;
+    *n_out = body.size();
+    if (out) { if (body.size() > cap) return SCS_EOVERFLOW; memcpy(out, body.data(), body.size()); }
     return SCS_OK;
 }
 

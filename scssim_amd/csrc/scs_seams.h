@@ -10,6 +10,8 @@
 //   SCS_TEST_TRUTH_LDS  bytes of LDS the truth BAM's emit pass fills before it copies a run out (small: several runs per workgroup)
 //   SCS_TEST_DEPTH_SLOTS  entries of the depth kernel's LDS table (a power of two up to 512; 4: it overflows into direct adds, 0: no table, every add goes to memory)
 //   SCS_TEST_AMP_CHUNK  amplicons per chunk of the amplicon table (scs_amplicons.cpp)       SCS_TEST_AMP_LDS  bytes of its emit pass' LDS run (small: lines straddle two runs)
+//   SCS_TEST_SITE_SLAB  genome indices per slab of the artefact table (scs_sites.cpp; small: amplicons and sites on both sides of slab borders; its fill and counting passes also take SCS_TEST_AMP_CHUNK)
+//   SCS_TEST_SITE_LDS  bytes of its emit pass' LDS run (small: lines straddle two runs)       SCS_TEST_SITE_PIECE  bytes of its file that cross to the host at a time
 // (SCS_ATTACH_GROUPS / SCS_ATTACH_G began as tuning seams; tests/test_gpu_attach.py now runs k_attach<false, 2 / 4 / 8 / 16> through them.)
 #pragma once
 namespace scs { const char* seam_env(const char* name); }
