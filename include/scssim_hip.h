@@ -357,6 +357,44 @@ int         scs_artefact_probe(const uint64_t* amp_start, const uint32_t* amp_le
                                const uint32_t* ed_amp, const uint64_t* ed_x, const uint8_t* ed_alt, uint64_t n_ed,
                                const uint64_t* rec_len, const char* const* rec_names, uint32_t n_rec, const char* genome, uint64_t genome_len,
                                uint32_t min_reads, int flags, char* out, size_t cap, size_t* n_out);
+/* ---- site support: what the reads of a yield call show at the artefact sites, counted on the GPU ----------------------------
+ * The artefact table's NR / TR is the EXPECTED allele fraction; these counters are the OBSERVED one, after fragment sampling,
+ * sequencing errors, indels and trimming.  scs_set_site_support(ctx, 1, min_reads): every later yield call first makes the site
+ * table scs_artefact_sites(ctx, min_reads, ..) reports (same sites, order, NA / TA / NR / TR; kept on the device) and the distinct
+ * genome positions of its sites (two alternate bases at one coordinate share a position; at most 2^29 - 1 positions, SCS_EOVERFLOW
+ * beyond -- raise min_reads), then counts per batch, right after the base pass: per position six uint32 counters,
+ *   0..3  reads whose aligned base there is A, C, G, T     4  any other character (N)     5  reads whose CIGAR deletes the position
+ * The alignment is the truth SAM's (POS, CIGAR, SEQ: genome-forward, a read with flag 0x10 shows the complement of its FASTQ base;
+ * inserted bases align to no position; leading and trailing deletions are dropped).  Every read with a FASTQ record counts, both
+ * mates of a pair separately, also where they overlap.  Per site DP = classes 0..4, AD = (class of REF -- N: class 4 --, class of
+ * ALT), DL = class 5.  The counters are zeroed on the ctx stream at the start of every yield call and hold that call's job; they do
+ * not depend on batch cuts, the sink, its writers or whether the text leaves the GPU, and work beside either truth output and the
+ * depth track.  A sharded ctx fails the yield call (SCS_EINVAL, naming this setter); 2^32 planned reads or more: SCS_EINVAL.  A read
+ * that cannot be counted right fails the call with SCS_EOVERFLOW ("site support"), never a wrong count.  Off (the default): no
+ * buffer exists and no code of it runs.  scs_set_site_support(ctx, 0, ..) releases every buffer of the feature.
+ * scs_site_support: the sites and their counters after a yield call with the feature on (SCS_EINVAL before one has finished); the
+ * arrays as scs_artefact_sites', counts = 6 per site (A, C, G, T, other, deleted at the site's coordinate); any array may be NULL;
+ * *n is always set, SCS_EOVERFLOW when cap < *n (cap = 0 asks for the count); synchronises the ctx stream itself.
+ * scs_write_site_support: scs_write_artefacts' file at the same min_reads with three more ##INFO lines (DP, AD with Number=2, DL)
+ * behind the four and ";DP=d;AD=r,a;DL=x" at the end of every line, made on the GPU; flags: 1 = BGZF as there, any other bit
+ * SCS_EINVAL; SCS_EIO: the file cannot be opened or written, the ctx stays usable.
+ * scs_site_support_kernel_time: event pairs (one per batch), milliseconds and pairs of the last yield call's k_support launches
+ * (not a slot of scs_kernel_time). */
+int         scs_set_site_support(scs_ctx* ctx, int on, uint32_t min_reads);
+int         scs_site_support(scs_ctx* ctx, uint32_t* rec, uint64_t* pos, uint8_t* ref, uint8_t* alt, uint32_t* na, uint32_t* ta, uint64_t* nr, uint64_t* tr,
+                             uint32_t* counts /* 6 per site: A,C,G,T,other,deleted at the site's coordinate */, uint64_t cap, uint64_t* n);
+int         scs_write_site_support(scs_ctx* ctx, const char* path, int flags, uint64_t* sites, uint64_t* bytes);
+int         scs_site_support_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+/* Host-only test seams of the site support (no GPU, no ctx).  scs_support_read_probe: one read through the function the kernel runs;
+ * n, pos0, reverse, events, nev, rec_len as for scs_depth_read_probe; seq = the FASTQ record's len bases (read orientation);
+ * positions = n_pos record coordinates, ascending and distinct.  index / cls receive (position index, class) in ascending order
+ * (cap entries; *n_out their number).  SCS_EINVAL: not a valid alignment inside the record, more than 32 events, len is not the
+ * read's length, positions out of order; SCS_EOVERFLOW: cap too small.  scs_site_support_line_probe: one site's line through the
+ * formatter the emit kernel runs; counts = its six counters, or NULL for the artefact table's line. */
+int         scs_support_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, const char* seq, int len,
+                                   const uint64_t* positions, uint64_t n_pos, uint64_t* index, uint8_t* cls, int cap, int* n_out);
+int         scs_site_support_line_probe(const char* name, uint64_t pos, uint32_t ref, uint32_t alt, uint32_t na, uint32_t ta, uint64_t nr, uint64_t tr,
+                                        const uint32_t* counts, char* out, size_t cap, size_t* n_out);
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);

@@ -363,6 +363,48 @@ def depth_read_probe(pos0, n, events=(), reverse=False, rec_len=1 << 40, bin_wid
     return first.value, [(bins[i], bases[i]) for i in range(k.value)]
 
 
+def support_read_probe(pos0, n, seq, positions, events=(), reverse=False, rec_len=1 << 40):
+    """Host-only: what one read shows at the listed record coordinates, through the function the site support kernel runs.  pos0, n,
+    events, reverse, rec_len as for depth_read_probe; seq = the FASTQ record's bases; positions ascending and distinct.  Returns
+    [(position index, class), ...] in ascending order: class 0..3 = A, C, G, T (genome-forward), 4 = other, 5 = deleted."""
+    import numpy as np
+    L = load_library()
+    L.scs_support_read_probe.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_char_p, C.c_int,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    ev = (C.c_int32 * max(1, 3 * len(events)))(*[int(v) for e in events for v in e])
+    seq = seq.encode() if isinstance(seq, str) else bytes(seq)
+    pos = np.ascontiguousarray(list(positions), np.uint64)             # (exactly its size: the sanitizer tool's twin reads no further)
+    k = C.c_int()
+    args = (int(n), int(pos0), int(bool(reverse)), ev, len(events), int(rec_len), seq, len(seq), pos.ctypes.data if pos.size else None, pos.size)
+    rc = L.scs_support_read_probe(*args, None, None, 0, C.byref(k))
+    if rc not in (SCS_OK, SCS_EOVERFLOW):
+        raise ScsError(rc, "scs_support_read_probe: not a valid alignment inside the record, or positions out of order")
+    idx, cls = np.zeros(max(1, k.value), np.uint64), np.zeros(max(1, k.value), np.uint8)
+    rc = L.scs_support_read_probe(*args, idx.ctypes.data, cls.ctypes.data, k.value, C.byref(k))
+    if rc:
+        raise ScsError(rc, "scs_support_read_probe")
+    return [(int(idx[i]), int(cls[i])) for i in range(k.value)]
+
+
+def site_support_line_probe(name, pos, ref, alt, na, ta, nr, tr, counts=None):
+    """Host-only: one site's line through the formatter the emit kernel runs; counts = its six counters (A, C, G, T, other, deleted),
+    or None for the artefact table's line.  pos 0-based, ref a code 0..4, alt 0..3."""
+    L = load_library()
+    L.scs_site_support_line_probe.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                                              C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    cn = (C.c_uint32 * 6)(*[int(v) for v in counts]) if counts is not None else None
+    args = [name.encode(), int(pos), int(ref), int(alt), int(na), int(ta), int(nr), int(tr), cn]
+    n = C.c_size_t()
+    rc = L.scs_site_support_line_probe(*args, None, 0, C.byref(n))
+    if rc:
+        raise ScsError(rc, "scs_site_support_line_probe")
+    out = C.create_string_buffer(max(1, n.value))
+    rc = L.scs_site_support_line_probe(*args, out, n.value, C.byref(n))
+    if rc:
+        raise ScsError(rc, "scs_site_support_line_probe")
+    return out.raw[:n.value].decode()
+
+
 def amplicon_line_probe(frag, semi, full, genome, genome_start=0, rec_off=0, rec_len=None, rec_name="chr", index=0, reads=0, semi_index=0):
     """Host-only: one line of the amplicon table through the functions its kernels run.  frag = (genome offset, length, strand);
     semi / full = (spos, length, [(pos, alt), ...]) with alt a base code 0..3; genome = the bases from genome index genome_start on;
@@ -749,6 +791,44 @@ class GenReads:
         self._L.scs_artefact_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
         self._ck(self._L.scs_artefact_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def set_site_support(self, on, min_reads=0):
+        """Site support on / off: every later yield call counts, on the GPU, what its reads show at the coordinates of the artefact
+        sites with NR >= min_reads (artefact_sites(min_reads)): six counters per position.  Off releases every buffer of it."""
+        self._L.scs_set_site_support.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        self._ck(self._L.scs_set_site_support(self._ctx, 1 if on else 0, int(min_reads)))
+
+    def site_support(self):
+        """The last yield call's sites and counters as a dict of numpy arrays, one entry per site in file order: artefact_sites' arrays
+        and counts, uint32 [sites, 6]: reads that show A, C, G, T, another character, a deletion at the site's coordinate."""
+        np = self._np
+        fn = self._L.scs_site_support
+        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 9 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        n = C.c_uint64()
+        rc = fn(self._ctx, *([None] * 9), 0, C.byref(n))
+        if rc and not (rc == SCS_EOVERFLOW and n.value):
+            self._ck(rc)
+        a = dict(rec=np.zeros(n.value, np.uint32), pos=np.zeros(n.value, np.uint64), ref=np.zeros(n.value, np.uint8), alt=np.zeros(n.value, np.uint8),
+                 na=np.zeros(n.value, np.uint32), ta=np.zeros(n.value, np.uint32), nr=np.zeros(n.value, np.uint64), tr=np.zeros(n.value, np.uint64),
+                 counts=np.zeros((n.value, 6), np.uint32))
+        if n.value:
+            self._ck(fn(self._ctx, *[a[k].ctypes.data for k in ("rec", "pos", "ref", "alt", "na", "ta", "nr", "tr", "counts")], n.value, C.byref(n)))
+        return a
+
+    def write_site_support(self, path, bgzf=False):
+        """The artefact VCF of the same min_reads with DP / AD / DL of the last yield call's reads at the end of every line, made on
+        the GPU.  Returns dict(sites=, bytes=)."""
+        self._L.scs_write_site_support.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        n, b = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.scs_write_site_support(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n), C.byref(b)))
+        return dict(sites=n.value, bytes=b.value)
+
+    def site_support_kernel_time(self):
+        """Event pairs (one per batch), milliseconds and pairs of the last yield call's k_support launches."""
+        self._L.scs_site_support_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(self._L.scs_site_support_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
         return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def download_frags(self):

@@ -262,6 +262,13 @@ struct scs_ctx {
     // totals in pinned words behind ev_am_n / ev_am_made.  Every buffer holds one chunk and is released when the call returns
     DevBuf am_recs, am_sizes, am_offs, am_scan, am_bin, am_out[2]; BgzfLane am_z; Pinned<char> h_am[2]; Pinned<uint64_t> h_am_n; Event ev_am_n, ev_am_made[2], ev_am_d2h[2];
     KernelTimer tm_amp{"k_amplicons"};                    // the last scs_write_amplicons call's kernels (scs_amplicon_kernel_time; not one of tm[])
+    // site support (scs_set_site_support; scs_support.cpp): off -- no buffer below exists, no code of it runs.  The
+    // last yield call's site table (the artefact table's sites at support_min_reads, packed in order), every site's position index, the
+    // distinct positions (global genome indices, ascending), six uint32 counters per position (zeroed on the ctx stream at the start
+    // of every call; support_valid: a call with it on has finished) and the kernel's record starts
+    bool support_on = false, support_valid = false; uint32_t support_min_reads = 0; uint64_t sp_n_sites = 0, sp_n_pos = 0;
+    DevBuf sp_sites, sp_site_pos, sp_pos, sp_cnt, sp_tab;
+    KernelTimer tm_support{"k_support"};                  // the last yield call's k_support launches (scs_site_support_kernel_time; not one of tm[])
     KernelTimer tm_site{"k_sites"};                       // the last scs_write_artefacts call's kernels (scs_artefact_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
@@ -366,6 +373,9 @@ void truth_check(scs_ctx* c, bool device, int writers);
 // depth track: refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the staged records' bins (SCS_EINVAL beyond DEPTH_MAX_BINS)
 void depth_check(scs_ctx* c);
 uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);
+// site support (scs_support.cpp): refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the call's site table, positions and zeroed counters
+void support_check(scs_ctx* c);
+void support_open(scs_ctx* c);
 std::vector<int> gpu_local_cpus(int device);   // scs_sink.cpp
 
 template <class F>

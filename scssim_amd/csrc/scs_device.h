@@ -105,8 +105,8 @@ struct AllocPlan {
 struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned long long go[ALLOC_SLOTS]; };
 
 // error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right,
-// 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256 };
+// 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table, 9 for the site support counters
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -296,7 +296,28 @@ void launch_site_check(hipStream_t s, const unsigned long long* cur, uint64_t n_
 size_t site_sort_temp_bytes(size_t n);
 void launch_site_sort(hipStream_t s, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n, unsigned end_bit, void* temp, size_t temp_bytes);
 void launch_site_reduce(hipStream_t s, const SiteArgs& t, SiteRec* recs, uint32_t* sizes, uint32_t* keep);           // per entry: its site and line size if it opens a run and is reported, else 0 / 0
-void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out);   // lds: the LDS run in bytes (0: SITE_LDS); out 16-byte aligned
+// lds: the LDS run in bytes (0: SITE_LDS); out 16-byte aligned.  site_pos / counts (the site support table; else null): entry j's
+// line ends with the six counters at counts[6 site_pos[j]]
+void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out, const uint32_t* site_pos = nullptr, const uint32_t* counts = nullptr);
 void launch_site_compact(hipStream_t s, const SiteRec* recs, const uint32_t* keep, const uint32_t* pos, uint64_t n, SiteRec* out);
+
+// ---- site support (scs_k_support.hip; scs_set_site_support): per batch, what its reads show at the artefact
+// sites' coordinates -- six counters per listed position (A, C, G, T, other, deleted), summed per workgroup in an LDS table of `slots`
+// entries (a power of two <= SUPPORT_LDS_SLOTS; 0: every add goes to memory)
+#define SUPPORT_MAX_POS ((1u << 29) - 1u)                  // listed positions (key = position index << 3 | class is a uint32)
+#define SUPPORT_LDS_SLOTS 1024u
+struct SupportArgs : PlaceArgs {
+    const uint64_t* off1; const uint64_t* off2; const char* fq1; const char* fq2;   // the batch's FASTQ text and record offsets (OFF_MASK)
+    const uint64_t* rec_off; uint32_t n_rec;               // record starts (n_rec + 1)
+    const uint64_t* sp_pos; uint64_t n_pos;                // the listed positions: global genome indices, ascending
+    uint32_t* counts; uint32_t slots;                      // six counters per position
+};
+void launch_support(hipStream_t s, const SupportArgs& a);
+// the sorted sites' distinct global indices: head[i] = site i opens a coordinate; then (e = the exclusive scan of head) pos[e[i]] =
+// its index for every head, site_pos[i] = the position of site i
+void launch_support_heads(hipStream_t s, const SiteRec* sites, uint64_t n, const uint64_t* rec_off, uint32_t n_rec, uint32_t* head, uint32_t* flags);
+void launch_support_scatter(hipStream_t s, const SiteRec* sites, uint64_t n, const uint64_t* rec_off, const uint32_t* head, const uint32_t* e, uint64_t* pos, uint32_t* site_pos);
+// bytes of every site's line with its counters (site_line through a counting sink); offsets: exclusive_scan_u32_to_u64
+void launch_support_size(hipStream_t s, const SiteArgs& t, const SiteRec* sites, const uint32_t* site_pos, const uint32_t* counts, uint32_t* sizes);
 
 }  // namespace scs

@@ -114,8 +114,9 @@ struct SiteWinOut {
 
 // one workgroup per 256 entries (k_amp_emit's scheme): window by window the lanes whose entry is a reported site format the
 // lines that touch the window, then the workgroup copies the window's part of its text out: whole aligned 16-byte chunks, single
-// bytes at the two ends
-__global__ void __launch_bounds__(256) k_site_emit(SiteArgs T, const SiteRec* __restrict__ recs, const uint64_t* __restrict__ offs, uint32_t lds, char* __restrict__ out) {
+// bytes at the two ends.  counts (the site support table; else null): the line ends with the six counters of the entry's position
+__global__ void __launch_bounds__(256) k_site_emit(SiteArgs T, const SiteRec* __restrict__ recs, const uint64_t* __restrict__ offs, uint32_t lds, char* __restrict__ out,
+                                                   const uint32_t* __restrict__ site_pos, const uint32_t* __restrict__ counts) {
     extern __shared__ uint4 s_run4[];
     char* s_run = reinterpret_cast<char*>(s_run4);
     const uint64_t j0 = (uint64_t)blockIdx.x * 256u, j1 = j0 + 256u < T.n ? j0 + 256u : T.n, j = j0 + threadIdx.x;
@@ -124,11 +125,12 @@ __global__ void __launch_bounds__(256) k_site_emit(SiteArgs T, const SiteRec* __
     const bool ok = mine && my1 > my0;
     SiteRec r; const char* name = nullptr; uint32_t name_len = 0;
     if (ok) { r = recs[j]; if (r.rec < T.n_rec) { name = T.names + T.name_off[r.rec]; name_len = T.name_off[r.rec + 1] - T.name_off[r.rec]; } }
+    const uint32_t* cnt = ok && counts ? counts + 6ull * site_pos[j] : nullptr;
     for (uint64_t wa = b0 & ~15ull; wa < b1; wa += lds) {  // (b0, b1 and lds are the workgroup's: every lane takes every turn)
         const uint64_t c0 = wa > b0 ? wa : b0, c1 = wa + lds < b1 ? wa + lds : b1;
         if (ok && my0 < c1 && my1 > c0) {
             SiteWinOut o{s_run, my0, wa, wa + lds};
-            site_line(o, name, name_len, r);
+            site_line(o, name, name_len, r, cnt);
             if (o.pos != my1) atomicOr(T.flags, (uint32_t)FLAG_SITE);   // (the sizing pass and the formatter disagree: never a silent wrong file)
         }
         __syncthreads();
@@ -176,11 +178,11 @@ void launch_site_reduce(hipStream_t s, const SiteArgs& t, SiteRec* recs, uint32_
     hipLaunchKernelGGL(k_site_reduce, dim3(cdiv(t.n, 256)), dim3(256), 0, s, t, recs, sizes, keep);
     note_launch(hipGetLastError());
 }
-void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out) {
+void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out, const uint32_t* site_pos, const uint32_t* counts) {
     if (t.n == 0) return;
     lds = lds ? std::min(lds, SITE_LDS) & ~15u : SITE_LDS; // whole 16-byte chunks, at least one
     if (lds < 16u) lds = 16u;
-    hipLaunchKernelGGL(k_site_emit, dim3(cdiv(t.n, 256)), dim3(256), SITE_LDS, s, t, recs, offs, lds, out);
+    hipLaunchKernelGGL(k_site_emit, dim3(cdiv(t.n, 256)), dim3(256), SITE_LDS, s, t, recs, offs, lds, out, site_pos, counts);
     note_launch(hipGetLastError());
 }
 void launch_site_compact(hipStream_t s, const SiteRec* recs, const uint32_t* keep, const uint32_t* pos, uint64_t n, SiteRec* out) {

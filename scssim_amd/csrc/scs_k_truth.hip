@@ -15,10 +15,6 @@ namespace scs {
 
 #define TRUTH_LDS 61440u                                   // bytes of one workgroup's run of records (dynamic LDS: 2 workgroups per CU)
 
-__device__ __forceinline__ uint32_t t_digits(uint32_t v) {
-    uint32_t d = 1; while (v >= 10u) { v /= 10u; ++d; } return d;
-}
-
 struct DevSrc {                                            // a read's FASTQ bases and qualities, the genome as characters
     const char* s; const char* q; const uint8_t* g;
     __device__ char seq(int i) const { return s[i]; }
@@ -32,8 +28,7 @@ struct PtrOut { char* p; __device__ void put(char ch) { *p++ = ch; } };
 __device__ bool truth_load(const TruthArgs& A, const PairRec& pr, uint32_t pi, uint32_t rd, uint32_t* ev, TruthAln& a, DevSrc& src) {
     int n_out;
     if (!read_place(A, pr, pi, rd, ev, a, n_out, (uint32_t)FLAG_TRUTH)) return false;
-    const char* rec = (rd ? A.fq2 : A.fq1) + ((rd ? A.off2 : A.off1)[pi] & OFF_MASK);
-    src.s = rec + 1u + t_digits(pr.amp) + 1u + t_digits(pr.att + 1u) + (A.paired ? 2u : 0u) + 1u;   // "@amp#cnt[/r]\n"
+    src.s = read_text(A.off1, A.off2, A.fq1, A.fq2, A.paired, pr, pi, rd);
     src.q = src.s + n_out + 3; src.g = A.g;
     return true;
 }

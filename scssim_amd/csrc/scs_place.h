@@ -1,6 +1,7 @@
 // scs_place.h -- where a read of a batch lies on the genome: its indel events (the indel pass' packed ones, or drawn again for a
 // replayed read) and its placement (truth_place, scs_truth.h).  The one definition behind the truth passes (scs_k_truth.hip),
-// which go on to the read's FASTQ text, and the depth pass (scs_k_depth.hip), which needs nothing else.
+// which go on to the read's FASTQ text (read_text), the site support pass (scs_k_support.hip), which reads its bases there, and the
+// depth pass (scs_k_depth.hip), which needs neither.
 // Needs scs_device.h and scs_kernels_common.h before it.
 #pragma once
 #include "scs_indel.h"
@@ -35,6 +36,15 @@ __device__ __forceinline__ bool read_place(const PlaceArgs& A, const PairRec& pr
     a.n = A.tb.L; a.nev = nev; a.ev = ev;
     if (!truth_place(a) || a.qlen != n_out) { atomicOr(A.flags, flag); return false; }
     return true;
+}
+
+// where the bases of read rd of pair pi lie in the batch's FASTQ text: behind the record's name line "@amp#cnt[/r]\n" (off1 / off2:
+// the mates' record offsets, OFF_MASK; fq1 / fq2: their text).  *rec receives the record's first byte, its '@'
+__device__ __forceinline__ const char* read_text(const uint64_t* off1, const uint64_t* off2, const char* fq1, const char* fq2, int paired, const PairRec& pr, uint32_t pi, uint32_t rd,
+                                                 const char** rec = nullptr) {
+    const char* r = (rd ? fq2 : fq1) + ((rd ? off2 : off1)[pi] & OFF_MASK);
+    if (rec) *rec = r;
+    return r + 1u + truth_digits(pr.amp) + 1u + truth_digits(pr.att + 1u) + (paired ? 2u : 0u) + 1u;
 }
 
 }  // namespace scs

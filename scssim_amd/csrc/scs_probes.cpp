@@ -4,6 +4,7 @@
 #include "scs_ctx.h"
 #include "scs_amp.h"
 #include "scs_site.h"
+#include "scs_support.h"
 
 // host-only: one read's record through the formatter the truth kernels run (scs_truth.h), as SAM text or as a BAM record
 static int truth_probe(bool bam, int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
@@ -96,6 +97,41 @@ int scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events
     *n_out = (int)runs.size();
     if ((int)runs.size() > cap) return SCS_EOVERFLOW;
     for (size_t i = 0; i < runs.size(); ++i) { bins[i] = runs[i].first; bases[i] = runs[i].second; }
+    return SCS_OK;
+}
+
+// host-only: one read through the function the site support kernel runs (support_read, scs_support.h) after the truth passes'
+// placement: seq = the FASTQ record's `len` bases, positions = the listed record coordinates, ascending and distinct
+int scs_support_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, const char* seq, int len,
+                           const uint64_t* positions, uint64_t n_pos, uint64_t* index, uint8_t* cls, int cap, int* n_out) {
+    if (!n_out || !seq || n <= 0 || nev < 0 || (nev && !events) || (n_pos && !positions) || cap < 0 || (cap && (!index || !cls))) return SCS_EINVAL;
+    for (uint64_t i = 1; i < n_pos; ++i) if (positions[i] <= positions[i - 1]) return SCS_EINVAL;
+    std::vector<uint32_t> ev;
+    for (int i = 0; i < nev; ++i) {
+        if (events[3 * i] < 0 || events[3 * i] > 0xFFFF || events[3 * i + 2] <= 0 || events[3 * i + 2] > 0x7FFF) return SCS_EINVAL;
+        ev.push_back(tev_pack((uint32_t)events[3 * i], events[3 * i + 1] ? 1u : 0u, (uint32_t)events[3 * i + 2]));
+    }
+    if (nev > TRUTH_EVCAP) return SCS_EINVAL;                                        // (the kernel raises FLAG_SUPPORT there)
+    TruthAln a{pos0, reverse ? 1 : 0, n, nev, ev.data(), 0, 0, 0};
+    if (!truth_place(a) || a.lo < 0 || a.hi >= (int64_t)rec_len || a.qlen != len) return SCS_EINVAL;
+    std::vector<std::pair<uint64_t, uint32_t>> got;
+    support_read(a, positions, n_pos, [&](int i) { return seq[i]; }, [&](uint64_t i, uint32_t k) { got.push_back({i, k}); });
+    *n_out = (int)got.size();
+    if ((int)got.size() > cap) return SCS_EOVERFLOW;
+    for (size_t i = 0; i < got.size(); ++i) { index[i] = got[i].first; cls[i] = (uint8_t)got[i].second; }
+    return SCS_OK;
+}
+// host-only: one site's line through the formatter the emit kernel runs (site_line, scs_site.h); counts: its six counters (the site
+// support table's line), or NULL (the artefact table's)
+int scs_site_support_line_probe(const char* name, uint64_t pos, uint32_t ref, uint32_t alt, uint32_t na, uint32_t ta, uint64_t nr, uint64_t tr, const uint32_t* counts,
+                                char* out, size_t cap, size_t* n_out) {
+    if (!name || !n_out || ref > 4u || alt > 3u) return SCS_EINVAL;
+    SiteRec r{pos, nr, tr, 0u, na, ta, (uint8_t)ref, (uint8_t)alt, {0, 0}};
+    struct StrOut { std::string t; void put(char ch) { t.push_back(ch); } } o;
+    TruthCount cnt; site_line(cnt, name, (uint32_t)strlen(name), r, counts); site_line(o, name, (uint32_t)strlen(name), r, counts);
+    if (cnt.n != o.t.size()) return SCS_EDEVICE;                                      // (the sizing pass' sink and the emit pass' must agree)
+    *n_out = o.t.size();
+    if (out) { if (o.t.size() > cap) return SCS_EOVERFLOW; memcpy(out, o.t.data(), o.t.size()); }
     return SCS_OK;
 }
 

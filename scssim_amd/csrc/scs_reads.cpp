@@ -167,12 +167,12 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0; const std::string tname = bam ? "truth BAM" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, truth_sum = 0, bi = 0;            // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
     FdGuard truth_fd;                                                              // (closed after the pipe's writers have ended: declared first)
-    PipeGuard guard{nullptr}; TruthArgs ta{}; DepthArgs da{};
+    PipeGuard guard{nullptr}; TruthArgs ta{}; DepthArgs da{}; SupportArgs sa{};
     // shard index: the pair index at which each list segment starts (pair_off at the segment's first amplicon); the byte offset of
     // that record = the bytes of the batches before its batch (known once every batch is made) + its offset inside the batch
     std::vector<uint64_t> bpair, bb[2]; std::vector<SegAt> seg_at;
@@ -222,6 +222,14 @@ struct Yield {               // the state of one do_yield call
         da.reads = c->dp_cnt.as<unsigned long long>(); da.bases = da.reads + nb;
         da.paired = paired; da.tb = c->dtb; da.key = c->key; da.slot = slot; da.flags = c->flags.as<uint32_t>();
     }
+    void support_open() {
+        // the call's site table, its distinct positions and this call's counters, zeroed on the ctx stream (scs_support.cpp)
+        static const uint32_t slots = seam_env("SCS_TEST_SUPPORT_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_SUPPORT_SLOTS")) : SUPPORT_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
+        scs::support_open(c);
+        sa.rec_off = c->sp_tab.as<uint64_t>(); sa.n_rec = (uint32_t)c->recs.size(); sa.sp_pos = c->sp_pos.as<uint64_t>(); sa.n_pos = c->sp_n_pos;
+        sa.counts = c->sp_cnt.as<uint32_t>(); sa.slots = slots;
+        sa.paired = paired; sa.tb = c->dtb; sa.key = c->key; sa.slot = slot; sa.flags = c->flags.as<uint32_t>();
+    }
     void setup() {           // the batches' bounds; the truth file; the pipe's writers; the BGZF totals' pinned words and events, the BGZF kernels' CRC tables; the batches' two buffer sets; the pre-pass' stream; the shard index
         // The pairs are planned (k_plan_pairs: insert sizes, positions, the amplicon resolved to an index map) batch by batch, at the
         // head of each batch's pre-pass: bounds[b] = the amplicon that holds the batch's first pair.
@@ -233,6 +241,7 @@ struct Yield {               // the state of one do_yield call
         }
         if (truth) truth_open();
         if (depth) depth_open();
+        if (support) support_open();
         if (to_sink) {
             if (!c->pipe) c->pipe.reset(new SinkPipe);
             c->copy_stream.ensure(hipStreamNonBlocking); for (int k = 0; k < 2; ++k) { c->ev_made[k].ensure(hipEventDisableTiming); c->ev_d2h[k].ensure(hipEventDisableTiming); }
@@ -384,6 +393,14 @@ struct Yield {               // the state of one do_yield call
         launch_depth(s, da);
         c->tm[TM_DEPTH].end(s); c->tm[TM_DEPTH].add_units(b.np);
     }
+    void support_batch(const Batch& b) {
+        // the batch's reads into the site counters, from its pair records, indel events and FASTQ text.  Before ev_free, as truth_batch,
+        // and before the sink takes the text
+        sa.pairs = b.pr; sa.np = b.np; sa.ev_hdr = b.B->ev_hdr; sa.ev_dat = b.B->ev_dat; sa.off1 = b.B->off[0]; sa.off2 = b.B->off[1]; sa.fq1 = b.out[0]; sa.fq2 = b.out[1];
+        c->tm_support.begin(s);
+        launch_support(s, sa);
+        c->tm_support.end(s); c->tm_support.add_units(b.np);
+    }
     void ship(Ship sh) {                                                           // D2H on the copy stream into a free pinned slot, then to the region's writer
         if (bgzf || (bam && sh.p[2])) HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl]));   // the blocks' totals have arrived
         if (bgzf) { sh.n[0] = c->h_z[sh.dsl * 3]; sh.n[1] = c->h_z[sh.dsl * 3 + 1]; }
@@ -434,8 +451,8 @@ struct Yield {               // the state of one do_yield call
         mail_wait(c); flags_eval(c);
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];
-        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect(); c->tm[TM_DEPTH].collect();
-        c->depth_valid = depth;
+        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect(); c->tm[TM_DEPTH].collect(); c->tm_support.collect();
+        c->depth_valid = depth; c->support_valid = support;
         c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
         for (int m = 0; m < 2; ++m) { c->st.fastq_bytes[m] = tot[m]; c->st.sink_bytes[m] = to_sink ? sunk[m] : 0; }
         // 1526 B per created amplicon + per pair (insert size + FASTQ bytes of both records)
@@ -453,8 +470,8 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     Yield y{c, tg}; const hipStream_t s = y.s; const uint64_t P = y.P;
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
-    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset(); c->tm[TM_DEPTH].reset();
-    c->depth_valid = false;
+    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset(); c->tm[TM_DEPTH].reset(); c->tm_support.reset();
+    c->depth_valid = false; c->support_valid = false;
     if (c->depth_width) (void)depth_ctx_layout(c, nullptr);   // more than 2^27 bins: refused before any GPU work
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
@@ -466,6 +483,10 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         for (size_t r = 0; r < c->rec_len.size(); ++r)
             if (c->rec_len[r] >= (1ull << 29)) throw ScsError(SCS_EINVAL, "truth BAM (scs_set_truth_bam): record " + c->recs[r].name + " has 2^29 bases or more (the BAM bin scheme ends there); the truth SAM (scs_set_truth_sam) has no such limit");
         if ((y.paired ? 2 * P : P) > 0x7FFFFFFFull) throw ScsError(SCS_EINVAL, "truth BAM (scs_set_truth_bam): more than 2^31 - 1 records");
+    }
+    if (y.support) {                                                               // refused before any GPU work: a 32-bit counter could wrap
+        support_check(c);
+        if ((y.paired ? 2 * P : P) >> 32) throw ScsError(SCS_EINVAL, "site support (scs_set_site_support): 2^32 reads or more are planned (the counters are 32 bits wide)");
     }
     static const int batch_shift = seam_env("SCS_TEST_BATCH_SHIFT") ? atoi(seam_env("SCS_TEST_BATCH_SHIFT")) : 0;   // tests: many small batches
     y.plan = plan_batches(P, y.L, y.to_sink, y.to_sink ? tg.sink->writers : 1, y.to_sink ? tg.sink->regions : 1, batch_shift);
@@ -481,6 +502,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         y.base_pass(b);
         if (y.truth) y.truth_batch(b);
         if (y.depth) y.depth_batch(b);
+        if (y.support) y.support_batch(b);
         if (y.ps != s) { HIP_OK(hipEventRecord(c->ev_free[b.k], s)); y.free_rec[b.k] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
         if (y.to_sink) y.sink_batch(b);                                            // BGZF where asked; then to the region's writer (with BGZF: the batch before)

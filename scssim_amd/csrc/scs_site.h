@@ -55,26 +55,39 @@ SCS_HD bool site_make(const uint64_t* keys, const uint32_t* reads, uint64_t n, u
     return rs >= re && rs - re >= na && ps_start[rs] >= ps_end[re] && r.tr >= nr && x < rec_off[n_rec];
 }
 
-// "NAME\tPOS\t.\tR\tA\t.\t.\tNA=..;TA=..;NR=..;TR=..\n" through o.put(char); POS = record coordinate + 1 (VCF 4.2)
+// "NAME\tPOS\t.\tR\tA\t.\t.\tNA=..;TA=..;NR=..;TR=..\n" through o.put(char); POS = record coordinate + 1 (VCF 4.2).  cnt (the site
+// support table; else NULL): the six read counters of the site's coordinate -- A, C, G, T, other, deleted --
+// which add ";DP=..;AD=ref,alt;DL=.." to INFO: DP their first five, AD the classes of REF (N: class 4) and of ALT, DL the sixth
 template <class Out>
-SCS_HD void site_line(Out& o, const char* name, uint32_t name_len, const SiteRec& r) {
+SCS_HD void site_line(Out& o, const char* name, uint32_t name_len, const SiteRec& r, const uint32_t* cnt = nullptr) {
     for (uint32_t i = 0; i < name_len; ++i) o.put(name[i]);
     o.put('\t'); truth_num(o, r.pos + 1); o.put('\t'); o.put('.'); o.put('\t'); o.put(amp_letter(r.ref)); o.put('\t'); o.put(amp_letter(r.alt));
     o.put('\t'); o.put('.'); o.put('\t'); o.put('.'); o.put('\t');
     o.put('N'); o.put('A'); o.put('='); truth_num(o, r.na); o.put(';'); o.put('T'); o.put('A'); o.put('='); truth_num(o, r.ta); o.put(';');
-    o.put('N'); o.put('R'); o.put('='); truth_num(o, r.nr); o.put(';'); o.put('T'); o.put('R'); o.put('='); truth_num(o, r.tr); o.put('\n');
+    o.put('N'); o.put('R'); o.put('='); truth_num(o, r.nr); o.put(';'); o.put('T'); o.put('R'); o.put('='); truth_num(o, r.tr);
+    if (cnt) {
+        const uint64_t dp = (uint64_t)cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4];
+        o.put(';'); o.put('D'); o.put('P'); o.put('='); truth_num(o, dp);
+        o.put(';'); o.put('A'); o.put('D'); o.put('='); truth_num(o, cnt[r.ref < 4u ? r.ref : 4u]); o.put(','); truth_num(o, cnt[r.alt & 3u]);
+        o.put(';'); o.put('D'); o.put('L'); o.put('='); truth_num(o, cnt[5]);
+    }
+    o.put('\n');
 }
 
 // ---- host-only
-// the file's header: one contig line per staged record, in staging order
-inline std::string site_header(const std::vector<std::string>& names, const uint64_t* rec_len) {
+// the file's header: one contig line per staged record, in staging order (support: the site support table's, three more INFO lines)
+inline std::string site_header(const std::vector<std::string>& names, const uint64_t* rec_len, bool support = false) {
     std::string h = "##fileformat=VCFv4.2\n##source=scssim\n";
     for (size_t r = 0; r < names.size(); ++r) h += "##contig=<ID=" + names[r] + ",length=" + std::to_string(rec_len[r]) + ">\n";
     h += "##INFO=<ID=NA,Number=1,Type=Integer,Description=\"full amplicons that carry the alternate base\">\n"
          "##INFO=<ID=TA,Number=1,Type=Integer,Description=\"full amplicons that cover the site\">\n"
          "##INFO=<ID=NR,Number=1,Type=Integer,Description=\"reads allotted to the NA amplicons\">\n"
-         "##INFO=<ID=TR,Number=1,Type=Integer,Description=\"reads allotted to the TA amplicons\">\n"
-         "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+         "##INFO=<ID=TR,Number=1,Type=Integer,Description=\"reads allotted to the TA amplicons\">\n";
+    if (support)                                           // the site support table's three (scs_write_site_support)
+        h += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"reads of the job with a base aligned at the site\">\n"
+             "##INFO=<ID=AD,Number=2,Type=Integer,Description=\"reads that show the reference base, reads that show the alternate base\">\n"
+             "##INFO=<ID=DL,Number=1,Type=Integer,Description=\"reads whose alignment deletes the site\">\n";
+    h += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
     return h;
 }
 
