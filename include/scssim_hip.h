@@ -276,6 +276,78 @@ int         scs_write_depth(scs_ctx* ctx, const char* path);
 int         scs_depth_layout_probe(const uint64_t* rec_lens, int n_records, uint32_t bin_width, uint64_t* bin_off, uint64_t* n_bins);
 int         scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, uint32_t bin_width,
                                  uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out);
+/* ---- lift table and depth by reference bin: the job in the coordinates of the original reference ---------------------------
+ * Every other truth product lives in the coordinates of the staged haplotype records.  The lift table maps them to the reference
+ * `simuvars` built them from: segments that ascend and tile the staged genome, none straddling two staged records, each `len`
+ * bases from global index hap_off (records concatenated in staging order).  kind 0 (R): copies of reference record ref_rec,
+ * 0-based [ref_pos, ref_pos + len); SNP / SNV substitutions do not break a segment.  kind 1 (I): inserted sequence, no reference
+ * coordinate; ref_rec = the chromosome of its staged record, ref_pos = an anchor for information only (the end of the R segment
+ * before it in its record; none: the start of the next; no R segment in the record: 0).  The table is maximal (no two
+ * neighbours could be one) and belongs to the staged genome: every call that stages another genome drops it.
+ * scs_simuvars keeps the table of the genome it builds (nothing else about that call changes).
+ * scs_write_lift: the table as tab-separated text with BED coordinates inside the records:
+ *     ##scssim-lift v1
+ *     #ref  <name> <length>                         one per reference record, in order
+ *     #hap  <name> <length>                         one per staged record, in staging order
+ *     <hap name> <hap start> <hap end> <ref name> <ref start> <ref end> R|I         (I: ref start = ref end = the anchor)
+ * scs_load_lift: reads such a file for the genome that is staged (the two-step flow: `scssim simuvars --lift`, later `genreads
+ * -i simu.fa --lift`).  SCS_EINVAL: its #hap names and lengths are not the staged records' (the first record that differs is
+ * named).  SCS_EIO with the line number: a missing header, a wrong column count, an unknown record name, a gap, an overlap or
+ * lines out of order, a segment past its staged or its reference record, an R line whose two lengths differ.
+ * scs_lift_info: the table's size.  scs_lift_segments: the table as arrays (any may be NULL), read back from the device copy;
+ * ref_lens: the reference records' lengths (ref_cap entries of room).  SCS_EOVERFLOW: cap / ref_cap is too small.
+ * scs_lift_positions: n staged positions (rec[i] = staged record, pos[i] = 0-based coordinate in it; host arrays) lifted on the
+ * device: ref_rec / ref_pos / kind per position (I: the anchor).  How POS columns of the truth SAM, the amplicon table and the
+ * artefact VCF are lifted.  SCS_EINVAL: a position outside its record.
+ *
+ * scs_set_depth_ref(ctx, bin_width): the following yield calls also count the job per bin of bin_width >= 1 bases of the REFERENCE
+ * records (0: off, the default -- no buffer exists, no code of it runs).  Bins are numbered as scs_set_depth numbers them, over the
+ * reference lengths (the same 2^27 cap); one extra pseudo-bin at index n_bins collects what has no reference coordinate.  Placement
+ * is the truth SAM's.  bases[b] = (read, haplotype base) pairs an M operation aligns whose base lies in an R segment and lifts into
+ * bin b (in an I segment: the pseudo-bin).  reads[b] = FASTQ records whose first M-aligned base with a reference coordinate, in
+ * ascending haplotype order, lifts into b (no such base: the pseudo-bin).  So the sum of reads is scs_stats.reads_written and the
+ * sum of bases is the sum of the CIGARs' M lengths.  copies[b] = haplotype bases of R segments that lift into b, made once per
+ * layout, independent of the reads: copies[b] / (end - start) is the bin's true copy number; copies[n_bins] = inserted bases.
+ * Which reads, the counters' lifetime and where it works: as scs_set_depth, beside it and beside the site support.  A sharded ctx,
+ * or a staged genome without a lift table, fails the yield call with SCS_EINVAL.
+ * scs_depth_ref_bins / scs_depth_ref_record_bins: the layout (bin_off: reference records + 1 entries).
+ * scs_download_depth_ref: n_bins + 1 entries each (any pointer may be NULL); SCS_EINVAL before a yield call with it on has finished.
+ * scs_write_depth_ref: "#record\tstart\tend\treads\tbases\tcopies", one line per bin with the reference's record names, then
+ * "#unlifted\t<reads>\t<bases>\t<inserted bases>".
+ * scs_depth_ref_kernel_time: event pairs (one per batch), milliseconds and pairs of the last yield call's k_depth_lift launches
+ * (scs_kernel_time keeps its slots). */
+int         scs_write_lift(scs_ctx* ctx, const char* path);
+int         scs_load_lift(scs_ctx* ctx, const char* path);
+int         scs_lift_info(const scs_ctx* ctx, uint64_t* n_segments, uint32_t* n_ref_records);
+int         scs_lift_segments(scs_ctx* ctx, uint64_t* hap_off, uint64_t* len, uint64_t* ref_pos, uint32_t* ref_rec, uint32_t* kind, uint64_t cap, uint64_t* ref_lens, uint32_t ref_cap);
+int         scs_lift_positions(scs_ctx* ctx, const uint32_t* rec, const uint64_t* pos, uint64_t n, uint32_t* ref_rec, uint64_t* ref_pos, uint32_t* kind);
+int         scs_set_depth_ref(scs_ctx* ctx, uint32_t bin_width);
+int         scs_depth_ref_bins(const scs_ctx* ctx, uint64_t* n_bins, uint32_t* bin_width);
+int         scs_depth_ref_record_bins(const scs_ctx* ctx, uint64_t* bin_off, uint64_t cap);
+int         scs_download_depth_ref(scs_ctx* ctx, uint64_t* reads, uint64_t* bases, uint64_t* copies, uint64_t cap);
+int         scs_write_depth_ref(scs_ctx* ctx, const char* path);
+int         scs_depth_ref_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+/* Host-only test seams of the lift table (no GPU, no ctx).  scs_lift_plan_probe: plans scs_simuvars for these inputs, builds the
+ * table and (out_path) writes the file; the table comes back as arrays (any may be NULL; *n_seg, *n_hap, *n_ref are always set;
+ * SCS_EOVERFLOW: a cap is too small), names = the reference records' names then the staged records', a newline behind each;
+ * subst_pos = the global staged indices the plan substitutes.  scs_lift_file_probe: the parser scs_load_lift runs; SCS_EIO with
+ * *line (0: the file cannot be opened) when it is refused.  scs_lift_read_probe: one read through the function k_depth_lift runs;
+ * n, reverse, events, nev as for scs_truth_record_probe, pos0 = GLOBAL staged index of window base 0; the table and the records as
+ * arrays.  *reads_bin and bins[i] / bases[i], i < *n_out: the increments in the order the kernel makes them (a bin met again after a
+ * jump comes again), bins numbered over ref_lens, the pseudo-bin = their total.  SCS_EINVAL: not a valid alignment, or the read
+ * cannot be lifted -- *lift_err then says why (1 placed outside its record, 2 off the table, 3 lifted outside the reference). */
+int         scs_lift_plan_probe(const char* ref_fasta, const char* snp_file, const char* var_file, const char* out_path,
+                                uint64_t* hap_off, uint64_t* len, uint64_t* ref_pos, uint32_t* ref_rec, uint32_t* kind, uint64_t seg_cap, uint64_t* n_seg,
+                                uint64_t* subst_pos, uint64_t subst_cap, uint64_t* n_subst,
+                                uint64_t* hap_lens, uint64_t* ref_lens, uint32_t rec_cap, uint32_t* n_hap, uint32_t* n_ref,
+                                char* names, size_t names_cap, size_t* names_len, char* errbuf, size_t errlen);
+int         scs_lift_file_probe(const char* path, uint64_t* hap_off, uint64_t* len, uint64_t* ref_pos, uint32_t* ref_rec, uint32_t* kind, uint64_t seg_cap, uint64_t* n_seg,
+                                uint64_t* hap_lens, uint64_t* ref_lens, uint32_t rec_cap, uint32_t* n_hap, uint32_t* n_ref,
+                                char* names, size_t names_cap, size_t* names_len, uint64_t* line, char* errbuf, size_t errlen);
+int         scs_lift_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev,
+                                const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                                const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, uint32_t bin_width,
+                                uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out, int* lift_err);
 /* ---- amplicon table: the amplified pool the reads were drawn from, made on the GPU ---------------------------------------
  * One entry per FULL amplicon, in list order: entry i is the amplicon whose index the FASTQ / SAM record names print.
  *   rec          the staged record the amplicon lies in (a fragment never straddles records)

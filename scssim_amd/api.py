@@ -363,6 +363,103 @@ def depth_read_probe(pos0, n, events=(), reverse=False, rec_len=1 << 40, bin_wid
     return first.value, [(bins[i], bases[i]) for i in range(k.value)]
 
 
+class LiftTable:
+    """A lift table as numpy arrays: per segment hap_off (global staged index), len, ref_pos, ref_rec, kind (0: R, 1: I); the
+    reference records' and the staged records' names and lengths."""
+
+    def __init__(self, hap_off, length, ref_pos, ref_rec, kind, ref_names=None, ref_lens=None, hap_names=None, hap_lens=None):
+        self.hap_off, self.len, self.ref_pos, self.ref_rec, self.kind = hap_off, length, ref_pos, ref_rec, kind
+        self.ref_names, self.ref_lens, self.hap_names, self.hap_lens = ref_names, ref_lens, hap_names, hap_lens
+
+    def __len__(self):
+        return len(self.hap_off)
+
+    def same_segments(self, other):
+        return all((getattr(self, k) == getattr(other, k)).all() if len(self) == len(other) else False for k in ("hap_off", "len", "ref_pos", "ref_rec", "kind"))
+
+
+def _lift_probe(call):
+    """The two-call pattern of scs_lift_plan_probe / scs_lift_file_probe: sizes first, then the arrays."""
+    import numpy as np
+    n_seg, n_hap, n_ref, n_names = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_size_t()
+    call(None, None, None, None, None, 0, n_seg, None, None, 0, n_hap, n_ref, None, 0, n_names)
+    ns, nr = n_seg.value, max(n_hap.value, n_ref.value)
+    a = [np.zeros(max(ns, 1), np.uint64) for _ in range(3)] + [np.zeros(max(ns, 1), np.uint32) for _ in range(2)]
+    hap_lens, ref_lens = np.zeros(max(nr, 1), np.uint64), np.zeros(max(nr, 1), np.uint64)
+    names = C.create_string_buffer(max(1, n_names.value))
+    call(*[x.ctypes.data for x in a], ns, n_seg, hap_lens.ctypes.data, ref_lens.ctypes.data, nr, n_hap, n_ref, names, n_names.value, n_names)
+    nm = names.raw[:n_names.value].decode().split("\n")[:-1]
+    return LiftTable(*[x[:ns] for x in a], ref_names=nm[:n_ref.value], ref_lens=ref_lens[:n_ref.value], hap_names=nm[n_ref.value:], hap_lens=hap_lens[:n_hap.value])
+
+
+def lift_plan_probe(ref_fasta, snp_file=None, var_file=None, out_path=None):
+    """Host-only: (LiftTable, substituted global staged indices) of the genome GenReads.simuvars would build for these inputs,
+    through the planner and the table builder it runs; out_path: also write the lift file."""
+    import numpy as np
+    L = load_library()
+    L.scs_lift_plan_probe.argtypes = [C.c_char_p] * 4 + [C.c_void_p] * 5 + [C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                      C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+    enc = lambda p: os.fsencode(p) if p else None
+    err, n_sub = C.create_string_buffer(512), C.c_uint64()
+    state = dict(sub=None)
+
+    def call(h, l, rp, rr, k, cap, n_seg, hl, rl, rcap, n_hap, n_ref, names, ncap, nlen):
+        sub = state["sub"]
+        rc = L.scs_lift_plan_probe(enc(ref_fasta), enc(snp_file), enc(var_file), enc(out_path) if sub is not None else None, h, l, rp, rr, k, cap, C.byref(n_seg),
+                                   sub.ctypes.data if sub is not None else None, len(sub) if sub is not None else 0, C.byref(n_sub),
+                                   hl, rl, rcap, C.byref(n_hap), C.byref(n_ref), names, ncap, C.byref(nlen), err, 512)
+        if rc:
+            raise ScsError(rc, err.value.decode() or "scs_lift_plan_probe")
+        if sub is None:
+            state["sub"] = np.zeros(max(1, n_sub.value), np.uint64)
+    t = _lift_probe(call)
+    return t, state["sub"][:n_sub.value]
+
+
+def lift_file_probe(path):
+    """Host-only: the LiftTable a lift file holds, through the parser scs_load_lift runs.  A refused file raises ScsError (SCS_EIO)
+    whose .line is the line it was refused at."""
+    L = load_library()
+    L.scs_lift_file_probe.argtypes = [C.c_char_p] + [C.c_void_p] * 5 + [C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+    err, line = C.create_string_buffer(1024), C.c_uint64()
+
+    def call(h, l, rp, rr, k, cap, n_seg, hl, rl, rcap, n_hap, n_ref, names, ncap, nlen):
+        rc = L.scs_lift_file_probe(os.fsencode(path), h, l, rp, rr, k, cap, C.byref(n_seg), hl, rl, rcap, C.byref(n_hap), C.byref(n_ref), names, ncap, C.byref(nlen), C.byref(line), err, 1024)
+        if rc:
+            e = ScsError(rc, err.value.decode() or "scs_lift_file_probe")
+            e.line = line.value
+            raise e
+    return _lift_probe(call)
+
+
+def lift_read_probe(table, hap_lens, ref_lens, pos0, n, events=(), reverse=False, bin_width=1000):
+    """Host-only: what one read adds to the reference's bins through a lift table, through the function k_depth_lift runs.  table:
+    a LiftTable (or any object with its five arrays); pos0 = global staged index of window base 0.  Returns (bin of the `reads`
+    increment, [(bin, bases), ...] in the order made); the pseudo-bin is the number of bins.  A read that cannot be lifted raises
+    ScsError (SCS_EINVAL) whose .lift_err says why (0: not a valid alignment)."""
+    import numpy as np
+    L = load_library()
+    L.scs_lift_read_probe.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                      C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    ev = np.ascontiguousarray([v for e in events for v in e], np.int32)
+    segs = [np.ascontiguousarray(getattr(table, k), dt) for k, dt in (("hap_off", np.uint64), ("len", np.uint64), ("ref_pos", np.uint64), ("ref_rec", np.uint32), ("kind", np.uint32))]
+    hl, rl = np.ascontiguousarray(hap_lens, np.uint64), np.ascontiguousarray(ref_lens, np.uint64)
+    first, k, le = C.c_uint64(), C.c_int(), C.c_int()
+    args = (int(n), int(pos0), int(bool(reverse)), ev.ctypes.data if len(events) else None, len(events)) + tuple(x.ctypes.data for x in segs) + \
+           (len(segs[0]), hl.ctypes.data, len(hl), rl.ctypes.data, len(rl), int(bin_width), C.byref(first))
+    rc = L.scs_lift_read_probe(*args, None, None, 0, C.byref(k), C.byref(le))
+    if rc not in (SCS_OK, SCS_EOVERFLOW):
+        e = ScsError(rc, "scs_lift_read_probe: " + ("the read cannot be lifted (%d)" % le.value if le.value else "not a valid alignment"))
+        e.lift_err = le.value
+        raise e
+    bins, bases = np.zeros(max(1, k.value), np.uint64), np.zeros(max(1, k.value), np.uint32)
+    rc = L.scs_lift_read_probe(*args, bins.ctypes.data, bases.ctypes.data, k.value, C.byref(k), C.byref(le))
+    if rc:
+        raise ScsError(rc, "scs_lift_read_probe")
+    return first.value, [(int(bins[i]), int(bases[i])) for i in range(k.value)]
+
+
 def support_read_probe(pos0, n, seq, positions, events=(), reverse=False, rec_len=1 << 40):
     """Host-only: what one read shows at the listed record coordinates, through the function the site support kernel runs.  pos0, n,
     events, reverse, rec_len as for depth_read_probe; seq = the FASTQ record's bases; positions ascending and distinct.  Returns
@@ -823,6 +920,83 @@ class GenReads:
         n, b = C.c_uint64(), C.c_uint64()
         self._ck(self._L.scs_write_site_support(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n), C.byref(b)))
         return dict(sites=n.value, bytes=b.value)
+
+    # ---- lift table and depth by reference bin
+    def write_lift(self, path):
+        """The staged genome's lift table (kept by simuvars, or read by load_lift) as text: ##scssim-lift v1."""
+        self._L.scs_write_lift.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_write_lift(self._ctx, os.fsencode(path)))
+
+    def load_lift(self, path):
+        """Read the lift table `simuvars --lift` / write_lift wrote for the genome that is staged (after staging it)."""
+        self._L.scs_load_lift.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_load_lift(self._ctx, os.fsencode(path)))
+
+    def lift_info(self):
+        """(segments, reference records) of the staged genome's lift table."""
+        self._L.scs_lift_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        n, r = C.c_uint64(), C.c_uint32()
+        self._ck(self._L.scs_lift_info(self._ctx, C.byref(n), C.byref(r)))
+        return n.value, r.value
+
+    def lift_segments(self):
+        """The lift table as a LiftTable of numpy arrays, read back from the device copy (ref_lens filled in)."""
+        np = self._np
+        n, nr = self.lift_info()
+        a = [np.zeros(max(n, 1), np.uint64) for _ in range(3)] + [np.zeros(max(n, 1), np.uint32) for _ in range(2)]
+        rl = np.zeros(max(nr, 1), np.uint64)
+        self._L.scs_lift_segments.argtypes = [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p, C.c_uint32]
+        self._ck(self._L.scs_lift_segments(self._ctx, *[x.ctypes.data for x in a], n, rl.ctypes.data, nr))
+        return LiftTable(*[x[:n] for x in a], ref_lens=rl[:nr])
+
+    def lift_positions(self, rec, pos):
+        """Staged positions (record index, 0-based coordinate) -> (ref_rec, ref_pos, kind) arrays, lifted on the GPU."""
+        np = self._np
+        rec, pos = np.ascontiguousarray(rec, np.uint32), np.ascontiguousarray(pos, np.uint64)
+        n = len(rec)
+        assert len(pos) == n
+        rr, rp, k = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+        self._L.scs_lift_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._ck(self._L.scs_lift_positions(self._ctx, rec.ctypes.data, pos.ctypes.data, n, rr.ctypes.data, rp.ctypes.data, k.ctypes.data))
+        return rr[:n], rp[:n], k[:n]
+
+    def set_depth_ref(self, bin_width):
+        """Depth by bin of the ORIGINAL REFERENCE through the lift table: the following yield calls count reads and aligned bases per
+        bin of bin_width reference bases (0: off), plus one pseudo-bin for what has no reference coordinate."""
+        self._L.scs_set_depth_ref.argtypes = [C.c_void_p, C.c_uint32]
+        self._ck(self._L.scs_set_depth_ref(self._ctx, int(bin_width)))
+
+    def depth_ref_bins(self):
+        """(number of reference bins -- the pseudo-bin not counted --, bin width)."""
+        self._L.scs_depth_ref_bins.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+        n, w = C.c_uint64(), C.c_uint32()
+        self._ck(self._L.scs_depth_ref_bins(self._ctx, C.byref(n), C.byref(w)))
+        return n.value, w.value
+
+    def depth_ref(self):
+        """(reads, bases, copies, bin_off) of the last yield call: uint64 arrays of n_bins + 1 entries (the last one the pseudo-bin) and
+        the first bin of every reference record (records + 1 entries)."""
+        np = self._np
+        n, _ = self.depth_ref_bins()
+        _, nr = self.lift_info()
+        reads, bases, copies, off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(nr + 1, np.uint64)
+        self._L.scs_download_depth_ref.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        self._ck(self._L.scs_download_depth_ref(self._ctx, reads.ctypes.data, bases.ctypes.data, copies.ctypes.data, n + 1))
+        self._L.scs_depth_ref_record_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        self._ck(self._L.scs_depth_ref_record_bins(self._ctx, off.ctypes.data, off.size))
+        return reads, bases, copies, off
+
+    def write_depth_ref(self, path):
+        """The same as text: #record, start, end (BED coordinates of the reference), reads, bases, copies; last line #unlifted."""
+        self._L.scs_write_depth_ref.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_write_depth_ref(self._ctx, os.fsencode(path)))
+
+    def depth_ref_kernel_time(self):
+        """Event pairs (one per batch), milliseconds and pairs of the last yield call's k_depth_lift launches."""
+        self._L.scs_depth_ref_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(self._L.scs_depth_ref_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def site_support_kernel_time(self):
         """Event pairs (one per batch), milliseconds and pairs of the last yield call's k_support launches."""

@@ -12,6 +12,7 @@
 #include "scs_bgzf.h"
 #include "scs_truth.h"
 #include "scs_depth.h"
+#include "scs_lift.h"
 
 #include <atomic>
 #include <fcntl.h>
@@ -257,6 +258,15 @@ struct scs_ctx {
     // yield call (reads[n_bins] then bases[n_bins], zeroed on the ctx stream at the start of every call; depth_valid: a call with
     // depth on has finished) and the kernel's record table (rec_off[nr + 1] then bin_off[nr + 1])
     uint32_t depth_width = 0; uint64_t depth_bins = 0; bool depth_valid = false; DevBuf dp_cnt, dp_tab;
+    // lift table (scs_lift.cpp): the staged records as stretches of the original reference -- kept by scs_simuvars
+    // or read by scs_load_lift, on the host and (d_lift: the segments) on the device; tied to the staged genome: staging another drops it.
+    // Depth by reference bin (scs_set_depth_ref): the bin width (0: off -- no buffer below exists, no code of it runs), the bins of the
+    // reference records, the counters (reads, bases, copies: n_bins + 1 entries each; the first two zeroed on the ctx stream at the start
+    // of every yield call, copies made once per layout: dref_copies) and the kernel's tables (staged record starts, reference lengths
+    // and first bins)
+    bool have_lift = false; LiftTable lift; DevBuf d_lift;
+    uint32_t dref_width = 0; uint64_t dref_bins = 0; bool dref_valid = false, dref_copies = false; DevBuf dr_cnt, dr_tab;
+    KernelTimer tm_depth_ref{"k_depth_lift"};             // the last yield call's k_depth_lift launches (scs_depth_ref_kernel_time; not one of tm[])
     // amplicon table (scs_amplicon_places / scs_write_amplicons; scs_amplicons.cpp): the kernels' record table, a chunk's line sizes and
     // 64-bit offsets, the binary form's arrays, two text buffers (and the BGZF lane over them) with their pinned twins, the chunk's
     // totals in pinned words behind ev_am_n / ev_am_made.  Every buffer holds one chunk and is released when the call returns
@@ -373,6 +383,15 @@ void truth_check(scs_ctx* c, bool device, int writers);
 // depth track: refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the staged records' bins (SCS_EINVAL beyond DEPTH_MAX_BINS)
 void depth_check(scs_ctx* c);
 uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);
+// lift table and depth by reference bin (scs_lift.cpp): lift_install makes T the ctx's table (host and device), lift_drop forgets it
+// (every call that stages a genome); depth_ref_check refuses (SCS_EINVAL) a sharded or sliced ctx, and one without a table, at the yield call;
+// depth_ref_layout: the reference records' bins (SCS_EINVAL: no table, or beyond DEPTH_MAX_BINS); depth_ref_open: the kernel's
+// tables, this call's zeroed counters and (once per layout) the copies
+void lift_install(scs_ctx* c, LiftTable&& T);
+void lift_drop(scs_ctx* c);
+void depth_ref_check(scs_ctx* c);
+uint64_t depth_ref_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);
+void depth_ref_open(scs_ctx* c);
 // site support (scs_support.cpp): refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the call's site table, positions and zeroed counters
 void support_check(scs_ctx* c);
 void support_open(scs_ctx* c);

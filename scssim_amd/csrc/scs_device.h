@@ -105,8 +105,9 @@ struct AllocPlan {
 struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned long long go[ALLOC_SLOTS]; };
 
 // error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right,
-// 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table, 9 for the site support counters
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512 };
+// 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table, 9 for the site support counters, 10 for the
+// depth track by reference bin
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512, FLAG_LIFT = 1024 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -264,6 +265,25 @@ struct DepthArgs : PlaceArgs {
     unsigned long long* reads; unsigned long long* bases;  // the counters, one per bin each
 };
 void launch_depth(hipStream_t s, const DepthArgs& a);
+
+// ---- lift table (scs_k_lift.hip; scs_lift.h): the staged records as stretches of the original reference.
+// k_depth_lift: the depth track of a batch by REFERENCE bin -- k_depth's placement and LDS table, the bins found through the
+// segment table; bin n_bins collects what has no reference coordinate.  k_lift_copies: per reference bin the haplotype bases
+// that lift into it (the true copy number times the bin's width).  k_lift_points: staged positions -> reference coordinates
+struct LiftSeg;
+struct LiftArgs : PlaceArgs {
+    const uint64_t* rec_off; uint32_t n_rec;               // staged record starts (n_rec + 1)
+    const LiftSeg* segs; uint32_t n_seg;                   // the table
+    const uint64_t* ref_len; const uint64_t* ref_bin_off; uint32_t n_ref;   // reference lengths (n_ref) and first bins (n_ref + 1)
+    uint32_t bin_width, slots; uint64_t n_bins;
+    unsigned long long* reads; unsigned long long* bases;  // the counters, n_bins + 1 each
+};
+void launch_depth_lift(hipStream_t s, const LiftArgs& a);
+void launch_lift_copies(hipStream_t s, const LiftSeg* segs, uint32_t n_seg, const uint64_t* ref_len, const uint64_t* ref_bin_off, uint32_t n_ref, uint32_t bin_width,
+                        uint64_t n_bins, unsigned long long* copies, uint32_t* flags);   // copies: n_bins + 1, zeroed; FLAG_LIFT: a segment outside its reference record
+// bad: a word that becomes non-zero when a position lies outside its record (nothing is written for it)
+void launch_lift_points(hipStream_t s, const LiftSeg* segs, uint32_t n_seg, const uint64_t* rec_off, uint32_t n_rec, const uint32_t* rec, const uint64_t* pos, uint64_t n,
+                        uint32_t* ref_rec, uint64_t* ref_pos, uint32_t* kind, uint32_t* bad);
 
 // ---- amplicon table (scs_k_amplicons.hip; scs_amplicon_places / scs_write_amplicons): the full amplicons [first, first + n) of
 // the list, each resolved to its record, interval, strand and edits (scs_amp.h).  A chunk at a time: nothing is sized by the job

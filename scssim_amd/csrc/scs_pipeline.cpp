@@ -49,6 +49,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_DEPTH) m += " depth track (a read with more than 32 indel events, pair flags that are not a strand, or a read placed outside its record)";
         if (f & FLAG_AMP) m += " amplicon table (a lineage that does not fit its parents, view flags that are not a strand, an amplicon outside its record, or a line the two passes size differently)";
         if (f & FLAG_SITE) m += " artefact table (an amplicon that cannot be placed, a slab whose entries differ from their count, site counts that contradict each other, or a line the two passes size differently)";
+        if (f & FLAG_LIFT) m += " depth by reference bin (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand)";
         if (f & FLAG_SUPPORT) m += " site support (a read placed outside its record, pair flags that are not a strand, a read with more than 32 indel events, a FASTQ record that is not where the offsets say, or sites that are not in order)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
@@ -89,7 +90,7 @@ int scs_create(const scs_config* cfg, scs_ctx** out) {
         if (cfg->stream) c->stream.adopt((hipStream_t)cfg->stream); else c->stream.ensure(hipStreamNonBlocking);
         c->key = RngKey{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32)};
         for (KernelTimer& t : c->tm) t.gate = &c->timing_gate;
-        c->tm_support.gate = &c->timing_gate;
+        c->tm_support.gate = &c->timing_gate; c->tm_depth_ref.gate = &c->timing_gate;
         c->flags.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->flags.p, 0, 256, c->stream));
         c->dsums.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->dsums.p, 0, 256, c->stream));
         c->d_tot.reserve(256, c->stream);
@@ -190,6 +191,9 @@ int scs_simuvars(scs_ctx* c, const char* ref_fasta, const char* snp_file, const 
         c->recs.resize(P.rec_names.size());
         for (size_t i = 0; i < P.rec_names.size(); ++i) encode_record(P.rec_names[i].c_str(), nullptr, 0, c->recs[i]);
         stage_genome(c, c->genome.p, P.rec_lens.data());                                 // encode + bit index in place: ready for scs_create_frags
+        LiftTable T; std::string why;                                                    // the plan's map to the reference stays with the genome it built
+        if (!lift_from_plan(chroms, P, T, why)) throw ScsError(SCS_EDEVICE, why);
+        lift_install(c, std::move(T));
     });
 }
 int scs_create_frags(scs_ctx* c) { return guarded(c, [&] { double t = now_s(); do_create_frags(c); c->st.t_stage[1] = now_s() - t; }); }

@@ -167,12 +167,12 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, depth_ref = c->dref_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, truth_sum = 0, bi = 0;            // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
     FdGuard truth_fd;                                                              // (closed after the pipe's writers have ended: declared first)
-    PipeGuard guard{nullptr}; TruthArgs ta{}; DepthArgs da{}; SupportArgs sa{};
+    PipeGuard guard{nullptr}; TruthArgs ta{}; DepthArgs da{}; LiftArgs la{}; SupportArgs sa{};
     // shard index: the pair index at which each list segment starts (pair_off at the segment's first amplicon); the byte offset of
     // that record = the bytes of the batches before its batch (known once every batch is made) + its offset inside the batch
     std::vector<uint64_t> bpair, bb[2]; std::vector<SegAt> seg_at;
@@ -222,6 +222,17 @@ struct Yield {               // the state of one do_yield call
         da.reads = c->dp_cnt.as<unsigned long long>(); da.bases = da.reads + nb;
         da.paired = paired; da.tb = c->dtb; da.key = c->key; da.slot = slot; da.flags = c->flags.as<uint32_t>();
     }
+    void depth_ref_open() {
+        // the kernel's tables (staged record starts, the reference's lengths and first bins), this call's counters zeroed on the ctx
+        // stream, the copies where the layout is new (scs_lift.cpp)
+        static const uint32_t slots = seam_env("SCS_TEST_LIFT_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_LIFT_SLOTS")) : DEPTH_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
+        scs::depth_ref_open(c);
+        const uint32_t nr = (uint32_t)c->recs.size(), nf = (uint32_t)c->lift.ref_lens.size(); const uint64_t nb = c->dref_bins;
+        la.rec_off = c->dr_tab.as<uint64_t>(); la.n_rec = nr; la.ref_len = la.rec_off + nr + 1; la.ref_bin_off = la.ref_len + nf; la.n_ref = nf;
+        la.segs = c->d_lift.as<LiftSeg>(); la.n_seg = (uint32_t)c->lift.segs.size(); la.bin_width = c->dref_width; la.slots = slots; la.n_bins = nb;
+        la.reads = c->dr_cnt.as<unsigned long long>(); la.bases = la.reads + nb + 1;
+        la.paired = paired; la.tb = c->dtb; la.key = c->key; la.slot = slot; la.flags = c->flags.as<uint32_t>();
+    }
     void support_open() {
         // the call's site table, its distinct positions and this call's counters, zeroed on the ctx stream (scs_support.cpp)
         static const uint32_t slots = seam_env("SCS_TEST_SUPPORT_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_SUPPORT_SLOTS")) : SUPPORT_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
@@ -241,6 +252,7 @@ struct Yield {               // the state of one do_yield call
         }
         if (truth) truth_open();
         if (depth) depth_open();
+        if (depth_ref) depth_ref_open();
         if (support) support_open();
         if (to_sink) {
             if (!c->pipe) c->pipe.reset(new SinkPipe);
@@ -393,6 +405,13 @@ struct Yield {               // the state of one do_yield call
         launch_depth(s, da);
         c->tm[TM_DEPTH].end(s); c->tm[TM_DEPTH].add_units(b.np);
     }
+    void depth_ref_batch(const Batch& b) {
+        // the batch's reads into the reference's bins through the lift table, from what depth_batch reads.  Before ev_free, as truth_batch
+        la.pairs = b.pr; la.np = b.np; la.ev_hdr = b.B->ev_hdr; la.ev_dat = b.B->ev_dat;
+        c->tm_depth_ref.begin(s);
+        launch_depth_lift(s, la);
+        c->tm_depth_ref.end(s); c->tm_depth_ref.add_units(b.np);
+    }
     void support_batch(const Batch& b) {
         // the batch's reads into the site counters, from its pair records, indel events and FASTQ text.  Before ev_free, as truth_batch,
         // and before the sink takes the text
@@ -451,8 +470,8 @@ struct Yield {               // the state of one do_yield call
         mail_wait(c); flags_eval(c);
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];
-        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect(); c->tm[TM_DEPTH].collect(); c->tm_support.collect();
-        c->depth_valid = depth; c->support_valid = support;
+        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect(); c->tm[TM_DEPTH].collect(); c->tm_support.collect(); c->tm_depth_ref.collect();
+        c->depth_valid = depth; c->support_valid = support; c->dref_valid = depth_ref;
         c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
         for (int m = 0; m < 2; ++m) { c->st.fastq_bytes[m] = tot[m]; c->st.sink_bytes[m] = to_sink ? sunk[m] : 0; }
         // 1526 B per created amplicon + per pair (insert size + FASTQ bytes of both records)
@@ -470,9 +489,10 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     Yield y{c, tg}; const hipStream_t s = y.s; const uint64_t P = y.P;
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
-    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset(); c->tm[TM_DEPTH].reset(); c->tm_support.reset();
-    c->depth_valid = false; c->support_valid = false;
+    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset(); c->tm[TM_DEPTH].reset(); c->tm_support.reset(); c->tm_depth_ref.reset();
+    c->depth_valid = false; c->support_valid = false; c->dref_valid = false;
     if (c->depth_width) (void)depth_ctx_layout(c, nullptr);   // more than 2^27 bins: refused before any GPU work
+    if (c->dref_width) { depth_ref_check(c); (void)depth_ref_layout(c, nullptr); }   // no lift table, or more than 2^27 bins: the same
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
     // (Profile.cpp:1482-1485 -> Config.cpp:85-93) -- after the amplification, with the output files opened and empty.  Same here, as an error code.
@@ -502,6 +522,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         y.base_pass(b);
         if (y.truth) y.truth_batch(b);
         if (y.depth) y.depth_batch(b);
+        if (y.depth_ref) y.depth_ref_batch(b);
         if (y.support) y.support_batch(b);
         if (y.ps != s) { HIP_OK(hipEventRecord(c->ev_free[b.k], s)); y.free_rec[b.k] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
@@ -521,6 +542,7 @@ void truth_check(scs_ctx* c, bool device, int writers) {
 }
 
 void depth_check(scs_ctx* c) {
+    depth_ref_check(c);                                                            // (depth by reference bin: refused at the same place)
     if (!c->depth_width) return;
     if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, "depth track (scs_set_depth): not available for a sharded job (shard_count > 1); turn it off with scs_set_depth(ctx, 0)");
 }
