@@ -13,6 +13,7 @@
 #include "scs_truth.h"
 #include "scs_depth.h"
 #include "scs_lift.h"
+#include "scs_outfile.h"
 
 #include <atomic>
 #include <fcntl.h>
@@ -35,8 +36,6 @@
 #include <vector>
 
 namespace scs {
-
-struct ScsError : std::runtime_error { int code; ScsError(int c, const std::string& m) : std::runtime_error(m), code(c) {} };
 
 #define HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     throw ScsError(SCS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
@@ -146,6 +145,9 @@ template <class T> struct Pinned {                                              
     void release() { if (p) { (void)hipHostFree(p); census_add(census().pinned_bytes, -(uint64_t)bytes); } p = nullptr; bytes = 0; }
     operator T*() const { return p; }
 };
+// BGZF made on the device over one byte stream (scs_bgzf.hip; bgzf_in_place, scs_textout.h): the blocks' plans / sizes / offsets and two
+// output buffers, for the users that make one batch's blocks while the last one's cross to the host
+struct BgzfLane { DevBuf plan, sizes, offs, out[2]; };
 static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "DevBuf owns its memory");
 static_assert(!std::is_copy_constructible<Stream>::value && !std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Pinned<char>>::value, "the handles own what they hold");
 
@@ -241,10 +243,10 @@ struct scs_ctx {
     DevBuf slot_b, slot_q, lens, ev_hdr, ev_dat, sizes[2], off[2], out[2][2], rl_cls, rl_pos, rl_lists, d_bounds;   // sizes / off: per mate; out[slot][mate]: the FASTQ text (sink mode: two slots)
     Stream errs_stream; Event ev_att, ev_errs; bool errs_pending = false;   // k_errs<semi->full> of a cycle runs beside the fragment pass that follows it
     DevBuf slots_fr, slot_tmpl_fr;                        // the fragment passes' own slot arrays (the semi pass's are still being read then)
-    // BGZF made on the device (scs_bgzf.hip): per byte stream (z[0], z[1]: the mates' FASTQ text; z[2]: the truth BAM's records) the blocks'
-    // plans / sizes / offsets and two output buffers; the CRC tables; the blocks' totals per batch reach the host through a small pinned
-    // array (h_z[slot][stream]) behind the slot's event, the FASTQ blocks' one batch late (see do_yield)
-    struct BgzfLane { DevBuf plan, sizes, offs, out[2]; } z[3]; DevBuf z_crc; Pinned<uint32_t> h_z; Event ev_z[2];
+    // BGZF made on the device (scs_bgzf.hip): a lane per byte stream (z[0], z[1]: the mates' FASTQ text; z[2]: the truth BAM's records);
+    // the CRC tables; the blocks' totals per batch reach the host through a small pinned array (h_z[slot][stream]) behind the slot's
+    // event, the FASTQ blocks' one batch late (see do_yield)
+    BgzfLane z[3]; DevBuf z_crc; Pinned<uint32_t> h_z; Event ev_z[2];
     bool want_cks = false; DevBuf d_cks; std::vector<uint64_t> cks;   // scs_set_batch_checksums: per batch and mate, computed where the text lies in HBM
     // truth SAM (scs_set_truth_sam): the path (empty: off), per batch the pairs' SAM sizes and 64-bit offsets, two output buffers (the
     // batch's text crosses PCIe on the copy stream while the next batch is made), the record table the kernels name records from,
@@ -267,10 +269,8 @@ struct scs_ctx {
     bool have_lift = false; LiftTable lift; DevBuf d_lift;
     uint32_t dref_width = 0; uint64_t dref_bins = 0; bool dref_valid = false, dref_copies = false; DevBuf dr_cnt, dr_tab;
     KernelTimer tm_depth_ref{"k_depth_lift"};             // the last yield call's k_depth_lift launches (scs_depth_ref_kernel_time; not one of tm[])
-    // amplicon table (scs_amplicon_places / scs_write_amplicons; scs_amplicons.cpp): the kernels' record table, a chunk's line sizes and
-    // 64-bit offsets, the binary form's arrays, two text buffers (and the BGZF lane over them) with their pinned twins, the chunk's
-    // totals in pinned words behind ev_am_n / ev_am_made.  Every buffer holds one chunk and is released when the call returns
-    DevBuf am_recs, am_sizes, am_offs, am_scan, am_bin, am_out[2]; BgzfLane am_z; Pinned<char> h_am[2]; Pinned<uint64_t> h_am_n; Event ev_am_n, ev_am_made[2], ev_am_d2h[2];
+    // amplicon table (scs_amplicon_places / scs_write_amplicons; scs_amplicons.cpp): every buffer, stream and event of a call belongs to
+    // its AmpJob and goes with it; nothing of the call stays here but the kernels' times
     KernelTimer tm_amp{"k_amplicons"};                    // the last scs_write_amplicons call's kernels (scs_amplicon_kernel_time; not one of tm[])
     // site support (scs_set_site_support; scs_support.cpp): off -- no buffer below exists, no code of it runs.  The
     // last yield call's site table (the artefact table's sites at support_min_reads, packed in order), every site's position index, the

@@ -2,7 +2,7 @@
 // scs_lift_info, scs_lift_segments, scs_lift_positions, scs_set_depth_ref ...).  The table itself -- built from
 // the simuvars plan, written, parsed -- is scs_lift.h's; here it becomes the ctx's (host vector + device copy), the ctx's entry
 // points run over it, and the host-only probes expose what they run.  The per-batch kernel is launched from scs_reads.cpp.
-#include "scs_ctx.h"
+#include "scs_textout.h"
 #include <cerrno>
 
 namespace scs {
@@ -38,8 +38,7 @@ void depth_ref_open(scs_ctx* c) {
     const hipStream_t s = c->stream;
     const size_t nr = c->recs.size(), nf = c->lift.ref_lens.size(); std::vector<uint64_t> boff;
     const uint64_t nb = c->dref_bins = depth_ref_layout(c, &boff);
-    std::vector<uint64_t> tab(nr + 1 + nf + nf + 1, 0);
-    for (size_t r = 0; r < nr; ++r) { tab[r] = c->rec_off[r]; tab[r + 1] = c->rec_off[r] + c->rec_len[r]; }
+    std::vector<uint64_t> tab = record_starts(c); tab.resize(nr + 1 + nf + nf + 1, 0);
     std::copy(c->lift.ref_lens.begin(), c->lift.ref_lens.end(), tab.begin() + (long)(nr + 1));
     std::copy(boff.begin(), boff.end(), tab.begin() + (long)(nr + 1 + nf));
     upload(c->dr_tab, tab, s);
@@ -136,8 +135,7 @@ int scs_lift_positions(scs_ctx* c, const uint32_t* rec, const uint64_t* pos, uin
         if (!n) return;
         const hipStream_t s = c->stream; const size_t nr = c->recs.size();
         DevBuf d_in, d_out, d_tab;                                                     // the call's buffers: they go with it
-        std::vector<uint64_t> roff(nr + 1, 0);
-        for (size_t r = 0; r < nr; ++r) { roff[r] = c->rec_off[r]; roff[r + 1] = c->rec_off[r] + c->rec_len[r]; }
+        const std::vector<uint64_t> roff = record_starts(c);
         upload(d_tab, roff, s, 2);                                                     // (+ the `bad` word behind the record starts)
         uint32_t* bad = (uint32_t*)(d_tab.as<uint64_t>() + nr + 1);
         HIP_OK(hipMemsetAsync(bad, 0, 8, s));
@@ -213,12 +211,7 @@ int scs_write_depth_ref(scs_ctx* c, const char* path) {
         if (fclose(o) != 0 || !okw || b != nb) throw ScsError(SCS_EIO, std::string("scs_write_depth_ref: writing ") + path + " failed");
     });
 }
-int scs_depth_ref_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) {
-    if (!c) return SCS_EINVAL;
-    const KernelTimer& t = c->tm_depth_ref;
-    if (launches) *launches = t.launches; if (ms) *ms = t.ms; if (units) *units = t.units;
-    return SCS_OK;
-}
+int scs_depth_ref_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) { return kernel_time_of(c, &scs_ctx::tm_depth_ref, launches, ms, units); }
 
 // ---- host-only seams (no GPU, no ctx)
 // plan -> table -> optionally the file; subst_pos: the global haplotype indices the plan substitutes (SNP / SNV alleles)

@@ -1,6 +1,5 @@
 // scs_reads.cpp -- Malbac::setReadCounts and Malbac::yieldReads on the device
 #include "scs_sink.h"
-#include <cerrno>
 
 namespace scs {
 // ---------------------------------------------------------------- a8 + a9: Malbac::setReadCounts (Malbac.cpp:370-408) on the device
@@ -161,7 +160,6 @@ struct Ship { char* p[3]; uint64_t n[3]; int dsl; uint32_t region; };   // [0], 
 // one iteration of do_yield's loop: which pairs, which buffer set (k) and output slot (dsl), what the pre-pass mailed, where its text lies
 struct Batch { uint64_t it, p0; uint32_t bidx, np; int k, dsl; const PairRec* pr; const BatchSet* B; BatchCounts n; char* out[2]; char* t_text; uint64_t t_n; };
 struct SegAt { size_t seg; uint32_t b; uint64_t o[2]; };
-struct FdGuard { int fd = -1; ~FdGuard() { if (fd >= 0) ::close(fd); } };
 struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 
 struct Yield {               // the state of one do_yield call
@@ -169,52 +167,39 @@ struct Yield {               // the state of one do_yield call
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
     const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, depth_ref = c->dref_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
-    uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, truth_sum = 0, bi = 0;            // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
+    uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, bi = 0;                           // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
-    FdGuard truth_fd;                                                              // (closed after the pipe's writers have ended: declared first)
-    PipeGuard guard{nullptr}; TruthArgs ta{}; DepthArgs da{}; LiftArgs la{}; SupportArgs sa{};
+    OutFile truth_fd;                                                              // (closed after the pipe's writers have ended: declared first); its total: the header, every batch's bytes, the end-of-file block
+    PipeGuard guard{nullptr}; RecTable rt; TruthArgs ta{}; DepthArgs da{}; LiftArgs la{}; SupportArgs sa{};
     // shard index: the pair index at which each list segment starts (pair_off at the segment's first amplicon); the byte offset of
     // that record = the bytes of the batches before its batch (known once every batch is made) + its offset inside the batch
     std::vector<uint64_t> bpair, bb[2]; std::vector<SegAt> seg_at;
     void truth_open() {
         // the header first, then the batches' records from the pipe's writer; the kernels' record table: starts, name offsets, names
-        truth_fd.fd = ::open(c->truth_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
-        if (truth_fd.fd < 0) throw ScsError(SCS_EIO, tname + ": can not open " + c->truth_path + ": " + strerror(errno));
+        truth_fd.open(tname, c->truth_path, bam);
         std::string hd = "@HD\tVN:1.6\tSO:unsorted\n"; const uint32_t nr = (uint32_t)c->recs.size();
-        std::vector<uint64_t> roff(nr + 1, 0); std::vector<uint32_t> noff(nr + 1, 0); std::string names;
-        for (uint32_t r = 0; r < nr; ++r) {
-            hd += "@SQ\tSN:" + c->recs[r].name + "\tLN:" + std::to_string(c->rec_len[r]) + "\n";
-            roff[r] = c->rec_off[r]; roff[r + 1] = c->rec_off[r] + c->rec_len[r];
-            names += c->recs[r].name; noff[r + 1] = (uint32_t)names.size();
-        }
+        for (uint32_t r = 0; r < nr; ++r) hd += "@SQ\tSN:" + c->recs[r].name + "\tLN:" + std::to_string(c->rec_len[r]) + "\n";
         hd += "@PG\tID:scssim\tPN:scssim\n";
-        if (bam) {                                                                 // magic, l_text, the SAM's header text, n_ref, per record l_name / name / l_ref: BGZF made on the host
+        if (bam) {                                                                 // magic, l_text, the SAM's header text, n_ref, per record l_name / name / l_ref: BGZF made on the host (OutFile::header)
             std::string bh = "BAM\1";
             auto le32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) bh.push_back((char)(v >> (8 * k))); };
             le32((uint32_t)hd.size()); bh += hd; le32(nr);
             for (uint32_t r = 0; r < nr; ++r) { le32((uint32_t)c->recs[r].name.size() + 1u); bh += c->recs[r].name; bh.push_back('\0'); le32((uint32_t)c->rec_len[r]); }
-            std::vector<uint8_t> z; bgzf_compress_host((const uint8_t*)bh.data(), bh.size(), BGZF_LDS_OUT, z);
-            hd.assign((const char*)z.data(), z.size());
+            hd.swap(bh);
         }
-        if (!SinkPipe::write_all(truth_fd.fd, hd.data(), hd.size())) throw ScsError(SCS_EIO, tname + ": writing " + c->truth_path + " failed");
-        truth_sum = hd.size();
-        const size_t o_name = (size_t)(nr + 1) * 8, o_text = o_name + (size_t)(nr + 1) * 4; std::vector<uint8_t> blob(o_text + names.size() + 16, 0);
-        memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nr + 1) * 4); memcpy(blob.data() + o_text, names.data(), names.size());
-        upload(c->t_recs, blob, s);
+        truth_fd.header(hd);
         c->t_sizes.reserve((plan.batch + 1) * 4, s); c->t_offs.reserve((plan.batch + 1) * 8, s); c->t_scan.reserve(scan_temp_bytes(plan.batch), s);
         c->h_t.reserve(64, hipHostMallocDefault); c->ev_t.ensure(hipEventDisableTiming | hipEventBlockingSync);
-        HIP_OK(hipStreamSynchronize(s));                                           // (the host blob goes)
-        const uint8_t* tb = c->t_recs.as<uint8_t>();
-        ta.g = c->genome.as<uint8_t>(); ta.rec_off = (const uint64_t*)tb; ta.name_off = (const uint32_t*)(tb + o_name); ta.names = (const char*)(tb + o_text); ta.n_rec = nr;
+        rt.make(c, s, &c->t_recs);                                                 // (in the ctx's buffer: it stays allocated between yield calls)
+        ta.g = c->genome.as<uint8_t>(); ta.rec_off = rt.rec_off; ta.name_off = rt.name_off; ta.names = rt.names; ta.n_rec = nr;
         ta.paired = paired; ta.tb = c->dtb; ta.key = c->key; ta.slot = slot; ta.flags = c->flags.as<uint32_t>();
     }
     void depth_open() {
         // the kernel's record table (record starts, first bins) and this call's counters, zeroed on the ctx stream
         static const uint32_t slots = seam_env("SCS_TEST_DEPTH_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_DEPTH_SLOTS")) : DEPTH_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
-        const uint32_t nr = (uint32_t)c->recs.size(); std::vector<uint64_t> tab(2 * ((size_t)nr + 1), 0), boff;
+        const uint32_t nr = (uint32_t)c->recs.size(); std::vector<uint64_t> tab = record_starts(c), boff;
         const uint64_t nb = c->depth_bins = depth_ctx_layout(c, &boff);
-        for (uint32_t r = 0; r < nr; ++r) { tab[r] = c->rec_off[r]; tab[r + 1] = c->rec_off[r] + c->rec_len[r]; }
-        std::copy(boff.begin(), boff.end(), tab.begin() + nr + 1);
+        tab.insert(tab.end(), boff.begin(), boff.end());
         upload(c->dp_tab, tab, s);
         c->dp_cnt.reserve(std::max<size_t>((size_t)nb * 16, 16), s); HIP_OK(hipMemsetAsync(c->dp_cnt.p, 0, std::max<size_t>((size_t)nb * 16, 16), s));
         HIP_OK(hipStreamSynchronize(s));                                           // (the host table goes)
@@ -260,9 +245,7 @@ struct Yield {               // the state of one do_yield call
             c->pipe->truth_fd = truth_fd.fd; c->pipe->start(tg.sink, paired != 0, c->cfg.device); guard.p = c->pipe.get();
         }
         if (bgzf || bam) { c->h_z.reserve(64, hipHostMallocDefault); memset(c->h_z, 0, 64); for (int k = 0; k < 2; ++k) c->ev_z[k].ensure(hipEventDisableTiming | hipEventBlockingSync); }
-        if ((bgzf || bam) && !c->z_crc.p) {                                        // the CRC tables of the BGZF kernels (FASTQ blocks and the truth BAM's)
-            std::vector<uint32_t> tabs(512); bgzf_host_tables(tabs.data(), tabs.data() + 256); upload(c->z_crc, tabs, s); HIP_OK(hipStreamSynchronize(s));
-        }
+        if (bgzf || bam) bgzf_crc_tables(c->z_crc, s);                             // (FASTQ blocks and the truth BAM's)
         // Per batch a PRE-PASS (indel events -> record sizes -> offsets, class lists; k_indels + scans) must finish before the host
         // can launch the base pass (it needs the batch's byte counts and class counts).  The pre-pass of batch i+1 is therefore
         // queued BEFORE the base pass of batch i, into a second set of buffers: while the host waits for its mail the GPU
@@ -358,17 +341,12 @@ struct Yield {               // the state of one do_yield call
         c->tm[TM_READS].end(s); c->tm[TM_READS].add_units(b.np);
         if (c->want_cks && !tg.device) for (int m = 0; m < 2; ++m) launch_text_checksum(s, b.out[m], m && !paired ? 0 : b.n.bytes[m], c->d_cks.as<unsigned long long>() + 2 * (size_t)b.bidx + m);
     }
-    // a byte stream becomes BGZF blocks where it lies: plan (code lengths, exact block sizes), prefix sum, emit at the final offsets.  The
-    // blocks' total is only known on the device: it travels to the pinned word h_z[dsl][lane].  Returns where the blocks lie
+    // a byte stream becomes BGZF blocks where it lies (scs_textout.h), in the lane's output of slot dsl; the blocks' total travels to the
+    // pinned word h_z[dsl][lane].  Returns where the blocks lie
     char* bgzf_in_place(int lane, const char* text, uint64_t n, int dsl, const char* too_large) {
-        if (bgzf_bound(n) > 0xFFFFFFF0ull) throw ScsError(SCS_EOVERFLOW, too_large);
-        scs_ctx::BgzfLane& z = c->z[lane]; DevBuf& zo = z.out[dsl]; const uint32_t nblk = bgzf_blocks(n); const uint64_t zb = bgzf_bound(n);
-        z.plan.reserve(std::max<size_t>((size_t)nblk * BGZF_PLAN_BYTES, 16), s); z.sizes.reserve(((size_t)nblk + 2) * 4, s); z.offs.reserve(((size_t)nblk + 2) * 4, s);
+        DevBuf& zo = c->z[lane].out[dsl]; const uint64_t zb = bgzf_bound(n);
         reserve_slot(&zo, 1, &zb, &zb, dsl, false);
-        launch_bgzf_plan(s, text, n, z.plan.as<uint8_t>(), z.sizes.as<uint32_t>());
-        exclusive_scan_u32(s, z.sizes.as<uint32_t>(), z.offs.as<uint32_t>(), nblk, nullptr, 0);   // (n <= 256 k: the one-workgroup scan, no scratch)
-        launch_bgzf_emit(s, text, n, z.plan.as<uint8_t>(), z.sizes.as<uint32_t>(), z.offs.as<uint32_t>(), c->z_crc.as<uint32_t>(), c->z_crc.as<uint32_t>() + 256, zo.as<char>(), 0);
-        HIP_OK(hipMemcpyAsync(c->h_z + (dsl * 3 + lane), z.offs.as<uint32_t>() + nblk, 4, hipMemcpyDeviceToHost, s));
+        scs::bgzf_in_place(s, c->z[lane], c->z_crc, text, n, zo.as<char>(), c->h_z + (dsl * 3 + lane), nullptr, 0, too_large);   // (at most 256 k blocks: the one-workgroup scan, no scratch)
         return zo.as<char>();
     }
     void truth_batch(Batch& b) {
@@ -389,7 +367,7 @@ struct Yield {               // the state of one do_yield call
         c->tm[TM_TRUTH].begin(s);
         if (!bam) {
             launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(fq_bytes, np), to.as<char>());
-            b.t_text = to.as<char>(); b.t_n = t_n; truth_sum += t_n;
+            b.t_text = to.as<char>(); b.t_n = t_n; truth_fd.total += t_n;
         } else if (t_n) {
             // the batch's records, then BGZF over them where they lie (the FASTQ blocks' kernels); ship reads n[2] from h_z[dsl][2], behind ev_z
             launch_truth_bam_emit(s, ta, c->t_offs.as<uint64_t>(), truth_bam_pairs_per_block(fq_bytes, np), bam_lds, to.as<char>());
@@ -423,7 +401,7 @@ struct Yield {               // the state of one do_yield call
     void ship(Ship sh) {                                                           // D2H on the copy stream into a free pinned slot, then to the region's writer
         if (bgzf || (bam && sh.p[2])) HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl]));   // the blocks' totals have arrived
         if (bgzf) { sh.n[0] = c->h_z[sh.dsl * 3]; sh.n[1] = c->h_z[sh.dsl * 3 + 1]; }
-        if (bam && sh.p[2]) { sh.n[2] = c->h_z[sh.dsl * 3 + 2]; truth_sum += sh.n[2]; }
+        if (bam && sh.p[2]) { sh.n[2] = c->h_z[sh.dsl * 3 + 2]; truth_fd.total += sh.n[2]; }
         const int hs = c->pipe->acquire(sh.n[0], sh.n[1], sh.n[2]);                     // (a pinned slot no writer holds: the host waits here when the sink is the slower side)
         if (hs < 0) throw ScsError(SCS_EIO, "sink aborted");
         SinkPipe::Slot& H = c->pipe->slots[(size_t)hs];
@@ -461,12 +439,7 @@ struct Yield {               // the state of one do_yield call
         { Mail m; m.add(c->flags.p, 4, 30); m.add(c->dsums.as<unsigned long long>() + DS_HOLES, 8, 2); mail_post(c, m, true); }   // flags + hole count land before the final synchronize: no second round trip
         HIP_OK(hipStreamSynchronize(s));
         if (to_sink) { HIP_OK(hipStreamSynchronize(c->copy_stream)); guard.p = nullptr; const bool ok = c->pipe->finish(); c->pipe->truth_fd = -1; if (!ok) throw ScsError(SCS_EIO, truth ? "sink aborted (or the " + tname + " could not be written)" : std::string("sink aborted")); }
-        if (bam) {                                                                 // the BGZF end-of-file block (SAM specification, section 4.1.2)
-            static const unsigned char eof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            if (!SinkPipe::write_all(truth_fd.fd, (const char*)eof, 28)) throw ScsError(SCS_EIO, "truth BAM: writing " + c->truth_path + " failed");
-            truth_sum += 28;
-        }
-        if (truth) { const int fd = truth_fd.fd; truth_fd.fd = -1; if (::close(fd) != 0) throw ScsError(SCS_EIO, tname + ": closing " + c->truth_path + " failed"); c->truth_bytes = truth_sum; }
+        if (truth) { truth_fd.finish("closing"); c->truth_bytes = truth_fd.total; }   // (BAM: the end-of-file block first)
         mail_wait(c); flags_eval(c);
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];

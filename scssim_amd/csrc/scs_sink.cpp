@@ -1,6 +1,5 @@
 // scs_sink.cpp -- the FASTQ sink (SeqWriter's replacement): where its host work runs, and the pipeline of pinned slots and writer threads
 #include "scs_sink.h"
-#include <cerrno>
 
 namespace scs {
 // FASTQ sink pipeline (replaces the mutexed ofstream of lib/seqwriter/SeqWriter.cpp:41-54).  A batch's text is
@@ -41,10 +40,6 @@ struct NumaScope {
     }
     ~NumaScope() { if (on) (void)pthread_setaffinity_np(pthread_self(), sizeof old, &old); }
 };
-bool SinkPipe::write_all(int fd, const char* p, size_t n) {
-    while (n) { const ssize_t w = ::write(fd, p, n); if (w < 0 && errno == EINTR) continue; if (w <= 0) return false; p += w; n -= (size_t)w; }
-    return true;
-}
 void SinkPipe::start(BatchSink* f, bool pe, int dev) {
     sink = f; paired = pe; device = dev; done = failed = false;
     local_cpus = gpu_local_cpus(dev);
@@ -63,7 +58,7 @@ void SinkPipe::start(BatchSink* f, bool pe, int dev) {
             Slot& sl = slots[(size_t)j.slot];
             bool bad = hipEventSynchronize(sl.ev) != hipSuccess;
             if (!bad && !failed) bad = sink->put(j.region, sl.h[0], j.n1, paired ? sl.h[1] : nullptr, j.n2) != 0;
-            if (!bad && !failed && j.n3) bad = !write_all(truth_fd, sl.h[2], j.n3);
+            if (!bad && !failed && j.n3) bad = !write_all(truth_fd, sl.h[2], j.n3);   // (scs_outfile.h)
             { std::lock_guard<std::mutex> lk(mu); sl.busy = false; if (bad) failed = true; }
             cv.notify_all();
         }

@@ -1,6 +1,6 @@
 // scs_sink.h -- the FASTQ sink pipeline (scs_sink.cpp): pinned slots, one writer thread per region of the job's records
 #pragma once
-#include "scs_ctx.h"
+#include "scs_textout.h"
 namespace scs {
 struct SinkPipe {
     std::vector<int> local_cpus;                                                   // of the device's NUMA node (gpu_local_cpus)
@@ -11,7 +11,6 @@ struct SinkPipe {
     std::mutex mu; std::condition_variable cv; bool done = false, failed = false;
     BatchSink* sink = nullptr; bool paired = true; int device = 0;
     int truth_fd = -1;                                                             // the truth SAM / BAM (one writer: batch order), or -1
-    static bool write_all(int fd, const char* p, size_t n);
     void start(BatchSink* f, bool pe, int dev);
     // a free pinned slot with room for the batch (blocks while every slot is with a writer); -1: the sink failed
     int acquire(size_t need1, size_t need2, size_t need3 = 0);

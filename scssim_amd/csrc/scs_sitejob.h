@@ -2,9 +2,8 @@
 // which is the same table with the reads' counters: one call's pass over the amplicons slab by slab (SiteJob) and what turns a
 // run of sites into bytes of a file (SiteOut).  Every buffer, stream and event belongs to the struct that holds it and goes with it.
 #pragma once
-#include "scs_ctx.h"
+#include "scs_textout.h"
 #include "scs_site.h"
-#include <cerrno>
 
 namespace scs {
 
@@ -19,36 +18,12 @@ inline void site_check(scs_ctx* c, const char* fn) {              // (amp_check'
     if (!c->allocated) throw ScsError(SCS_EINVAL, std::string(fn) + ": call scs_allocate_reads first (the table states every site's read support)");
 }
 
-struct SiteFd {
-    int fd = -1; ~SiteFd() { if (fd >= 0) ::close(fd); }
-    bool write_all(const char* p, size_t n) {
-        while (n) { const ssize_t w = ::write(fd, p, n); if (w < 0) { if (errno == EINTR) continue; return false; } p += w; n -= (size_t)w; }
-        return true;
-    }
-};
-
-// the kernels' record table on the device: record starts (nr + 1), name offsets (nr + 1), names -- the truth passes' table
-struct RecTable {
-    DevBuf tab; const uint64_t* rec_off = nullptr; const uint32_t* name_off = nullptr; const char* names = nullptr; uint32_t n_rec = 0; uint64_t bases = 0;
-    void make(scs_ctx* c, hipStream_t s) {
-        const uint32_t nr = (uint32_t)c->recs.size();
-        std::vector<uint64_t> roff(nr + 1, 0); std::vector<uint32_t> noff(nr + 1, 0); std::string text;
-        for (uint32_t r = 0; r < nr; ++r) { roff[r] = c->rec_off[r]; roff[r + 1] = c->rec_off[r] + c->rec_len[r]; text += c->recs[r].name; noff[r + 1] = (uint32_t)text.size(); }
-        bases = roff[nr];
-        const size_t o_name = (size_t)(nr + 1) * 8, o_text = o_name + (size_t)(nr + 1) * 4; std::vector<uint8_t> blob(o_text + text.size() + 16, 0);
-        memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nr + 1) * 4); memcpy(blob.data() + o_text, text.data(), text.size());
-        upload(tab, blob, s); HIP_OK(hipStreamSynchronize(s));                        // (the host blob goes)
-        const uint8_t* tb = tab.as<uint8_t>();
-        rec_off = (const uint64_t*)tb; name_off = (const uint32_t*)(tb + o_name); names = (const char*)(tb + o_text); n_rec = nr;
-    }
-};
-
 // A run of sites becomes bytes of the file: the emit pass over their sized lines (and BGZF over the text where it lies), then the
 // bytes travel in PIECES over the copy stream into two pinned blocks, piece p + 1 on its way while the host writes piece p to the
 // file.  The pinned blocks hold a piece, the device buffers a run's text: nothing holds the job's
 struct SiteOut {
     uint32_t lds = 0; uint64_t piece = kSitePiece;
-    Stream copy; Event ev_made, ev_d2h[2]; DevBuf out, crc; scs_ctx::BgzfLane z; Pinned<char> h_out[2]; Pinned<uint32_t> h_z;
+    Stream copy; Event ev_made, ev_d2h[2]; DevBuf out, crc; BgzfLane z; Pinned<char> h_out[2]; Pinned<uint32_t> h_z;
     SiteOut() {
         if (seam_env("SCS_TEST_SITE_LDS")) lds = (uint32_t)std::max(16, atoi(seam_env("SCS_TEST_SITE_LDS")));                            // tests: lines that straddle two LDS runs
         if (seam_env("SCS_TEST_SITE_PIECE")) piece = (uint64_t)std::max(1L, std::min(atol(seam_env("SCS_TEST_SITE_PIECE")), 1L << 30));      // tests: a run's bytes in many pieces
@@ -57,7 +32,7 @@ struct SiteOut {
         copy.ensure(hipStreamNonBlocking);
         ev_made.ensure(hipEventDisableTiming | hipEventBlockingSync); for (int k = 0; k < 2; ++k) ev_d2h[k].ensure(hipEventDisableTiming | hipEventBlockingSync);
         h_z.reserve(64, hipHostMallocDefault); memset(h_z, 0, 64);
-        if (bgzf && !crc.p) { std::vector<uint32_t> tabs(512); bgzf_host_tables(tabs.data(), tabs.data() + 256); upload(crc, tabs, s); HIP_OK(hipStreamSynchronize(s)); }
+        if (bgzf) bgzf_crc_tables(crc, s);
     }
     // the t.n entries' lines (t_n bytes at the offsets offs; site_pos / counts: launch_site_emit's) made on the ctx stream; returns where
     // the bytes to ship lie and sets *n to their number, once they are made
@@ -68,14 +43,8 @@ struct SiteOut {
         tm.begin(s);
         launch_site_emit(s, t, recs, offs, lds, out.as<char>(), site_pos, counts);
         if (bgzf) {                                        // the text becomes BGZF blocks where it lies (the FASTQ blocks' kernels); their total travels to h_z
-            if (bgzf_bound(t_n) > 0xFFFFFFF0ull) throw ScsError(SCS_EOVERFLOW, too_large);
-            const uint32_t nblk = bgzf_blocks(t_n);
-            z.plan.reserve(std::max<size_t>((size_t)nblk * BGZF_PLAN_BYTES, 16), s); z.sizes.reserve(((size_t)nblk + 2) * 4, s); z.offs.reserve(((size_t)nblk + 2) * 4, s);
             z.out[0].reserve(bgzf_bound(t_n), s);
-            launch_bgzf_plan(s, made, t_n, z.plan.as<uint8_t>(), z.sizes.as<uint32_t>());
-            exclusive_scan_u32(s, z.sizes.as<uint32_t>(), z.offs.as<uint32_t>(), nblk, scan_tmp, scan_bytes);
-            launch_bgzf_emit(s, made, t_n, z.plan.as<uint8_t>(), z.sizes.as<uint32_t>(), z.offs.as<uint32_t>(), crc.as<uint32_t>(), crc.as<uint32_t>() + 256, z.out[0].as<char>(), 0);
-            HIP_OK(hipMemcpyAsync(h_z, z.offs.as<uint32_t>() + nblk, 4, hipMemcpyDeviceToHost, s));
+            bgzf_in_place(s, z, crc, made, t_n, z.out[0].as<char>(), h_z, scan_tmp, scan_bytes, too_large);
             made = z.out[0].as<char>();
         }
         tm.end(s);
@@ -83,7 +52,7 @@ struct SiteOut {
         *n = bgzf ? (uint64_t)h_z[0] : t_n;
         return made;
     }
-    void ship(SiteFd& fd, const char* p, uint64_t n, const std::string& failed) {
+    void ship(OutFile& fd, const char* p, uint64_t n) {
         const uint64_t P = piece, np = (n + P - 1) / P;
         for (int q = 0; q < 2; ++q) h_out[q].reserve(std::min<uint64_t>(P, std::max<uint64_t>(n, 16)), hipHostMallocDefault);
         for (uint64_t sent = 0, done = 0; done < np; ++done) {
@@ -92,13 +61,11 @@ struct SiteOut {
                 HIP_OK(hipEventRecord(ev_d2h[sent & 1], copy));
             }
             HIP_OK(hipEventSynchronize(ev_d2h[done & 1]));
-            if (!fd.write_all(h_out[done & 1], std::min(P, n - done * P))) throw ScsError(SCS_EIO, failed);
+            fd.write(h_out[done & 1], std::min(P, n - done * P));
         }
     }
     ~SiteOut() { if (copy.s) (void)hipStreamSynchronize(copy); }
 };
-// the BGZF end-of-file block (SAM specification, section 4.1.2)
-static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // One call's work: the kernels' arguments over the ctx's tables, the per-slab counts, and everything the call allocates.  Its
 // destructor ends every way out of the call: both streams drained; the members then release themselves

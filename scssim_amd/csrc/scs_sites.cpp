@@ -45,15 +45,11 @@ int scs_write_artefacts(scs_ctx* c, const char* path, int flags, uint32_t min_re
         if (flags & ~1) throw ScsError(SCS_EINVAL, "scs_write_artefacts: unknown flag");
         site_check(c, "scs_write_artefacts");
         const bool bgzf = (flags & 1) != 0;
-        SiteFd fd; fd.fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
-        if (fd.fd < 0) throw ScsError(SCS_EIO, std::string("scs_write_artefacts: can not open ") + path + ": " + strerror(errno));
-        const std::string failed = std::string("scs_write_artefacts: writing ") + path + " failed";
+        OutFile fd; fd.open("scs_write_artefacts", path, bgzf);
         SiteJob J(c, min_reads, true); const hipStream_t s = J.s; KernelTimer& tm = J.tm;
         std::vector<std::string> names; for (const auto& r : c->recs) names.push_back(r.name);
-        std::string hd = site_header(names, c->rec_len.data());
-        if (bgzf) { std::vector<uint8_t> z; bgzf_compress_host((const uint8_t*)hd.data(), hd.size(), BGZF_LDS_OUT, z); hd.assign((const char*)z.data(), z.size()); }
-        if (!fd.write_all(hd.data(), hd.size())) throw ScsError(SCS_EIO, failed);
-        uint64_t total = hd.size(), n_sites = 0;
+        fd.header(site_header(names, c->rec_len.data()));
+        uint64_t n_sites = 0;
         if (J.max_e) J.em.open(s, bgzf);
         // Slab k: its sites and the text's size to the host (it sizes the output), emit pass (and BGZF over the text where it lies);
         // then the slab's bytes travel in pieces into the file (SiteOut)
@@ -64,21 +60,16 @@ int scs_write_artefacts(scs_ctx* c, const char* path, int flags, uint32_t min_re
             if (!t_n) continue;                            // (every site of the slab below min_reads)
             uint64_t n = 0;
             const char* made = J.em.make(s, tm, J.t, J.site_recs.as<SiteRec>(), J.offs.as<uint64_t>(), t_n, bgzf, J.scan_tmp.p, J.scan_bytes, "scs_write_artefacts: a slab's text exceeds 4 GB", &n);
-            J.em.ship(fd, made, n, failed); total += n;
+            J.em.ship(fd, made, n);
         }
         check_flags(c);                                    // (also: everything on the ctx stream is over)
         tm.add_units(n_sites); tm.collect();
-        if (bgzf) { if (!fd.write_all((const char*)kBgzfEof, 28)) throw ScsError(SCS_EIO, failed); total += 28; }
-        { const int f = fd.fd; fd.fd = -1; if (::close(f) != 0) throw ScsError(SCS_EIO, failed); }
+        fd.finish();
         if (sites) *sites = n_sites;
-        if (bytes) *bytes = total;
+        if (bytes) *bytes = fd.total;
     });
 }
 
-int scs_artefact_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) {
-    if (!c) return SCS_EINVAL;
-    if (launches) *launches = c->tm_site.launches; if (ms) *ms = c->tm_site.ms; if (units) *units = c->tm_site.units;
-    return SCS_OK;
-}
+int scs_artefact_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) { return kernel_time_of(c, &scs_ctx::tm_site, launches, ms, units); }
 
 }  // extern "C"

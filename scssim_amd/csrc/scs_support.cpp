@@ -45,8 +45,7 @@ void support_open(scs_ctx* c) {
             n += kept;
         }
         // the record starts for the kernels of this call (the job's own table goes with it)
-        std::vector<uint64_t> roff(c->recs.size() + 1, 0);
-        for (size_t r = 0; r < c->recs.size(); ++r) { roff[r] = c->rec_off[r]; roff[r + 1] = c->rec_off[r] + c->rec_len[r]; }
+        const std::vector<uint64_t> roff = record_starts(c);
         upload(c->sp_tab, roff, s); HIP_OK(hipStreamSynchronize(s));
     }
     uint32_t n_pos = 0;
@@ -115,14 +114,9 @@ int scs_write_site_support(scs_ctx* c, const char* path, int flags, uint64_t* si
         if (flags & ~1) throw ScsError(SCS_EINVAL, "scs_write_site_support: unknown flag");
         support_ready(c, "scs_write_site_support");
         const bool bgzf = (flags & 1) != 0; const hipStream_t s = c->stream; const uint64_t total_sites = c->sp_n_sites;
-        SiteFd fd; fd.fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
-        if (fd.fd < 0) throw ScsError(SCS_EIO, std::string("scs_write_site_support: can not open ") + path + ": " + strerror(errno));
-        const std::string failed = std::string("scs_write_site_support: writing ") + path + " failed";
+        OutFile fd; fd.open("scs_write_site_support", path, bgzf);
         std::vector<std::string> names; for (const auto& r : c->recs) names.push_back(r.name);
-        std::string hd = site_header(names, c->rec_len.data(), true);
-        if (bgzf) { std::vector<uint8_t> z; bgzf_compress_host((const uint8_t*)hd.data(), hd.size(), BGZF_LDS_OUT, z); hd.assign((const char*)z.data(), z.size()); }
-        if (!fd.write_all(hd.data(), hd.size())) throw ScsError(SCS_EIO, failed);
-        uint64_t total = hd.size();
+        fd.header(site_header(names, c->rec_len.data(), true));
         // what the call needs beyond the ctx's arrays belongs to it: the record table, a chunk's line sizes and offsets, the emitter.
         // The struct's destructor ends every way out: both streams drained, then the members release themselves
         struct Call { hipStream_t s; RecTable rt; SiteOut em; DevBuf sizes, offs, scan; Pinned<uint64_t> h_n; Event ev_n; KernelTimer idle{"k_sites"};
@@ -144,21 +138,16 @@ int scs_write_site_support(scs_ctx* c, const char* path, int flags, uint64_t* si
                 { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("site support: the sizing pass failed: ") + hipGetErrorString(le)); }
                 const uint64_t t_n = W.h_n[0]; uint64_t nb = 0;
                 const char* made = W.em.make(s, W.idle, t, recs, W.offs.as<uint64_t>(), t_n, bgzf, W.scan.p, sb, "scs_write_site_support: a chunk's text exceeds 4 GB", &nb, sp, c->sp_cnt.as<uint32_t>());
-                W.em.ship(fd, made, nb, failed); total += nb;
+                W.em.ship(fd, made, nb);
             }
         }
         check_flags(c);                                    // (also: everything on the ctx stream is over)
-        if (bgzf) { if (!fd.write_all((const char*)kBgzfEof, 28)) throw ScsError(SCS_EIO, failed); total += 28; }
-        { const int f = fd.fd; fd.fd = -1; if (::close(f) != 0) throw ScsError(SCS_EIO, failed); }
+        fd.finish();
         if (sites) *sites = total_sites;
-        if (bytes) *bytes = total;
+        if (bytes) *bytes = fd.total;
     });
 }
 
-int scs_site_support_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) {
-    if (!c) return SCS_EINVAL;
-    if (launches) *launches = c->tm_support.launches; if (ms) *ms = c->tm_support.ms; if (units) *units = c->tm_support.units;
-    return SCS_OK;
-}
+int scs_site_support_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) { return kernel_time_of(c, &scs_ctx::tm_support, launches, ms, units); }
 
 }  // extern "C"

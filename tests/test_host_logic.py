@@ -636,3 +636,18 @@ def test_batch_plan_sizes():
         assert batch == 64 and order == list(range(16)) and region_of == [0] * 16
         assert 1000 - (len(order) - 1) * batch == 40                  # what is left for the last batch, from the probe's batch and nbatch
     assert scssim_amd.batch_plan_probe(0, 150, False)[1:] == ([], []) and scssim_amd.batch_plan_probe(1, 150, True, 4, 4)[0] == 1
+
+
+def test_output_file_sanitizer_tool_builds_and_passes(tmp_path):
+    """tools/outfile_host_check.py: the output file of the truth SAM / BAM and of the tables (scs_outfile.h) as a stand-alone CPU
+    program under AddressSanitizer and UndefinedBehaviorSanitizer -- header, buffers and end-of-file block, plain and BGZF, read back
+    and inflated; the error texts.  Skips only where the host compiler has no sanitizer runtimes."""
+    import subprocess
+    import sys
+    probe = tmp_path / "p.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    r = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp_path / "p")], capture_output=True, text=True)
+    if r.returncode != 0 or subprocess.run([str(tmp_path / "p")]).returncode != 0:
+        pytest.skip("the host compiler lacks the AddressSanitizer / UndefinedBehaviorSanitizer runtimes: " + r.stderr[-300:])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "outfile_host_check.py")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and " 0 wrong" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
