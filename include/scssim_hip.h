@@ -470,6 +470,18 @@ int         scs_site_support_line_probe(const char* name, uint64_t pos, uint32_t
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);
+/* Test seam of the staging kernels (the FASTA parser, the slice gather, the genome index): what they left on the device for the
+ * resident stretch of the genome, copied back as it lies -- no kernel is launched, no state changes.  info[0..3] = slice_base (genome
+ * coordinate of the first resident base; 0 unless a sharded ctx staged only its own stretch), slice_len (resident bases), the number
+ * of records, the bytes of their names.  names: the index names, each followed by '\n' (names_cap bytes); rec_lens: the records'
+ * lengths (rec_cap entries); SCS_EOVERFLOW with info filled in when either is too small.  With nwords = (slice_len + 63) / 64:
+ * codes: slice_len base codes (0..3 = ACGT, 4 = anything else); gc_bits / n_bits: nwords + 1 words, bit i & 63 of word i >> 6 set for a
+ * G or C / for a code 4, word nwords zero; gc_pref / n_pref: nwords + 1 exclusive running popcounts of them; gc_pair: nwords + 1 pairs
+ * {gc_bits, gc_pref}; g2: 4 nwords words, base i in bits 2 (i & 15) of word i >> 4, a code 4 as 0; has_n: after scs_create_frags, one
+ * byte per fragment of scs_download_frags, 1 when it holds a code 4.  Any pointer but info may be NULL.  SCS_EINVAL: no genome
+ * staged, or has_n asked for before scs_create_frags. */
+int         scs_download_genome(scs_ctx* ctx, uint64_t info[4], char* names, size_t names_cap, uint64_t* rec_lens, uint64_t rec_cap, uint8_t* codes,
+                                uint64_t* gc_bits, uint64_t* n_bits, uint64_t* gc_pref, uint64_t* n_pref, uint64_t* gc_pair, uint32_t* g2, uint8_t* has_n);
 /* Host-only test seam of the truth kernels: one read's SAM record through their formatter.  n = window length (the model's read
  * length); pos0 = 0-based record coordinate of window base 0 (the rightmost base when reverse); events = nev triples {window
  * position, deletion?, length} in read orientation, as Profile::predict draws them (a deletion clipped to the window end); the

@@ -1015,6 +1015,31 @@ class GenReads:
         self._ck(self._L.scs_download_frags(self._ctx, ptr(goff), ptr(ln), ptr(st)))
         return dict(goff=goff, len=ln, strand=st)
 
+    def download_genome(self, has_n=False):
+        """Test seam: what staging left on the device for the resident stretch of the genome (scs_download_genome), copied back as it
+        lies: dict of slice_base, slice_len, names, rec_lens and the numpy arrays codes (uint8), gc_bits / n_bits / gc_pref / n_pref
+        (uint64, words + 1), gc_pair (uint64 [words + 1, 2]), g2 (uint32, 4 x words); has_n=True, after create_frags: has_n (uint8
+        per fragment of download_frags)."""
+        np = self._np
+        fn = self._L.scs_download_genome
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64] + [C.c_void_p] * 8
+        info = np.zeros(4, np.uint64)
+        self._ck(fn(self._ctx, info.ctypes.data, None, 0, None, 0, *([None] * 8)))
+        base, n, nrec, nbytes = (int(v) for v in info)
+        nw = (n + 63) // 64
+        names, lens = C.create_string_buffer(max(1, nbytes)), np.zeros(max(1, nrec), np.uint64)
+        a = dict(codes=np.zeros(n, np.uint8), gc_bits=np.zeros(nw + 1, np.uint64), n_bits=np.zeros(nw + 1, np.uint64), gc_pref=np.zeros(nw + 1, np.uint64),
+                 n_pref=np.zeros(nw + 1, np.uint64), gc_pair=np.zeros((nw + 1, 2), np.uint64), g2=np.zeros(4 * nw, np.uint32))
+        nf = self.stats()["fragments"] if has_n else 0
+        hn = np.zeros(max(1, nf), np.uint8)                           # (a pointer even for no fragments: asking before create_frags is refused)
+        ptr = lambda x: x.ctypes.data if x.size else None
+        self._ck(fn(self._ctx, info.ctypes.data, names, nbytes, lens.ctypes.data, nrec, *[ptr(a[k]) for k in ("codes", "gc_bits", "n_bits", "gc_pref", "n_pref", "gc_pair", "g2")],
+                    hn.ctypes.data if has_n else None))
+        if has_n:
+            a["has_n"] = hn[:nf]
+        a.update(slice_base=base, slice_len=n, names=names.raw[:nbytes].decode("latin-1").split("\n")[:nrec], rec_lens=lens[:nrec].copy())
+        return a
+
     def set_batch_checksums(self, on=True):
         """Every batch of the following yield_reads* calls gets a 64-bit checksum per mate, computed on the device."""
         self._L.scs_set_batch_checksums.argtypes = [C.c_void_p, C.c_int]

@@ -28,7 +28,8 @@ __global__ void k_encode_bases(uint8_t* __restrict__ g, uint64_t n) {
 // ------------------------------------------------------------------------------------------------
 // FASTA parsed on the device (lib/fastahack/Fasta.cpp:45-215 index + 304-334 getSubSequence, Genome.cpp:176-195):
 // the file's raw bytes arrive in chunks; a byte is a base iff its LINE is a sequence line (not a '>' header, not a ';'
-// comment) and it is neither '\n' nor '\r'.  The line's kind is the kind of its first byte carried forward: an inclusive scan
+// comment) and it is neither '\n' nor the one '\r' in front of a '\n' or of the file's end (the host parser's rule, load_fasta:
+// any other '\r' is a base that is not ACGT).  The line's kind is the kind of its first byte carried forward: an inclusive scan
 // with "the right operand wins if it starts a line" (kinds 1 header, 2 comment, 3 sequence; 0 = not a line start).  Kept
 // bytes are compacted behind the bases of the earlier chunks; headers (rare) are listed with their file offset and the
 // number of bases before them, from which the host takes the names and the record lengths.
@@ -44,12 +45,13 @@ __global__ void __launch_bounds__(256) k_fa_kind(const uint8_t* __restrict__ raw
     if (i == 0 && !start) k = (uint8_t)st[2];                                      // the line continues from the previous chunk
     kind[i] = k;
 }
+// raw[n] is readable: the byte behind the chunk -- the file's next byte, or a '\n' behind the file's last one (what ends a '\r' line end there)
 __global__ void __launch_bounds__(256) k_fa_keep(const uint8_t* __restrict__ raw, const uint8_t* __restrict__ kind, uint32_t n, uint32_t* __restrict__ keep) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i > n) return;
     if (i == n) { keep[i] = 0; return; }
     const uint32_t b = raw[i];
-    keep[i] = (kind[i] == 3 && b != '\n' && b != '\r') ? 1u : 0u;
+    keep[i] = (kind[i] == 3 && b != '\n' && !(b == '\r' && raw[i + 1] == '\n')) ? 1u : 0u;
 }
 __global__ void __launch_bounds__(256) k_fa_scatter(const uint8_t* __restrict__ raw, const uint8_t* __restrict__ kind, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos,
                                                     uint32_t n, unsigned long long chunk_off, const unsigned long long* __restrict__ st, uint8_t* __restrict__ out,

@@ -207,6 +207,31 @@ int scs_detlog_batch(scs_ctx* c, const double* x, size_t n, double* out) {
     });
 }
 
+// what staging left on the device for the resident stretch of the genome, copied back as it lies: no kernel runs, no state changes
+int scs_download_genome(scs_ctx* c, uint64_t info[4], char* names, size_t names_cap, uint64_t* rec_lens, uint64_t rec_cap, uint8_t* codes,
+                        uint64_t* gc_bits, uint64_t* n_bits, uint64_t* gc_pref, uint64_t* n_pref, uint64_t* gc_pair, uint32_t* g2, uint8_t* has_n) {
+    return guarded(c, [&] {
+        if (!info) throw ScsError(SCS_EINVAL, "scs_download_genome: null info");
+        if (!c->have_genome) throw ScsError(SCS_EINVAL, "scs_download_genome: no genome loaded");
+        if (has_n && !c->have_frags) throw ScsError(SCS_EINVAL, "scs_download_genome: has_n needs scs_create_frags first");
+        std::string nm; for (auto& r : c->recs) { nm += r.name; nm += '\n'; }
+        const uint64_t n = c->slice_len, nw = (n + 63) / 64;
+        info[0] = c->slice_base; info[1] = n; info[2] = c->recs.size(); info[3] = nm.size();
+        if ((names && names_cap < nm.size()) || (rec_lens && rec_cap < c->rec_len.size())) throw ScsError(SCS_EOVERFLOW, "scs_download_genome: names or rec_lens too small");
+        if (names) memcpy(names, nm.data(), nm.size());
+        if (rec_lens) std::copy(c->rec_len.begin(), c->rec_len.end(), rec_lens);
+        hipStream_t s = c->stream;
+        auto down = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s)); };
+        down(codes, c->genome.p, n);
+        down(gc_bits, c->gx_gc_bits.p, (nw + 1) * 8); down(n_bits, c->gx_n_bits.p, (nw + 1) * 8);
+        down(gc_pref, c->gx_gc_pref.p, (nw + 1) * 8); down(n_pref, c->gx_n_pref.p, (nw + 1) * 8);
+        down(gc_pair, c->gx_gc_pair.p, (nw + 1) * 16);
+        down(g2, c->genome2.as<uint32_t>() + 16, nw * 16);                             // (behind the 64 bytes of slack in front: index_genome)
+        down(has_n, c->df_hasn.p, c->f_len.size());
+        HIP_OK(hipStreamSynchronize(s));
+    });
+}
+
 int scs_fasta_probe(const char* path, int* n_records, uint64_t* total_bases, uint64_t* checksum, char* names_buf, size_t names_len, char* errbuf, size_t errlen) {
     if (!path) return SCS_EINVAL;
     std::vector<FastaRecord> recs;

@@ -105,10 +105,18 @@ void index_genome(scs_ctx* c, uint64_t tot) {
     }
 }
 
+// bytes of the raw file per chunk of the parser, and of a piece of the slice path (SCS_TEST_FASTA_CHUNK: chunk borders wherever a test wants them)
+static size_t fasta_chunk_bytes() {
+    const char* e = seam_env("SCS_TEST_FASTA_CHUNK");
+    return e ? (size_t)std::max(1L, std::min(atol(e), 1L << 30)) : (size_t)64u << 20;
+}
+
 // Genome::loadRefSeq for whole-genome inputs: the FASTA is mmap'ed and its RAW bytes go to the device in
 // 64 MB chunks through two pinned buffers (four host threads copy a chunk out of the page cache while the GPU works on the
 // one before); the device separates bases from line ends, headers and comments (k_fa_*), compacts them into the genome
 // buffer and lists the headers; the host only reads the header lines.  Then encode + bit index as for every genome.
+// Every chunk goes up with the one byte behind it (the next chunk's first, or a '\n' behind the file's end): k_fa_keep's look-ahead
+// for a '\r', which is a line end only in front of a '\n' or of the end of the file.
 void stage_fasta_on_device(scs_ctx* c, const std::string& path_in) {
     const std::string path = fasta_plain_path(path_in);
     const int fd = open(path.c_str(), O_RDONLY);
@@ -122,10 +130,10 @@ void stage_fasta_on_device(scs_ctx* c, const std::string& path_in) {
     (void)madvise((void*)base, size, MADV_SEQUENTIAL);
     struct Unmap { const char* b; size_t n; int fd; ~Unmap() { munmap((void*)b, n); close(fd); } } unmap{base, size, fd};
     hipStream_t s = c->stream;
-    const size_t CH = 64u << 20; const uint32_t hdr_cap = 1u << 20;
+    const size_t CH = fasta_chunk_bytes(); const uint32_t hdr_cap = 1u << 20;
     DevBuf d_raw[2], d_kind, d_keep, d_pos, d_st, d_hdr, d_tmp; Pinned<char> h_raw[2]; Event ev[2]; bool ev_used[2] = {false, false};
     const size_t ch = std::min(CH, size);
-    for (int k = 0; k < 2; ++k) { d_raw[k].reserve(ch + 16, s); h_raw[k].reserve(ch, hipHostMallocDefault); ev[k].ensure(hipEventDisableTiming); }
+    for (int k = 0; k < 2; ++k) { d_raw[k].reserve(ch + 16, s); h_raw[k].reserve(ch + 1, hipHostMallocDefault); ev[k].ensure(hipEventDisableTiming); }
     d_kind.reserve(ch + 16, s); d_keep.reserve((ch + 2) * 4, s); d_pos.reserve((ch + 2) * 4, s); d_st.reserve(64, s); d_hdr.reserve((size_t)hdr_cap * 16, s);
     d_tmp.reserve(fasta_chunk_temp_bytes((uint32_t)ch), s);
     HIP_OK(hipMemsetAsync(d_st.p, 0, 64, s));
@@ -139,7 +147,8 @@ void stage_fasta_on_device(scs_ctx* c, const std::string& path_in) {
             memcpy(h_raw[b], base + off, std::min(per, n));
             for (auto& t : th) t.join();
         }
-        HIP_OK(hipMemcpyAsync(d_raw[b].p, h_raw[b], n, hipMemcpyHostToDevice, s));
+        h_raw[b][n] = off + n < size ? base[off + n] : '\n';                       // the byte behind the chunk (k_fa_keep)
+        HIP_OK(hipMemcpyAsync(d_raw[b].p, h_raw[b], n + 1, hipMemcpyHostToDevice, s));
         HIP_OK(hipEventRecord(ev[b], s)); ev_used[b] = true;
         launch_fasta_chunk(s, d_raw[b].as<uint8_t>(), (uint32_t)n, (unsigned long long)off, d_st.as<unsigned long long>(), d_kind.as<uint8_t>(), d_keep.as<uint32_t>(), d_pos.as<uint32_t>(),
                            c->genome.as<uint8_t>(), d_hdr.as<unsigned long long>(), hdr_cap, d_tmp.p, d_tmp.cap);
@@ -254,7 +263,7 @@ bool stage_fasta_slice(scs_ctx* c, const std::string& path) {
     DevBuf d_ragged;
     d_ragged.reserve(16, s); HIP_OK(hipMemsetAsync(d_ragged.p, 0, 4, s));
     // record by record: the bytes of [a, b) -> pinned -> device, line ends dropped by the gather
-    const size_t CH = 64u << 20; DevBuf d_raw; Pinned<char> h_raw;
+    const size_t CH = fasta_chunk_bytes(); DevBuf d_raw; Pinned<char> h_raw;
     h_raw.reserve(CH, hipHostMallocDefault); d_raw.reserve(CH + 16, s);
     for (size_t r = 0; r < ents.size() && n_slice; ++r) {
         if (ents[r].len == 0) continue;                                             // an empty record (index line "name 0 off 0 0"): nothing to read, no line geometry
