@@ -239,6 +239,33 @@ int         scs_truth_bytes(const scs_ctx* ctx, uint64_t* bytes);
  * GPU work.  scs_truth_bytes then reports the BAM file's size (compressed; header and end-of-file block included), and
  * scs_kernel_time(which = 6) the BAM passes with their BGZF launches. */
 int         scs_set_truth_bam(scs_ctx* ctx, const char* path);
+/* scs_set_truth_ref_sam(ctx, path): a third truth output (NULL: off, the default -- no code of it runs): a plain-text SAM whose
+ * records are aligned to the ORIGINAL REFERENCE the lift table names (see "lift table" below), made on the GPU from the
+ * haplotype alignment and the table.  Still at most one truth output per ctx: setting one while another is on fails with
+ * SCS_EINVAL and names both; NULL clears only its own (and frees what its yield calls allocated).  It applies where the truth
+ * SAM does; a sharded ctx, writers > 1, scs_yield_reads_device and a ctx without a lift table (scs_simuvars keeps one,
+ * scs_load_lift reads one) fail the yield call with SCS_EINVAL.  It works beside the depth tracks and the site support.
+ * scs_truth_bytes and scs_kernel_time(which = 6) report it as they do the SAM.
+ * Header: @HD VN:1.6 SO:unsorted, one @SQ SN LN per reference record of the table in its order, @PG ID:scssim PN:scssim.
+ * One record per FASTQ record, in FASTQ order; QNAME, SEQ, QUAL, their orientation and the 0x10 / 0x20 bits are the haplotype
+ * SAM's (simuvars makes no inversions).  The haplotype CIGAR is walked with a cursor through the segment table: M in an R
+ * segment stays M at ref_pos + (g - hap_off), M in an I segment and a sequencing insertion are I, D in an R segment stays D, D in
+ * an I segment is nothing.  Going from R segment s to the next R segment t it touches, the walk emits D of t.ref_pos - (s.ref_pos +
+ * s.len) bases when t.ref_rec == s.ref_rec and that is >= 0 (collinear: a planted deletion, a CN-0 stretch); any other junction
+ * (the jump back between tandem copies, another reference record) is a cut, and cuts split the read into blocks.  The record
+ * shows the PRIMARY block -- the one with the most M bases, the first on a tie: the read bases from its first to its last M base
+ * keep their ops (merged by kind), every base outside is soft-clipped (S), D at the block's edges is dropped; POS = the first M
+ * base's reference coordinate + 1, RNAME its reference record, MAPQ 255.  A read with no lifted M base (wholly in inserted
+ * sequence) is unmapped: FLAG |= 0x4, MAPQ 0, CIGAR *, RNAME / POS the mate's when that is mapped, else * 0.  Mate fields come
+ * from the two primary blocks: 0x1, 0x40 / 0x80; 0x8 when the mate is unmapped; 0x2 only when both are mapped to one reference
+ * record; RNEXT '=' on the same record, the mate's name on another, '*' when neither is mapped; PNEXT the mate's POS (the read's
+ * own when only the mate is unmapped); TLEN +-(rightmost reference end - leftmost reference start + 1) when both are mapped to
+ * one record (+ on the smaller POS, on read 1 on a tie), else 0.  SE: '*' 0 0.  Tags: YH:Z the haplotype record's name and YP:i
+ * the haplotype POS (the join key to the haplotype SAM and the amplicon table), YB:i the number of blocks (0: unmapped).  There
+ * is no NM / MD: against the reference they need the reference's bases under the planted SNPs and deletions, which genreads
+ * never stages.  A read that cannot be lifted (placed outside its record, a walk that leaves the table or its record's segments,
+ * a segment that lifts outside its reference record) fails the call (SCS_EOVERFLOW), never writes a wrong record. */
+int         scs_set_truth_ref_sam(scs_ctx* ctx, const char* path);
 /* ---- depth track: binned read and base counts of the job, made on the GPU ----------------------------------------------
  * scs_set_depth(ctx, bin_width): the following yield calls also count, per bin of bin_width >= 1 bases of the staged genome, the
  * reads that start in the bin and the bases aligned in it (0: off, the default -- no buffer exists, no depth code runs).  Record r
@@ -348,6 +375,18 @@ int         scs_lift_read_probe(int n, int64_t pos0, int reverse, const int32_t*
                                 const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
                                 const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, uint32_t bin_width,
                                 uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out, int* lift_err);
+/* Host-only test seam of the truth SAM on the reference: one read's line through the formatter its kernels run.  The arguments of
+ * scs_truth_record_probe without the genome, pos0 / mate_pos0 = GLOBAL staged indices of window base 0; the table and the records
+ * as arrays (scs_lift_read_probe); names = the reference records' names then the staged records', a newline behind each
+ * (scs_lift_plan_probe); rname = the staged record's name for YH (NULL: taken from names).  SCS_EINVAL: not a valid alignment, or
+ * the read cannot be lifted -- *lift_err then says why, as scs_lift_read_probe's. */
+int         scs_truth_ref_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                                       int64_t pos0, int reverse, const int32_t* events, int nev,
+                                       int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                                       const char* seq, const char* qual, int len,
+                                       const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                                       const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, const char* names, size_t names_len,
+                                       char* out, size_t cap, size_t* n_out, int* lift_err);
 /* ---- amplicon table: the amplified pool the reads were drawn from, made on the GPU ---------------------------------------
  * One entry per FULL amplicon, in list order: entry i is the amplicon whose index the FASTQ / SAM record names print.
  *   rec          the staged record the amplicon lies in (a fragment never straddles records)

@@ -460,6 +460,42 @@ def lift_read_probe(table, hap_lens, ref_lens, pos0, n, events=(), reverse=False
     return first.value, [(int(bins[i]), int(bases[i])) for i in range(k.value)]
 
 
+def truth_ref_record_probe(table, hap_lens, ref_lens, ref_names, seq, qual, pos0, n, events=(), reverse=False, hap_names=None, rname=None,
+                           amp=0, cnt=1, paired=False, is_read2=False, mate=None):
+    """Host-only: one read's line (with its newline) of the truth SAM on the original reference, through the formatter its kernels
+    run.  table: a LiftTable (or any object with its five arrays); hap_lens / ref_lens / ref_names: the staged and the reference
+    records; pos0 = GLOBAL staged index of window base 0; n, events, reverse, seq, qual, mate as for truth_record_probe (the
+    mate's pos0 global too).  rname = the staged record's name for YH (None: from hap_names).  A read that cannot be lifted
+    raises ScsError (SCS_EINVAL) whose .lift_err says why (0: not a valid alignment)."""
+    import numpy as np
+    L = load_library()
+    f = L.scs_truth_ref_record_probe
+    f.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int,
+                  C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int] + [C.c_void_p] * 5 + \
+                 [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    enc = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+    seq, qual = enc(seq), enc(qual)
+    ev = lambda es: (C.c_int32 * max(1, 3 * len(es)))(*[int(v) for e in es for v in e])
+    m_pos, m_rev, m_ev = mate if mate is not None else (0, False, ())
+    segs = [np.ascontiguousarray(getattr(table, k), dt) for k, dt in (("hap_off", np.uint64), ("len", np.uint64), ("ref_pos", np.uint64), ("ref_rec", np.uint32), ("kind", np.uint32))]
+    hl, rl = np.ascontiguousarray(hap_lens, np.uint64), np.ascontiguousarray(ref_lens, np.uint64)
+    names = "".join(x + "\n" for x in list(ref_names) + list(hap_names or ())).encode()
+    args = [int(paired), int(is_read2), amp, cnt, enc(rname) if rname is not None else None, int(n), int(pos0), int(bool(reverse)), ev(events), len(events),
+            int(m_pos), int(bool(m_rev)), ev(m_ev), len(m_ev), seq, qual, len(seq)] + [x.ctypes.data for x in segs] + \
+           [len(segs[0]), hl.ctypes.data, len(hl), rl.ctypes.data, len(rl), names, len(names)]
+    size, le = C.c_size_t(), C.c_int()
+    rc = f(*args, None, 0, C.byref(size), C.byref(le))
+    if rc:
+        e = ScsError(rc, "scs_truth_ref_record_probe: " + ("the read cannot be lifted (%d)" % le.value if le.value else "not a valid alignment"))
+        e.lift_err = le.value
+        raise e
+    out = C.create_string_buffer(size.value)
+    rc = f(*args, out, size.value, C.byref(size), C.byref(le))
+    if rc:
+        raise ScsError(rc, "scs_truth_ref_record_probe")
+    return out.raw[:size.value].decode()
+
+
 def support_read_probe(pos0, n, seq, positions, events=(), reverse=False, rec_len=1 << 40):
     """Host-only: what one read shows at the listed record coordinates, through the function the site support kernel runs.  pos0, n,
     events, reverse, rec_len as for depth_read_probe; seq = the FASTQ record's bases; positions ascending and distinct.  Returns
@@ -793,6 +829,12 @@ class GenReads:
         """The same records as BAM, made and compressed on the GPU (None: off).  One truth output per ctx: fails while the SAM is on."""
         self._L.scs_set_truth_bam.argtypes = [C.c_void_p, C.c_char_p]
         self._ck(self._L.scs_set_truth_bam(self._ctx, os.fsencode(path) if path is not None else None))
+
+    def set_truth_ref_sam(self, path):
+        """The reads' true alignments on the ORIGINAL REFERENCE as SAM, lifted through the lift table on the GPU (None: off).  Needs a
+        lift table (simuvars, load_lift); one truth output per ctx: fails while the SAM or the BAM is on."""
+        self._L.scs_set_truth_ref_sam.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_set_truth_ref_sam(self._ctx, os.fsencode(path) if path is not None else None))
 
     def truth_bytes(self):
         """Bytes of the truth SAM (header included) or BAM (compressed, header and end-of-file block included) the last yield call wrote."""

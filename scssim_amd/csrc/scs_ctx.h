@@ -129,8 +129,9 @@ struct Stream {
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default; Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }         // (movable, for vectors of them; not copyable)
-    ~Event() { if (e) { (void)hipEventDestroy(e); census_add(census().events, -1); } }
+    ~Event() { release(); }
     void ensure(unsigned flags) { if (e) return; HIP_OK(hipEventCreateWithFlags(&e, flags)); census_add(census().events, 1); }
+    void release() { if (e) { (void)hipEventDestroy(e); census_add(census().events, -1); } e = nullptr; }
     operator hipEvent_t() const { return e; }
 };
 template <class T> struct Pinned {                                               // a pinned host block of T
@@ -256,6 +257,9 @@ struct scs_ctx {
     // truth BAM (scs_set_truth_bam): truth_path names a BAM; t_out then holds the batch's binary records, which become BGZF blocks in
     // z[2].out; the blocks' total reaches the host through h_z[slot][2] behind ev_z[slot]
     bool truth_bam = false;
+    // truth SAM on the original reference (scs_set_truth_ref_sam): truth_path names a SAM whose records are
+    // lifted through the lift table (d_lift); t_refs: the reference records' lengths, name offsets and names as the kernels read them
+    bool truth_ref = false; DevBuf t_refs;
     // depth track (scs_set_depth): the bin width (0: off -- no buffer below exists, no depth code runs), the counters of the last
     // yield call (reads[n_bins] then bases[n_bins], zeroed on the ctx stream at the start of every call; depth_valid: a call with
     // depth on has finished) and the kernel's record table (rec_off[nr + 1] then bin_off[nr + 1])
@@ -380,6 +384,9 @@ BatchPlan plan_batches(uint64_t P, uint32_t read_length, bool to_sink, int write
 void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_out, uint64_t* pairs_out);
 // truth SAM: refuses (SCS_EINVAL) the targets it does not apply to; device: scs_yield_reads_device, writers: the file sink's
 void truth_check(scs_ctx* c, bool device, int writers);
+// the truth SAM on the reference is switched off: everything its yield calls made for it goes (the truth passes' buffers, which
+// the next truth output of any kind makes again)
+void truth_ref_release(scs_ctx* c);
 // depth track: refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the staged records' bins (SCS_EINVAL beyond DEPTH_MAX_BINS)
 void depth_check(scs_ctx* c);
 uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);

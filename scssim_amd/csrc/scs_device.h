@@ -244,10 +244,14 @@ struct PlaceArgs {
     const uint32_t* ev_hdr; const uint4* ev_dat;           // the batch's indel pass
     DevTables tb; RngKey key; uint32_t slot; uint32_t* flags;
 };
+struct LiftSeg;
 struct TruthArgs : PlaceArgs {
     const uint64_t* off1; const uint64_t* off2; const char* fq1; const char* fq2;   // its FASTQ text and record offsets (OFF_MASK)
     const uint8_t* g;                                      // the byte genome
     const uint64_t* rec_off; const uint32_t* name_off; const char* names; uint32_t n_rec;   // record starts (n_rec + 1), names
+    // the truth SAM on the reference alone (behind everything the SAM and BAM kernels read): the lift table, the reference
+    // records' lengths (n_ref) and names (offsets: n_ref + 1)
+    const LiftSeg* segs; uint32_t n_seg; const uint64_t* ref_len; uint32_t n_ref; const uint32_t* ref_name_off; const char* ref_names;
 };
 void launch_truth_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);                 // SAM bytes per pair (both mates); offsets: exclusive_scan_u32_to_u64
 uint32_t truth_pairs_per_block(uint64_t fq_bytes, uint32_t np);                             // the emit pass' LDS run, from the batch's FASTQ bytes
@@ -256,6 +260,11 @@ void launch_truth_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, 
 void launch_truth_bam_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);
 uint32_t truth_bam_pairs_per_block(uint64_t fq_bytes, uint32_t np);
 void launch_truth_bam_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, uint32_t lds, char* out);
+// the same passes for the truth SAM on the original reference (scs_k_truth_ref.hip): the records lifted
+// through a.segs; FLAG_LIFT where a read cannot be lifted
+void launch_truth_ref_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);
+uint32_t truth_ref_pairs_per_block(uint64_t fq_bytes, uint32_t np);
+void launch_truth_ref_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, uint32_t lds, char* out);
 
 // ---- depth track of a batch (scs_k_depth.hip; scs_set_depth): per bin the reads that start in it and the bases aligned in it,
 // summed per workgroup in an LDS table of `slots` entries (a power of two <= DEPTH_LDS_SLOTS; 0: every add goes to memory)

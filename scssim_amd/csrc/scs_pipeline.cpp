@@ -45,11 +45,11 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_READSLOT) m += " read slot (indel-extended read longer than the slot)";
         if (f & FLAG_INTERNAL) m += " internal";
         if (f & FLAG_KEYSPACE) m += " primer budget of a fragment beyond 2^20 (-p / -r far outside the reference's ranges)";
-        if (f & FLAG_TRUTH) m += " truth SAM / BAM (a read with more than 32 indel events, pair flags that are not a strand, or a pair whose BAM records outgrow the emit pass' LDS)";
+        if (f & FLAG_TRUTH) m += " truth SAM / BAM (a read with more than 32 indel events, pair flags that are not a strand, a pair whose records outgrow the emit pass' LDS, or a record the two passes size differently)";
         if (f & FLAG_DEPTH) m += " depth track (a read with more than 32 indel events, pair flags that are not a strand, or a read placed outside its record)";
         if (f & FLAG_AMP) m += " amplicon table (a lineage that does not fit its parents, view flags that are not a strand, an amplicon outside its record, or a line the two passes size differently)";
         if (f & FLAG_SITE) m += " artefact table (an amplicon that cannot be placed, a slab whose entries differ from their count, site counts that contradict each other, or a line the two passes size differently)";
-        if (f & FLAG_LIFT) m += " depth by reference bin (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand)";
+        if (f & FLAG_LIFT) m += " depth by reference bin / truth SAM on the reference (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand)";
         if (f & FLAG_SUPPORT) m += " site support (a read placed outside its record, pair flags that are not a strand, a read with more than 32 indel events, a FASTQ record that is not where the offsets say, or sites that are not in order)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
@@ -308,21 +308,26 @@ int scs_batch_checksums(const scs_ctx* c, uint64_t* out, size_t cap, size_t* n_b
 }
 int scs_get_stats(const scs_ctx* c, scs_stats* out) { if (!c || !out) return SCS_EINVAL; *out = c->st; return SCS_OK; }
 
-// one truth output per ctx: truth_path is the SAM's or (truth_bam) the BAM's; NULL clears only the caller's own
-static int set_truth(scs_ctx* c, const char* path, bool bam) {
+// one truth output per ctx: truth_path is the SAM's, (truth_bam) the BAM's or (truth_ref) the reference SAM's; NULL clears only the caller's own
+static int set_truth(scs_ctx* c, const char* path, int kind) {
+    static const char* const fn[3] = {"scs_set_truth_sam", "scs_set_truth_bam", "scs_set_truth_ref_sam"};
+    static const char* const what[3] = {"truth SAM", "truth BAM", "truth SAM on the reference"};
     if (!c) return SCS_EINVAL;
-    const bool on = !c->truth_path.empty();
-    if (path && on && c->truth_bam != bam) {
-        c->err = bam ? "scs_set_truth_bam: the truth SAM is on (scs_set_truth_sam); one truth output per ctx: clear it with scs_set_truth_sam(ctx, NULL) first"
-                     : "scs_set_truth_sam: the truth BAM is on (scs_set_truth_bam); one truth output per ctx: clear it with scs_set_truth_bam(ctx, NULL) first";
+    const bool on = !c->truth_path.empty(); const int cur = c->truth_bam ? 1 : c->truth_ref ? 2 : 0;
+    if (path && on && cur != kind) {
+        c->err = std::string(fn[kind]) + ": the " + what[cur] + " is on (" + fn[cur] + "); one truth output per ctx: clear it with " + fn[cur] + "(ctx, NULL) first";
         return SCS_EINVAL;
     }
-    if (path) { c->truth_path = path; c->truth_bam = bam; }
-    else if (!on || c->truth_bam == bam) { c->truth_path.clear(); c->truth_bam = false; }
+    if (path) { c->truth_path = path; c->truth_bam = kind == 1; c->truth_ref = kind == 2; }
+    else if (!on || cur == kind) {
+        if (c->truth_ref) truth_ref_release(c);
+        c->truth_path.clear(); c->truth_bam = false; c->truth_ref = false;
+    }
     return SCS_OK;
 }
-int scs_set_truth_sam(scs_ctx* c, const char* path) { return set_truth(c, path, false); }
-int scs_set_truth_bam(scs_ctx* c, const char* path) { return set_truth(c, path, true); }
+int scs_set_truth_sam(scs_ctx* c, const char* path) { return set_truth(c, path, 0); }
+int scs_set_truth_bam(scs_ctx* c, const char* path) { return set_truth(c, path, 1); }
+int scs_set_truth_ref_sam(scs_ctx* c, const char* path) { return set_truth(c, path, 2); }
 int scs_truth_bytes(const scs_ctx* c, uint64_t* bytes) { if (!c || !bytes) return SCS_EINVAL; *bytes = c->truth_bytes; return SCS_OK; }
 // ---- depth track
 int scs_set_depth(scs_ctx* c, uint32_t bin_width) {

@@ -5,6 +5,7 @@
 #include "scs_amp.h"
 #include "scs_site.h"
 #include "scs_support.h"
+#include "scs_truth_ref.h"
 
 // host-only: one read's record through the formatter the truth kernels run (scs_truth.h), as SAM text or as a BAM record
 static int truth_probe(bool bam, int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
@@ -69,6 +70,59 @@ int scs_truth_bam_record_probe(int paired, int is_read2, uint32_t amp, uint32_t 
                                char* out, size_t cap, size_t* n_out) {
     return truth_probe(true, paired, is_read2, amp, cnt, rname, n, pos0, reverse, events, nev, mate_pos0, mate_reverse, mate_events, mate_nev,
                        seq, qual, len, genome, genome_start, genome_len, out, cap, n_out);
+}
+
+// host-only: one read's record on the original reference through the formatter the kernels of scs_k_truth_ref.hip run
+// (scs_truth_ref.h), the sizing pass' counting sink checked against it.  names: the reference records' names, then the staged
+// records', a newline behind each (rname NULL: the staged record's name from there)
+int scs_truth_ref_record_probe(int paired, int is_read2, uint32_t amp, uint32_t cnt, const char* rname, int n,
+                               int64_t pos0, int reverse, const int32_t* events, int nev,
+                               int64_t mate_pos0, int mate_reverse, const int32_t* mate_events, int mate_nev,
+                               const char* seq, const char* qual, int len,
+                               const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                               const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, const char* names, size_t names_len,
+                               char* out, size_t cap, size_t* n_out, int* lift_err) {
+    if (lift_err) *lift_err = 0;
+    if (!seq || !qual || !n_out || n <= 0 || nev < 0 || mate_nev < 0 || nev > TRUTH_EVCAP || mate_nev > TRUTH_EVCAP || (nev && !events) || (paired && mate_nev && !mate_events) ||
+        !n_hap || !hap_lens || (n_ref && !ref_lens) || !names || (n_seg && (!seg_hap_off || !seg_len || !seg_ref_pos || !seg_ref_rec || !seg_kind))) return SCS_EINVAL;
+    auto pack = [](const int32_t* e, int k, std::vector<uint32_t>& v) {
+        for (int i = 0; i < k; ++i) {
+            if (e[3 * i] < 0 || e[3 * i] > 0xFFFF || e[3 * i + 2] <= 0 || e[3 * i + 2] > 0x7FFF) return false;
+            v.push_back(tev_pack((uint32_t)e[3 * i], e[3 * i + 1] ? 1u : 0u, (uint32_t)e[3 * i + 2]));
+        }
+        return true;
+    };
+    std::vector<uint32_t> e1, e2;
+    if (!pack(events, nev, e1) || (paired && !pack(mate_events, mate_nev, e2))) return SCS_EINVAL;
+    TruthAln a{pos0, reverse ? 1 : 0, n, nev, e1.data(), 0, 0, 0}, m{mate_pos0, mate_reverse ? 1 : 0, n, mate_nev, e2.data(), 0, 0, 0};
+    if (!truth_place(a) || a.qlen != len || (paired && !truth_place(m))) return SCS_EINVAL;
+    std::vector<std::string> nm; { std::string cur; for (size_t i = 0; i < names_len; ++i) { if (names[i] == '\n') { nm.push_back(cur); cur.clear(); } else cur.push_back(names[i]); } }
+    if (nm.size() < n_ref || (!rname && nm.size() < (size_t)n_ref + n_hap)) return SCS_EINVAL;
+    std::vector<uint32_t> noff(n_ref + 1, 0); std::string text;
+    for (uint32_t r = 0; r < n_ref; ++r) { text += nm[r]; noff[r + 1] = (uint32_t)text.size(); }
+    std::vector<LiftSeg> segs(n_seg);
+    for (uint32_t i = 0; i < n_seg; ++i) segs[i] = LiftSeg{seg_hap_off[i], seg_len[i], seg_ref_pos[i], seg_ref_rec[i], seg_kind[i]};
+    std::vector<uint64_t> roff(n_hap + 1, 0);
+    for (uint32_t r = 0; r < n_hap; ++r) roff[r + 1] = roff[r] + hap_lens[r];
+    uint32_t lo = 0, hi = n_hap;                                                       // the staged record, as the kernel finds it (read 1's; the mate must lie there too)
+    const int64_t first_lo = paired && is_read2 ? m.lo : a.lo;
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)roff[mid] <= first_lo) lo = mid; else hi = mid; }
+    const int64_t r0 = (int64_t)roff[lo], r1 = (int64_t)roff[lo + 1];
+    const LiftTab T{segs.data(), n_seg, ref_lens, n_ref};
+    LiftAln la{}, lm{};
+    int err = lift_align(a, r0, r1, T, la);
+    if (!err && paired) err = lift_align(m, r0, r1, T, lm);
+    if (err) { if (lift_err) *lift_err = err; return SCS_EINVAL; }
+    const std::string hname = rname ? std::string(rname) : nm[n_ref + lo];
+    const TruthRefLine li{amp, cnt, paired ? 1 : 0, is_read2 ? 1 : 0, paired ? m.rev : 0, hname.data(), (uint32_t)hname.size(), r0, r1, noff.data(), text.data()};
+    struct Src { const char* s; const char* q; char seq(int i) const { return s[i]; } char qual(int i) const { return q[i]; } } src{seq, qual};
+    struct VecOut { std::string t; void put(char ch) { t.push_back(ch); } } o;
+    TruthCount cn;
+    if ((err = truth_ref_record(o, a, li, T, la, lm, src)) || (err = truth_ref_record(cn, a, li, T, la, lm, src))) { if (lift_err) *lift_err = err; return SCS_EINVAL; }
+    if (cn.n != o.t.size()) return SCS_EDEVICE;                                        // (the sizing pass' sink and the formatter must agree)
+    *n_out = o.t.size();
+    if (out) { if (o.t.size() > cap) return SCS_EOVERFLOW; memcpy(out, o.t.data(), o.t.size()); }
+    return SCS_OK;
 }
 
 // host-only: the depth track's bin layout through the function the ctx runs (depth_layout, scs_depth.h); nothing of the bins' size is allocated

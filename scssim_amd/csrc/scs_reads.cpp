@@ -165,7 +165,7 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, depth_ref = c->dref_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, depth_ref = c->dref_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, bi = 0;                           // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
@@ -178,7 +178,8 @@ struct Yield {               // the state of one do_yield call
         // the header first, then the batches' records from the pipe's writer; the kernels' record table: starts, name offsets, names
         truth_fd.open(tname, c->truth_path, bam);
         std::string hd = "@HD\tVN:1.6\tSO:unsorted\n"; const uint32_t nr = (uint32_t)c->recs.size();
-        for (uint32_t r = 0; r < nr; ++r) hd += "@SQ\tSN:" + c->recs[r].name + "\tLN:" + std::to_string(c->rec_len[r]) + "\n";
+        if (tref) for (size_t r = 0; r < c->lift.ref_names.size(); ++r) hd += "@SQ\tSN:" + c->lift.ref_names[r] + "\tLN:" + std::to_string(c->lift.ref_lens[r]) + "\n";   // (the records of the reference the table names)
+        else for (uint32_t r = 0; r < nr; ++r) hd += "@SQ\tSN:" + c->recs[r].name + "\tLN:" + std::to_string(c->rec_len[r]) + "\n";
         hd += "@PG\tID:scssim\tPN:scssim\n";
         if (bam) {                                                                 // magic, l_text, the SAM's header text, n_ref, per record l_name / name / l_ref: BGZF made on the host (OutFile::header)
             std::string bh = "BAM\1";
@@ -193,6 +194,16 @@ struct Yield {               // the state of one do_yield call
         rt.make(c, s, &c->t_recs);                                                 // (in the ctx's buffer: it stays allocated between yield calls)
         ta.g = c->genome.as<uint8_t>(); ta.rec_off = rt.rec_off; ta.name_off = rt.name_off; ta.names = rt.names; ta.n_rec = nr;
         ta.paired = paired; ta.tb = c->dtb; ta.key = c->key; ta.slot = slot; ta.flags = c->flags.as<uint32_t>();
+        if (tref) {                                                                // the reference's table, made as RecTable is: lengths (nf), name offsets (nf + 1), names, 16 bytes of slack
+            const uint32_t nf = (uint32_t)c->lift.ref_lens.size(); std::vector<uint32_t> noff(nf + 1, 0); std::string text;
+            for (uint32_t r = 0; r < nf; ++r) { text += c->lift.ref_names[r]; noff[r + 1] = (uint32_t)text.size(); }
+            const size_t o_name = (size_t)nf * 8, o_text = o_name + (size_t)(nf + 1) * 4; std::vector<uint8_t> blob(o_text + text.size() + 16, 0);
+            memcpy(blob.data(), c->lift.ref_lens.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nf + 1) * 4); memcpy(blob.data() + o_text, text.data(), text.size());
+            upload(c->t_refs, blob, s); HIP_OK(hipStreamSynchronize(s));          // (the host blob goes)
+            const uint8_t* tb = c->t_refs.as<uint8_t>();
+            ta.segs = c->d_lift.as<LiftSeg>(); ta.n_seg = (uint32_t)c->lift.segs.size(); ta.ref_len = (const uint64_t*)tb; ta.n_ref = nf;
+            ta.ref_name_off = (const uint32_t*)(tb + o_name); ta.ref_names = (const char*)(tb + o_text);
+        }
     }
     void depth_open() {
         // the kernel's record table (record starts, first bins) and this call's counters, zeroed on the ctx stream
@@ -352,11 +363,11 @@ struct Yield {               // the state of one do_yield call
     void truth_batch(Batch& b) {
         // the batch's SAM: sizing pass + 64-bit offsets, the total to the host (it sizes the output), emit pass.  Before ev_free: the
         // passes read the batch's indel events and record offsets
-        static const uint32_t bam_lds = seam_env("SCS_TEST_TRUTH_LDS") ? (uint32_t)atoi(seam_env("SCS_TEST_TRUTH_LDS")) : 0u;   // tests: the BAM emit pass cuts its runs
+        static const uint32_t bam_lds = seam_env("SCS_TEST_TRUTH_LDS") ? (uint32_t)atoi(seam_env("SCS_TEST_TRUTH_LDS")) : 0u;   // tests: the BAM and the reference SAM's emit passes cut their runs
         const uint32_t np = b.np; const uint64_t fq_bytes = b.n.bytes[0] + b.n.bytes[1];
         ta.pairs = b.pr; ta.np = np; ta.ev_hdr = b.B->ev_hdr; ta.ev_dat = b.B->ev_dat; ta.off1 = b.B->off[0]; ta.off2 = b.B->off[1]; ta.fq1 = b.out[0]; ta.fq2 = b.out[1];
         c->tm[TM_TRUTH].begin(s);
-        if (bam) launch_truth_bam_size(s, ta, c->t_sizes.as<uint32_t>()); else launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
+        if (bam) launch_truth_bam_size(s, ta, c->t_sizes.as<uint32_t>()); else if (tref) launch_truth_ref_size(s, ta, c->t_sizes.as<uint32_t>()); else launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
         exclusive_scan_u32_to_u64(s, c->t_sizes.as<uint32_t>(), c->t_offs.as<uint64_t>(), np, c->t_scan.p, c->t_scan.cap);
         HIP_OK(hipMemcpyAsync(c->h_t, c->t_offs.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, s)); HIP_OK(hipEventRecord(c->ev_t, s));
         c->tm[TM_TRUTH].end(s);
@@ -366,7 +377,8 @@ struct Yield {               // the state of one do_yield call
         reserve_slot(&to, 1, &need, &room, b.dsl, false);
         c->tm[TM_TRUTH].begin(s);
         if (!bam) {
-            launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(fq_bytes, np), to.as<char>());
+            if (tref) launch_truth_ref_emit(s, ta, c->t_offs.as<uint64_t>(), truth_ref_pairs_per_block(fq_bytes, np), bam_lds, to.as<char>());
+            else launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(fq_bytes, np), to.as<char>());
             b.t_text = to.as<char>(); b.t_n = t_n; truth_fd.total += t_n;
         } else if (t_n) {
             // the batch's records, then BGZF over them where they lie (the FASTQ blocks' kernels); ship reads n[2] from h_z[dsl][2], behind ev_z
@@ -508,10 +520,20 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
 
 void truth_check(scs_ctx* c, bool device, int writers) {
     if (c->truth_path.empty()) return;
-    const std::string fn = c->truth_bam ? "scs_set_truth_bam" : "scs_set_truth_sam", what = (c->truth_bam ? "truth BAM (" : "truth SAM (") + fn + ")";
+    const std::string fn = c->truth_bam ? "scs_set_truth_bam" : c->truth_ref ? "scs_set_truth_ref_sam" : "scs_set_truth_sam",
+                      what = (c->truth_bam ? "truth BAM (" : c->truth_ref ? "truth SAM on the reference (" : "truth SAM (") + fn + ")";
     if (device) throw ScsError(SCS_EINVAL, what + ": not available with scs_yield_reads_device; turn it off with " + fn + "(ctx, NULL)");
     if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, what + ": not available for a sharded job (shard_count > 1)");
     if (writers > 1) throw ScsError(SCS_EINVAL, what + ": needs writers <= 1 (part files are made out of record order)");
+    if (c->truth_ref && !c->have_lift) throw ScsError(SCS_EINVAL, what + ": the staged genome has no lift table; stage it with scs_simuvars, or read its table with scs_load_lift after staging");
+}
+
+void truth_ref_release(scs_ctx* c) {
+    (void)hipStreamSynchronize(c->stream); if (c->copy_stream.s) (void)hipStreamSynchronize(c->copy_stream);   // nothing may still read them
+    c->t_sizes.release(); c->t_offs.release(); c->t_scan.release(); c->t_out[0].release(); c->t_out[1].release(); c->t_recs.release(); c->t_refs.release();
+    c->h_t.release(); c->ev_t.release();
+    c->tm[TM_TRUTH].ev.clear(); c->tm[TM_TRUTH].used = 0; c->tm[TM_TRUTH].reset();
+    if (c->pipe) for (auto& sl : c->pipe->slots) sl.h[2].release();                // (no writer runs between two yield calls)
 }
 
 void depth_check(scs_ctx* c) {
