@@ -468,6 +468,59 @@ int         scs_artefact_probe(const uint64_t* amp_start, const uint32_t* amp_le
                                const uint32_t* ed_amp, const uint64_t* ed_x, const uint8_t* ed_alt, uint64_t n_ed,
                                const uint64_t* rec_len, const char* const* rec_names, uint32_t n_rec, const char* genome, uint64_t genome_len,
                                uint32_t min_reads, int flags, char* out, size_t cap, size_t* n_out);
+/* ---- artefact table on the ORIGINAL REFERENCE: the same artefacts where a caller's VCF has them, made on the GPU -------------
+ * The table above is keyed by staged haplotype record.  This one is keyed by the reference the lift table (scs_simuvars,
+ * scs_load_lift) maps the staged records to, so that a caller's VCF can be intersected with it.  X = the index of a reference
+ * base among the reference records of the lift table, concatenated in table order.
+ *   entry  a (full amplicon, staged index g) pair with an edit -- the edits of the tables above.  With g in an R segment it belongs
+ *          to the SITE (X(g), REF, ALT); with g in an I segment (inserted sequence) it has no reference coordinate: it is counted
+ *          in unlifted[0] (entries) and unlifted[1] (their amplicons' read numbers) and makes no line.
+ *   REF    the base of the staged haplotype at g: the template the polymerase misread.  It is part of the site's identity: where a
+ *          heterozygous substitution was planted the two haplotypes hold different bases at one reference position, and one POS
+ *          may carry lines with different REF.  It differs from the reference FASTA's base exactly there.
+ *   piece  the part of a full amplicon's interval that lies in one R segment, as a reference interval [X0, X1): one per R segment
+ *          the amplicon touches, none for an amplicon wholly in inserted sequence.  Two pieces of one amplicon may overlap on the
+ *          reference (an amplicon longer than a tandem copy unit); they count separately.
+ *   NA / NR  the site's entries and the sum of their amplicons' read numbers;
+ *   TA / TR  the pieces, of any haplotype record and copy, with X0 <= X < X1, and the sum of their amplicons' read numbers.
+ * So 1 <= NA, and over the lines of one position sum(NA) <= TA and sum(NR) <= TR; NR / TR is the artefact's expected allele
+ * fraction among the reads that align to the reference position.  The counters are exact and do not depend on slab, chunk or LDS
+ * sizes.  The sites come in ascending (reference record in table order, coordinate, REF A < C < G < T < N, ALT A < C < G < T), each
+ * once; min_reads keeps the sites with NR >= min_reads.
+ * Both calls need a lift table, scs_allocate_reads to have run and an unsharded ctx (SCS_EINVAL otherwise; the message names the
+ * missing step).  An amplicon that cannot be placed, a walk that leaves the table or its record's segments, a segment that lifts
+ * outside its reference record, counts that contradict each other or a line the two passes size differently fail the call with
+ * SCS_EOVERFLOW ("artefact table" / "artefact table on the reference"), never a wrong line.  The reference is worked in slabs of
+ * 2^28 reference indices; every buffer, stream and event of the call is released when it returns, on every way out.  A reference
+ * of 2^58 bases or more is refused (SCS_EOVERFLOW).
+ * scs_write_artefacts_ref: VCF 4.2, made on the GPU: ##fileformat=VCFv4.2, ##source=scssim, ##scssim_coordinates=reference,
+ * ##scssim_REF=<what REF is>, ##scssim_unlifted=<entries=E,reads=R>, one ##contig=<ID=NAME,length=LEN> per REFERENCE record of the
+ * lift table in its order, the four ##INFO lines, the #CHROM line, then per site NAME, POS (reference coordinate + 1), ".", REF,
+ * ALT, ".", ".", "NA=..;TA=..;NR=..;TR=..".  flags: 1 = BGZF exactly as scs_write_artefacts; any other bit is SCS_EINVAL.  A job
+ * without a site writes the header.  *sites / *bytes / unlifted (each may be NULL) receive the sites written, the file's size and
+ * the two unlifted totals.  SCS_EIO: the file cannot be opened or written; the ctx stays usable.
+ * scs_artefact_ref_sites: the binary form, as scs_artefact_sites (ref_rec: the reference record; the cap / SCS_EOVERFLOW protocol
+ * is the same); unlifted may be NULL.
+ * scs_artefact_ref_kernel_time: event pairs, milliseconds and sites of the last scs_write_artefacts_ref call's kernels. */
+int         scs_write_artefacts_ref(scs_ctx* ctx, const char* path, int flags, uint32_t min_reads, uint64_t* sites, uint64_t* bytes, uint64_t unlifted[2]);
+int         scs_artefact_ref_sites(scs_ctx* ctx, uint32_t min_reads, uint32_t* ref_rec, uint64_t* pos, uint8_t* ref, uint8_t* alt, uint32_t* na, uint32_t* ta,
+                                   uint64_t* nr, uint64_t* tr, uint64_t cap, uint64_t* n, uint64_t unlifted[2]);
+int         scs_artefact_ref_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+/* Host-only test seam of that table (no GPU, no ctx): the table's body through the functions its kernels run (the segment cursor,
+ * the pieces, key packing, run heads, the cover count by bisection, the line formatter under a counting and a writing sink), slab
+ * by slab as the device works it, with std::sort where the device has the radix sort.  The amplicons and edit entries as for
+ * scs_artefact_probe (staged indices; the entries in any order), the staged records' lengths and bases, the lift table as five
+ * arrays (scs_lift_segments' layout), the reference records' lengths and names.  slab: reference indices per slab (0: 2^28).
+ * flags & 1: the header goes in front.  unlifted / lift_err may be NULL.  SCS_EINVAL: an amplicon off its record, an edit outside
+ * its amplicon, twice at one index or with an alternate base above 3, records that do not add up to the genome, a reference of 2^58
+ * bases, or a walk that gives up (*lift_err: 1 the amplicon, 2 the table does not tile under it, 3 a segment past its reference
+ * record); SCS_EOVERFLOW: cap too small. */
+int         scs_artefact_ref_probe(const uint64_t* amp_start, const uint32_t* amp_len, const uint32_t* amp_reads, uint64_t n_amp,
+                                   const uint32_t* ed_amp, const uint64_t* ed_x, const uint8_t* ed_alt, uint64_t n_ed,
+                                   const uint64_t* hap_len, uint32_t n_hap, const char* genome, uint64_t genome_len,
+                                   const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                                   const uint64_t* ref_len, const char* const* ref_names, uint32_t n_ref,
+                                   uint32_t min_reads, uint64_t slab, int flags, char* out, size_t cap, size_t* n_out, uint64_t unlifted[2], int* lift_err);
 /* ---- site support: what the reads of a yield call show at the artefact sites, counted on the GPU ----------------------------
  * The artefact table's NR / TR is the EXPECTED allele fraction; these counters are the OBSERVED one, after fragment sampling,
  * sequencing errors, indels and trimming.  scs_set_site_support(ctx, 1, min_reads): every later yield call first makes the site

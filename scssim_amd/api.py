@@ -594,6 +594,46 @@ def artefact_probe(starts, lens, reads, edits, rec_lens, rec_names, genome, min_
     return out.raw[:n.value].decode()
 
 
+def artefact_ref_probe(starts, lens, reads, edits, hap_lens, genome, table, ref_lens, ref_names, min_reads=0, slab=0, header=False):
+    """Host-only: the body of the artefact table on the original reference (header=True: behind its header) through the functions its
+    kernels run, slab by slab.  starts / lens / reads: the full amplicons' global staged start, length and read number; edits =
+    [(amplicon, global staged index, alt code 0..3), ...] in any order; hap_lens: the staged records; genome = their bases,
+    concatenated; table: a LiftTable (or any object with its five arrays); ref_lens / ref_names: the reference records; slab:
+    reference indices per slab (0: 2^28).  Returns (text, (unlifted entries, unlifted reads)).  A refused input raises ScsError
+    (SCS_EINVAL) whose .lift_err says why a walk gave up (0: it was not a walk)."""
+    import numpy as np
+    L = load_library()
+    L.scs_artefact_ref_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint32,
+                                         C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint64, C.c_int,
+                                         C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int)]
+    genome = genome.encode() if isinstance(genome, str) else bytes(genome)
+    n_amp, n_ed = len(starts), len(edits)
+    a_s, a_l, a_r = (np.ascontiguousarray(list(starts) + [0], np.uint64), np.ascontiguousarray(list(lens) + [0], np.uint32), np.ascontiguousarray(list(reads) + [0], np.uint32))
+    e_a = np.ascontiguousarray([e[0] for e in edits] + [0], np.uint32)
+    e_x = np.ascontiguousarray([e[1] for e in edits] + [0], np.uint64)
+    e_b = np.ascontiguousarray([e[2] for e in edits] + [0], np.uint8)
+    h_l = np.ascontiguousarray(list(hap_lens), np.uint64)
+    r_l = np.ascontiguousarray(list(ref_lens), np.uint64)
+    seg = [np.ascontiguousarray(getattr(table, k), t) for k, t in (("hap_off", np.uint64), ("len", np.uint64), ("ref_pos", np.uint64), ("ref_rec", np.uint32), ("kind", np.uint32))]
+    names = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
+    unl = np.zeros(2, np.uint64)
+    args = [a_s.ctypes.data, a_l.ctypes.data, a_r.ctypes.data, n_amp, e_a.ctypes.data, e_x.ctypes.data, e_b.ctypes.data, n_ed,
+            h_l.ctypes.data, len(h_l), genome, len(genome)] + [x.ctypes.data for x in seg] + [len(seg[0]),
+            r_l.ctypes.data, names, len(ref_names), int(min_reads), int(slab), 1 if header else 0]
+    n, le = C.c_size_t(), C.c_int()
+    rc = L.scs_artefact_ref_probe(*args, None, 0, C.byref(n), unl.ctypes.data, C.byref(le))
+    if rc:
+        e = ScsError(rc, "scs_artefact_ref_probe: " + ("an amplicon cannot be lifted (%d)" % le.value if le.value else "an amplicon off its record, an edit that is none of its amplicon, or tables that do not fit each other"))
+        e.lift_err = le.value
+        raise e
+    out = C.create_string_buffer(max(1, n.value))
+    rc = L.scs_artefact_ref_probe(*args, out, n.value, C.byref(n), unl.ctypes.data, C.byref(le))
+    if rc:
+        raise ScsError(rc, "scs_artefact_ref_probe")
+    return out.raw[:n.value].decode(), (int(unl[0]), int(unl[1]))
+
+
 def fasta_probe(path):
     """Host-only: (names, total bases, FNV-1a checksum of the upper-cased sequence) as the library stages the file."""
     L = load_library()
@@ -930,6 +970,40 @@ class GenReads:
         self._L.scs_artefact_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
         self._ck(self._L.scs_artefact_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def write_artefacts_ref(self, path, bgzf=False, min_reads=0):
+        """The amplification's artefacts by site of the ORIGINAL REFERENCE as a sorted VCF made on the GPU, after allocate_reads; needs
+        a lift table (simuvars, load_lift).  Per (reference record, coordinate, the template's base, alternate base) NA / NR (the edit
+        entries that lift to the site, their amplicons' reads) and TA / TR (the pieces of amplicons, of every haplotype and copy,
+        that cover it, and theirs).  Returns dict(sites=, bytes=, unlifted_entries=, unlifted_reads=)."""
+        self._L.scs_write_artefacts_ref.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        n, b, u = C.c_uint64(), C.c_uint64(), (C.c_uint64 * 2)()
+        self._ck(self._L.scs_write_artefacts_ref(self._ctx, os.fsencode(path), 1 if bgzf else 0, int(min_reads), C.byref(n), C.byref(b), u))
+        return dict(sites=n.value, bytes=b.value, unlifted_entries=u[0], unlifted_reads=u[1])
+
+    def artefact_ref_sites(self, min_reads=0):
+        """The same table as a dict of numpy arrays, one entry per site in file order: ref_rec (reference record of the lift table), pos
+        (0-based reference coordinate), ref (code 0..4), alt (0..3), na, ta, nr, tr; and unlifted = (entries, reads)."""
+        np = self._np
+        fn = self._L.scs_artefact_ref_sites
+        fn.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        n, u = C.c_uint64(), (C.c_uint64 * 2)()
+        rc = fn(self._ctx, int(min_reads), *([None] * 8), 0, C.byref(n), u)
+        if rc and not (rc == SCS_EOVERFLOW and n.value):
+            self._ck(rc)
+        a = dict(ref_rec=np.zeros(n.value, np.uint32), pos=np.zeros(n.value, np.uint64), ref=np.zeros(n.value, np.uint8), alt=np.zeros(n.value, np.uint8),
+                 na=np.zeros(n.value, np.uint32), ta=np.zeros(n.value, np.uint32), nr=np.zeros(n.value, np.uint64), tr=np.zeros(n.value, np.uint64))
+        if n.value:
+            self._ck(fn(self._ctx, int(min_reads), *[a[k].ctypes.data for k in ("ref_rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")], n.value, C.byref(n), u))
+        a["unlifted"] = (int(u[0]), int(u[1]))
+        return a
+
+    def artefact_ref_kernel_time(self):
+        """Event pairs, milliseconds and sites of the last write_artefacts_ref call's kernels (the sorts and scans included)."""
+        self._L.scs_artefact_ref_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(self._L.scs_artefact_ref_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
         return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def set_site_support(self, on, min_reads=0):

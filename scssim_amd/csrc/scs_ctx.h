@@ -284,6 +284,7 @@ struct scs_ctx {
     DevBuf sp_sites, sp_site_pos, sp_pos, sp_cnt, sp_tab;
     KernelTimer tm_support{"k_support"};                  // the last yield call's k_support launches (scs_site_support_kernel_time; not one of tm[])
     KernelTimer tm_site{"k_sites"};                       // the last scs_write_artefacts call's kernels (scs_artefact_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
+    KernelTimer tm_site_ref{"k_sites_ref"};               // the last scs_write_artefacts_ref call's kernels (scs_artefact_ref_kernel_time); the call's buffers live and die with it (scs_sites_ref.cpp)
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)

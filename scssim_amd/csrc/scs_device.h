@@ -330,6 +330,16 @@ void launch_site_reduce(hipStream_t s, const SiteArgs& t, SiteRec* recs, uint32_
 void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out, const uint32_t* site_pos = nullptr, const uint32_t* counts = nullptr);
 void launch_site_compact(hipStream_t s, const SiteRec* recs, const uint32_t* keep, const uint32_t* pos, uint64_t n, SiteRec* out);
 
+// ---- artefact table on the original reference (scs_k_sites_ref.hip; scs_write_artefacts_ref / scs_artefact_ref_sites; scs_site_ref.h,
+// DESIGN.md section 18): the same entries lifted through the lift table and grouped by REFERENCE site, a slab of reference indices at
+// a time.  The sorts, the check, the emit pass and the compaction are the artefact table's above; SiteArgs then names the reference
+// records.  FLAG_LIFT: a walk that leaves the table, or a segment outside its reference record
+struct SiteRefView;
+void launch_site_ref_count(hipStream_t s, const AmpArgs& a, const SiteRefView& v, uint64_t slab, uint32_t n_slabs, unsigned long long* cnt);   // cnt[2 k] += entries of slab k, cnt[2 k + 1] += pieces that overlap it; cnt[2 n_slabs ..]: the unlifted entries and their reads
+void launch_site_ref_fill(hipStream_t s, const AmpArgs& a, const SiteRefView& v, uint64_t x0, uint64_t x1, unsigned long long* cur, uint64_t cap_e, uint64_t cap_p,
+                          uint64_t* keys, uint32_t* kreads, uint64_t* starts, uint64_t* ends, uint32_t* preads);       // appends the slab [x0, x1)'s entries and pieces behind cur[0] / cur[1]
+void launch_site_ref_reduce(hipStream_t s, const SiteArgs& t, SiteRec* recs, uint32_t* sizes, uint32_t* keep);         // launch_site_reduce over lifted keys
+
 // ---- site support (scs_k_support.hip; scs_set_site_support): per batch, what its reads show at the artefact
 // sites' coordinates -- six counters per listed position (A, C, G, T, other, deleted), summed per workgroup in an LDS table of `slots`
 // entries (a power of two <= SUPPORT_LDS_SLOTS; 0: every add goes to memory)

@@ -1,9 +1,11 @@
-// scs_sitejob.h -- private to the host files of the artefact table (scs_sites.cpp) and of the site support table (scs_support.cpp),
-// which is the same table with the reads' counters: one call's pass over the amplicons slab by slab (SiteJob) and what turns a
+// scs_sitejob.h -- private to the host files of the artefact table (scs_sites.cpp), of the site support table (scs_support.cpp),
+// which is the same table with the reads' counters, and of the artefact table on the original reference (scs_sites_ref.cpp), which
+// is the same scheme over the reference axis: one call's pass over the amplicons slab by slab (SiteJob) and what turns a
 // run of sites into bytes of a file (SiteOut).  Every buffer, stream and event belongs to the struct that holds it and goes with it.
 #pragma once
 #include "scs_textout.h"
 #include "scs_site.h"
+#include "scs_site_ref.h"
 
 namespace scs {
 
@@ -68,17 +70,22 @@ struct SiteOut {
 };
 
 // One call's work: the kernels' arguments over the ctx's tables, the per-slab counts, and everything the call allocates.  Its
-// destructor ends every way out of the call: both streams drained; the members then release themselves
+// destructor ends every way out of the call: both streams drained; the members then release themselves.
+// on_ref (scs_sites_ref.cpp): the slabs are slabs of REFERENCE indices, the counting, fill and reduce passes are
+// scs_k_sites_ref.hip's over the lift table (v), `amplicons` reads `pieces of amplicons`, t names the reference records, and the
+// counting pass also finds the two unlifted totals and is followed by a check of the flags.  Everything else is one code
 struct SiteJob {
-    scs_ctx* const c; const hipStream_t s; KernelTimer idle{"k_sites"}; KernelTimer& tm; AmpArgs a{}; SiteArgs t{};   // tm: the ctx's timer (scs_write_artefacts), or one that is off
-    uint32_t chunk = kSiteChunk, min_reads = 0; uint64_t slab = kSiteSlab, bases = 0; uint32_t n_slabs = 0;
-    std::vector<uint64_t> cnt;                             // [2 k]: edit entries of slab k, [2 k + 1]: amplicons that overlap it
+    scs_ctx* const c; const hipStream_t s; const bool on_ref; const char* const what; KernelTimer idle{"k_sites"}; KernelTimer& tm; AmpArgs a{}; SiteArgs t{};   // tm: the ctx's timer (scs_write_artefacts / _ref), or one that is off
+    uint32_t chunk = kSiteChunk, min_reads = 0; uint64_t slab = kSiteSlab, bases = 0; uint32_t n_slabs = 0;   // bases: of the axis the slabs cut
+    std::vector<uint64_t> cnt;                             // [2 k]: edit entries of slab k, [2 k + 1]: amplicons (pieces) that overlap it; on_ref: behind them the two unlifted totals
+    SiteRefView v{}; DevBuf ref_tab; uint64_t unlifted[2] = {0, 0};   // on_ref: the walk's view of the lift table; the reference records' starts, name offsets and names
     uint64_t max_e = 0, max_a = 0; size_t sort_bytes = 0, scan_bytes = 0;
     Event ev_n; RecTable rt; SiteOut em;                   // em: the file's bytes (scs_write_artefacts)
     DevBuf d_cnt, cur, keys[2], kreads[2], starts[2], ends[2], areads[3], ps_start, ps_end, sort_tmp, scan_tmp, site_recs, sizes, offs, keep, keep_pos, packed;
     Pinned<uint64_t> h_n;
 
-    SiteJob(scs_ctx* c_, uint32_t min_reads_, bool timed) : c(c_), s(c_->stream), tm(timed ? c_->tm_site : idle), min_reads(min_reads_) {
+    SiteJob(scs_ctx* c_, uint32_t min_reads_, bool timed, bool on_ref_ = false)
+        : c(c_), s(c_->stream), on_ref(on_ref_), what(on_ref_ ? "artefact table on the reference" : "artefact table"), tm(timed ? (on_ref_ ? c_->tm_site_ref : c_->tm_site) : idle), min_reads(min_reads_) {
         idle.on = false;
         if (seam_env("SCS_TEST_AMP_CHUNK")) chunk = (uint32_t)std::max(1L, std::min(atol(seam_env("SCS_TEST_AMP_CHUNK")), 1L << 30));     // tests: chunk edges
         if (seam_env("SCS_TEST_SITE_SLAB")) slab = (uint64_t)std::max(1L, std::min(atol(seam_env("SCS_TEST_SITE_SLAB")), 1L << 40));      // tests: sites and amplicons on both sides of slab borders
@@ -90,14 +97,33 @@ struct SiteJob {
         a.flags = c->flags.as<uint32_t>();
         t.g = a.g; t.rec_off = a.rec_off; t.name_off = a.name_off; t.names = a.names; t.n_rec = nr; t.min_reads = min_reads; t.flags = a.flags;
         if (bases >> 60) throw ScsError(SCS_EOVERFLOW, "artefact table: the genome exceeds 2^60 bases");
-        const uint64_t ns = nr && c->fulls.n ? (bases + slab - 1) / slab : 0;
-        if (ns > (1u << 24)) throw ScsError(SCS_EINVAL, "artefact table: more than 2^24 slabs (SCS_TEST_SITE_SLAB too small for this genome)");
+        if (on_ref) reference();
+        const uint64_t ns = t.n_rec && c->fulls.n && (!on_ref || v.n_seg) ? (bases + slab - 1) / slab : 0;
+        if (ns > (1u << 24)) throw ScsError(SCS_EINVAL, std::string(what) + ": more than 2^24 slabs (SCS_TEST_SITE_SLAB too small for this genome)");
         n_slabs = (uint32_t)ns;
         count();
     }
     ~SiteJob() {
         (void)hipStreamSynchronize(s); if (em.copy.s) (void)hipStreamSynchronize(em.copy);
         tm.ev.clear(); tm.used = 0;                        // (the timer's events were this call's too; its sums stay)
+    }
+
+    // on_ref: the reference records as the kernels read them -- starts (nf + 1), name offsets (nf + 1), names, 16 bytes of slack -- take
+    // the staged records' place in t, and the slabs cut the reference
+    void reference() {
+        const LiftTable& L = c->lift; const uint32_t nf = (uint32_t)L.ref_lens.size();
+        std::vector<uint64_t> roff(nf + 1, 0); std::vector<uint32_t> noff(nf + 1, 0); std::string text;
+        for (uint32_t r = 0; r < nf; ++r) {
+            roff[r + 1] = roff[r] + L.ref_lens[r]; text += L.ref_names[r]; noff[r + 1] = (uint32_t)text.size();
+            if ((L.ref_lens[r] >> 58) || (roff[r + 1] >> 58)) throw ScsError(SCS_EOVERFLOW, "artefact table on the reference: the reference exceeds 2^58 bases");
+        }
+        bases = roff[nf];
+        const size_t o_name = (size_t)(nf + 1) * 8, o_text = o_name + (size_t)(nf + 1) * 4; std::vector<uint8_t> blob(o_text + text.size() + 16, 0);
+        memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nf + 1) * 4); memcpy(blob.data() + o_text, text.data(), text.size());
+        upload(ref_tab, blob, s); HIP_OK(hipStreamSynchronize(s));                    // (the host blob goes)
+        const uint8_t* tb = ref_tab.as<uint8_t>();
+        v.segs = c->d_lift.as<LiftSeg>(); v.n_seg = (uint32_t)L.segs.size(); v.ref_off = (const uint64_t*)tb; v.n_ref = nf;
+        t.rec_off = v.ref_off; t.name_off = (const uint32_t*)(tb + o_name); t.names = (const char*)(tb + o_text); t.n_rec = nf;
     }
 
     template <class F> void chunks(F f) {                  // the amplicon list, a chunk at a time
@@ -107,17 +133,19 @@ struct SiteJob {
 
     // the one pass over all amplicons: every slab's counts in one round trip, and the call's buffers sized by the largest slab
     void count() {
-        cnt.assign((size_t)2 * n_slabs, 0);
+        cnt.assign((size_t)2 * n_slabs + (on_ref ? 2 : 0), 0);
         if (!n_slabs) return;
-        d_cnt.reserve((size_t)n_slabs * 16, s); HIP_OK(hipMemsetAsync(d_cnt.p, 0, (size_t)n_slabs * 16, s));
+        const size_t bytes = cnt.size() * 8;
+        d_cnt.reserve(bytes, s); HIP_OK(hipMemsetAsync(d_cnt.p, 0, bytes, s));
         tm.begin(s);
-        chunks([&] { launch_site_count(s, a, slab, n_slabs, d_cnt.as<unsigned long long>()); });
+        chunks([&] { if (on_ref) launch_site_ref_count(s, a, v, slab, n_slabs, d_cnt.as<unsigned long long>()); else launch_site_count(s, a, slab, n_slabs, d_cnt.as<unsigned long long>()); });
         tm.end(s);
-        HIP_OK(hipMemcpyAsync(cnt.data(), d_cnt.p, (size_t)n_slabs * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s));
-        { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("artefact table: counting pass failed: ") + hipGetErrorString(le)); }
+        HIP_OK(hipMemcpyAsync(cnt.data(), d_cnt.p, bytes, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s));
+        { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string(what) + ": counting pass failed: " + hipGetErrorString(le)); }
+        if (on_ref) { check_flags(c); unlifted[0] = cnt[(size_t)2 * n_slabs]; unlifted[1] = cnt[(size_t)2 * n_slabs + 1]; }   // a walk that failed is reported here, before anything is written
         for (uint32_t k = 0; k < n_slabs; ++k) if (cnt[2 * k]) { max_e = std::max(max_e, cnt[2 * k]); max_a = std::max(max_a, cnt[2 * k + 1]); }
         if (!max_e) return;
-        if (max_e > kSiteMaxEntries || max_a > kSiteMaxEntries) throw ScsError(SCS_EOVERFLOW, "artefact table: a slab holds more than 2^31 edit entries or amplicons");
+        if (max_e > kSiteMaxEntries || max_a > kSiteMaxEntries) throw ScsError(SCS_EOVERFLOW, std::string(what) + ": a slab holds more than 2^31 edit entries or amplicons");
         cur.reserve(16, s);
         for (int k = 0; k < 2; ++k) { keys[k].reserve((max_e + 1) * 8, s); kreads[k].reserve((max_e + 1) * 4, s); starts[k].reserve((max_a + 1) * 8, s); ends[k].reserve((max_a + 1) * 8, s); }
         for (int k = 0; k < 3; ++k) areads[k].reserve((max_a + 1) * 4, s);
@@ -139,10 +167,13 @@ struct SiteJob {
     // the two totals arrive in h_n[0] and h_n[1].  Returns the slab's edit entries
     uint64_t make(uint32_t k) {
         const uint64_t e = cnt[2 * k], m = cnt[2 * k + 1], x0 = (uint64_t)k * slab, x1 = std::min(bases, x0 + slab);
-        const unsigned kb = site_bits(bases, 2), ib = site_bits(bases, 0);
+        const unsigned kb = site_bits(bases, on_ref ? SITE_REF_KEY_BITS : 2u), ib = site_bits(bases, 0);
         HIP_OK(hipMemsetAsync(cur.p, 0, 16, s));
         tm.begin(s);
-        chunks([&] { launch_site_fill(s, a, x0, x1, cur.as<unsigned long long>(), e, m, keys[0].as<uint64_t>(), kreads[0].as<uint32_t>(), starts[0].as<uint64_t>(), ends[0].as<uint64_t>(), areads[0].as<uint32_t>()); });
+        chunks([&] {
+            if (on_ref) launch_site_ref_fill(s, a, v, x0, x1, cur.as<unsigned long long>(), e, m, keys[0].as<uint64_t>(), kreads[0].as<uint32_t>(), starts[0].as<uint64_t>(), ends[0].as<uint64_t>(), areads[0].as<uint32_t>());
+            else launch_site_fill(s, a, x0, x1, cur.as<unsigned long long>(), e, m, keys[0].as<uint64_t>(), kreads[0].as<uint32_t>(), starts[0].as<uint64_t>(), ends[0].as<uint64_t>(), areads[0].as<uint32_t>());
+        });
         launch_site_check(s, cur.as<unsigned long long>(), e, m, a.flags);
         launch_site_sort(s, keys[0].as<uint64_t>(), keys[1].as<uint64_t>(), kreads[0].as<uint32_t>(), kreads[1].as<uint32_t>(), e, kb, sort_tmp.p, sort_bytes);
         launch_site_sort(s, starts[0].as<uint64_t>(), starts[1].as<uint64_t>(), areads[0].as<uint32_t>(), areads[1].as<uint32_t>(), m, ib, sort_tmp.p, sort_bytes);
@@ -151,14 +182,15 @@ struct SiteJob {
         exclusive_scan_u32_to_u64(s, areads[2].as<uint32_t>(), ps_end.as<uint64_t>(), m, scan_tmp.p, scan_bytes);
         t.keys = keys[1].as<uint64_t>(); t.reads = kreads[1].as<uint32_t>(); t.n = e;
         t.starts = starts[1].as<uint64_t>(); t.ps_start = ps_start.as<uint64_t>(); t.ends = ends[1].as<uint64_t>(); t.ps_end = ps_end.as<uint64_t>(); t.m = m;
-        launch_site_reduce(s, t, site_recs.as<SiteRec>(), sizes.as<uint32_t>(), keep.as<uint32_t>());
+        if (on_ref) launch_site_ref_reduce(s, t, site_recs.as<SiteRec>(), sizes.as<uint32_t>(), keep.as<uint32_t>());
+        else launch_site_reduce(s, t, site_recs.as<SiteRec>(), sizes.as<uint32_t>(), keep.as<uint32_t>());
         exclusive_scan_u32_to_u64(s, sizes.as<uint32_t>(), offs.as<uint64_t>(), e, scan_tmp.p, scan_bytes);
         exclusive_scan_u32(s, keep.as<uint32_t>(), keep_pos.as<uint32_t>(), e, scan_tmp.p, scan_bytes);
         tm.end(s);
         HIP_OK(hipMemcpyAsync(h_n, offs.as<uint64_t>() + e, 8, hipMemcpyDeviceToHost, s));
         HIP_OK(hipMemcpyAsync(h_n + 1, keep_pos.as<uint32_t>() + e, 4, hipMemcpyDeviceToHost, s));
         HIP_OK(hipEventRecord(ev_n, s)); HIP_OK(hipEventSynchronize(ev_n));
-        { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("artefact table: a slab's passes failed: ") + hipGetErrorString(le)); }
+        { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string(what) + ": a slab's passes failed: " + hipGetErrorString(le)); }
         return e;
     }
 };
