@@ -933,12 +933,16 @@ class GenReads:
         self._ck(self._L.scs_write_amplicons(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n)))
         return n.value
 
+    def _kernel_time(self, symbol):
+        fn = getattr(self._L, symbol)
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
     def amplicon_kernel_time(self):
         """Event pairs, milliseconds and amplicons of the last write_amplicons call's kernels."""
-        self._L.scs_amplicon_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(self._L.scs_amplicon_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_amplicon_kernel_time")
 
     def write_artefacts(self, path, bgzf=False, min_reads=0):
         """The amplification's artefacts by genome site as a sorted VCF made on the GPU, after allocate_reads: per (record, coordinate,
@@ -949,28 +953,36 @@ class GenReads:
         self._ck(self._L.scs_write_artefacts(self._ctx, os.fsencode(path), 1 if bgzf else 0, int(min_reads), C.byref(n), C.byref(b)))
         return dict(sites=n.value, bytes=b.value)
 
+    _SITE_ARRAYS = dict(pos="uint64", ref="uint8", alt="uint8", na="uint32", ta="uint32", nr="uint64", tr="uint64")
+
+    def _sites_into_arrays(self, symbol, rec_key, head=(), counts=False, tail=()):
+        """A site table's two calls: ask for the number of sites, then fill numpy arrays of that size.  rec_key: what the record
+        array is called; head: the arguments between ctx and the arrays; counts: a [sites, 6] array behind the eight; tail: extra
+        out-parameters behind n."""
+        np = self._np
+        fn = getattr(self._L, symbol)
+        na = 9 if counts else 8
+        fn.argtypes = [C.c_void_p] + [C.c_uint32] * len(head) + [C.c_void_p] * na + [C.c_uint64, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_uint64)] * len(tail)
+        n = C.c_uint64()
+        rc = fn(self._ctx, *head, *([None] * na), 0, C.byref(n), *tail)
+        if rc and not (rc == SCS_EOVERFLOW and n.value):
+            self._ck(rc)
+        a = {rec_key: np.zeros(n.value, np.uint32)}
+        a.update((k, np.zeros(n.value, getattr(np, t))) for k, t in self._SITE_ARRAYS.items())
+        if counts:
+            a["counts"] = np.zeros((n.value, 6), np.uint32)
+        if n.value:
+            self._ck(fn(self._ctx, *head, *[x.ctypes.data for x in a.values()], n.value, C.byref(n), *tail))
+        return a
+
     def artefact_sites(self, min_reads=0):
         """The same table as a dict of numpy arrays, one entry per site in file order: rec (staged record), pos (0-based record
         coordinate), ref (code 0..4), alt (0..3), na, ta, nr, tr."""
-        np = self._np
-        fn = self._L.scs_artefact_sites
-        fn.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint64, C.POINTER(C.c_uint64)]
-        n = C.c_uint64()
-        rc = fn(self._ctx, int(min_reads), *([None] * 8), 0, C.byref(n))
-        if rc and not (rc == SCS_EOVERFLOW and n.value):
-            self._ck(rc)
-        a = dict(rec=np.zeros(n.value, np.uint32), pos=np.zeros(n.value, np.uint64), ref=np.zeros(n.value, np.uint8), alt=np.zeros(n.value, np.uint8),
-                 na=np.zeros(n.value, np.uint32), ta=np.zeros(n.value, np.uint32), nr=np.zeros(n.value, np.uint64), tr=np.zeros(n.value, np.uint64))
-        if n.value:
-            self._ck(fn(self._ctx, int(min_reads), *[a[k].ctypes.data for k in ("rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")], n.value, C.byref(n)))
-        return a
+        return self._sites_into_arrays("scs_artefact_sites", "rec", head=(int(min_reads),))
 
     def artefact_kernel_time(self):
         """Event pairs, milliseconds and sites of the last write_artefacts call's kernels (the sorts and scans included)."""
-        self._L.scs_artefact_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(self._L.scs_artefact_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_artefact_kernel_time")
 
     def write_artefacts_ref(self, path, bgzf=False, min_reads=0):
         """The amplification's artefacts by site of the ORIGINAL REFERENCE as a sorted VCF made on the GPU, after allocate_reads; needs
@@ -985,26 +997,14 @@ class GenReads:
     def artefact_ref_sites(self, min_reads=0):
         """The same table as a dict of numpy arrays, one entry per site in file order: ref_rec (reference record of the lift table), pos
         (0-based reference coordinate), ref (code 0..4), alt (0..3), na, ta, nr, tr; and unlifted = (entries, reads)."""
-        np = self._np
-        fn = self._L.scs_artefact_ref_sites
-        fn.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        n, u = C.c_uint64(), (C.c_uint64 * 2)()
-        rc = fn(self._ctx, int(min_reads), *([None] * 8), 0, C.byref(n), u)
-        if rc and not (rc == SCS_EOVERFLOW and n.value):
-            self._ck(rc)
-        a = dict(ref_rec=np.zeros(n.value, np.uint32), pos=np.zeros(n.value, np.uint64), ref=np.zeros(n.value, np.uint8), alt=np.zeros(n.value, np.uint8),
-                 na=np.zeros(n.value, np.uint32), ta=np.zeros(n.value, np.uint32), nr=np.zeros(n.value, np.uint64), tr=np.zeros(n.value, np.uint64))
-        if n.value:
-            self._ck(fn(self._ctx, int(min_reads), *[a[k].ctypes.data for k in ("ref_rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")], n.value, C.byref(n), u))
+        u = (C.c_uint64 * 2)()
+        a = self._sites_into_arrays("scs_artefact_ref_sites", "ref_rec", head=(int(min_reads),), tail=(u,))
         a["unlifted"] = (int(u[0]), int(u[1]))
         return a
 
     def artefact_ref_kernel_time(self):
         """Event pairs, milliseconds and sites of the last write_artefacts_ref call's kernels (the sorts and scans included)."""
-        self._L.scs_artefact_ref_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(self._L.scs_artefact_ref_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_artefact_ref_kernel_time")
 
     def set_site_support(self, on, min_reads=0):
         """Site support on / off: every later yield call counts, on the GPU, what its reads show at the coordinates of the artefact
@@ -1015,19 +1015,7 @@ class GenReads:
     def site_support(self):
         """The last yield call's sites and counters as a dict of numpy arrays, one entry per site in file order: artefact_sites' arrays
         and counts, uint32 [sites, 6]: reads that show A, C, G, T, another character, a deletion at the site's coordinate."""
-        np = self._np
-        fn = self._L.scs_site_support
-        fn.argtypes = [C.c_void_p] + [C.c_void_p] * 9 + [C.c_uint64, C.POINTER(C.c_uint64)]
-        n = C.c_uint64()
-        rc = fn(self._ctx, *([None] * 9), 0, C.byref(n))
-        if rc and not (rc == SCS_EOVERFLOW and n.value):
-            self._ck(rc)
-        a = dict(rec=np.zeros(n.value, np.uint32), pos=np.zeros(n.value, np.uint64), ref=np.zeros(n.value, np.uint8), alt=np.zeros(n.value, np.uint8),
-                 na=np.zeros(n.value, np.uint32), ta=np.zeros(n.value, np.uint32), nr=np.zeros(n.value, np.uint64), tr=np.zeros(n.value, np.uint64),
-                 counts=np.zeros((n.value, 6), np.uint32))
-        if n.value:
-            self._ck(fn(self._ctx, *[a[k].ctypes.data for k in ("rec", "pos", "ref", "alt", "na", "ta", "nr", "tr", "counts")], n.value, C.byref(n)))
-        return a
+        return self._sites_into_arrays("scs_site_support", "rec", counts=True)
 
     def write_site_support(self, path, bgzf=False):
         """The artefact VCF of the same min_reads with DP / AD / DL of the last yield call's reads at the end of every line, made on
@@ -1109,17 +1097,11 @@ class GenReads:
 
     def depth_ref_kernel_time(self):
         """Event pairs (one per batch), milliseconds and pairs of the last yield call's k_depth_lift launches."""
-        self._L.scs_depth_ref_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(self._L.scs_depth_ref_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_depth_ref_kernel_time")
 
     def site_support_kernel_time(self):
         """Event pairs (one per batch), milliseconds and pairs of the last yield call's k_support launches."""
-        self._L.scs_site_support_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(self._L.scs_site_support_kernel_time(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_site_support_kernel_time")
 
     def download_frags(self):
         """The fragments of create_frags: genome offset (records concatenated in staging order), length, strand (+1 / -1)."""

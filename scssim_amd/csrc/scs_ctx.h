@@ -21,6 +21,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -195,7 +196,11 @@ struct KernelTimer {         // HIP events on the ctx stream around the launches
     }
     void reset() { ms = 0; launches = 0; units = 0; used = 0; }
 };
-enum { TM_ERRSCAN, TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
+// One depth track of a ctx: the bin width (0: off -- no buffer of it exists, no code of it runs), the bins of its records, the
+// counters of the last yield call (planes of `bins` entries, zeroed on the ctx stream at the start of every call; valid: a call with
+// the track on has finished) and the kernel's tables
+struct DepthTrack { uint32_t width = 0; uint64_t bins = 0; bool valid = false; DevBuf cnt, tab; };
+enum { TM_ERRSCAN,TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
 struct SinkPipe;             // scs_sink.h
 struct SinkPipeDelete { void operator()(SinkPipe* p) const; };
@@ -260,18 +265,15 @@ struct scs_ctx {
     // truth SAM on the original reference (scs_set_truth_ref_sam): truth_path names a SAM whose records are
     // lifted through the lift table (d_lift); t_refs: the reference records' lengths, name offsets and names as the kernels read them
     bool truth_ref = false; DevBuf t_refs;
-    // depth track (scs_set_depth): the bin width (0: off -- no buffer below exists, no depth code runs), the counters of the last
-    // yield call (reads[n_bins] then bases[n_bins], zeroed on the ctx stream at the start of every call; depth_valid: a call with
-    // depth on has finished) and the kernel's record table (rec_off[nr + 1] then bin_off[nr + 1])
-    uint32_t depth_width = 0; uint64_t depth_bins = 0; bool depth_valid = false; DevBuf dp_cnt, dp_tab;
+    // depth track (scs_set_depth; scs_depth.cpp): counters reads[bins] then bases[bins]; tables rec_off[nr + 1] then bin_off[nr + 1]
+    DepthTrack depth;
     // lift table (scs_lift.cpp): the staged records as stretches of the original reference -- kept by scs_simuvars
     // or read by scs_load_lift, on the host and (d_lift: the segments) on the device; tied to the staged genome: staging another drops it.
-    // Depth by reference bin (scs_set_depth_ref): the bin width (0: off -- no buffer below exists, no code of it runs), the bins of the
-    // reference records, the counters (reads, bases, copies: n_bins + 1 entries each; the first two zeroed on the ctx stream at the start
-    // of every yield call, copies made once per layout: dref_copies) and the kernel's tables (staged record starts, reference lengths
-    // and first bins)
+    // Depth by reference bin (scs_set_depth_ref; scs_depth.cpp): the bins of the reference records; counters reads, bases, copies of
+    // bins + 1 entries each (the pseudo-bin last), copies made once per layout (dref_copies), not per call; tables: the staged record
+    // starts, the reference's lengths and first bins
     bool have_lift = false; LiftTable lift; DevBuf d_lift;
-    uint32_t dref_width = 0; uint64_t dref_bins = 0; bool dref_valid = false, dref_copies = false; DevBuf dr_cnt, dr_tab;
+    DepthTrack depth_ref; bool dref_copies = false;
     KernelTimer tm_depth_ref{"k_depth_lift"};             // the last yield call's k_depth_lift launches (scs_depth_ref_kernel_time; not one of tm[])
     // amplicon table (scs_amplicon_places / scs_write_amplicons; scs_amplicons.cpp): every buffer, stream and event of a call belongs to
     // its AmpJob and goes with it; nothing of the call stays here but the kernels' times
@@ -284,7 +286,7 @@ struct scs_ctx {
     DevBuf sp_sites, sp_site_pos, sp_pos, sp_cnt, sp_tab;
     KernelTimer tm_support{"k_support"};                  // the last yield call's k_support launches (scs_site_support_kernel_time; not one of tm[])
     KernelTimer tm_site{"k_sites"};                       // the last scs_write_artefacts call's kernels (scs_artefact_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
-    KernelTimer tm_site_ref{"k_sites_ref"};               // the last scs_write_artefacts_ref call's kernels (scs_artefact_ref_kernel_time); the call's buffers live and die with it (scs_sites_ref.cpp)
+    KernelTimer tm_site_ref{"k_sites_ref"};               // the last scs_write_artefacts_ref call's kernels (scs_artefact_ref_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
     ReadsSide reads_side;                                 // k_reads' two small class kernels run beside the big one on these (per ctx: two contexts on one device do not share events)
     Stream pre_stream; Event ev_pre[2], ev_free[2], ev_plan;   // the reads stage's pre-pass on its own stream, beside the previous batch's base pass
     hipStream_t mail_stream = nullptr;                                             // the stream of the last post (mail_wait watches it)
@@ -333,6 +335,8 @@ struct scs_ctx {
     }
     scs_stats st{};
     KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}, {"k_depth"}};
+    // the timers a yield call runs: reset at its start, collected at its end.  A new side output's timer is one more entry here
+    std::array<KernelTimer*, 6> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref}; }
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
@@ -388,18 +392,17 @@ void truth_check(scs_ctx* c, bool device, int writers);
 // the truth SAM on the reference is switched off: everything its yield calls made for it goes (the truth passes' buffers, which
 // the next truth output of any kind makes again)
 void truth_ref_release(scs_ctx* c);
-// depth track: refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the staged records' bins (SCS_EINVAL beyond DEPTH_MAX_BINS)
+// the depth tracks (scs_depth.cpp), both at once: depth_check refuses (SCS_EINVAL) a sharded or sliced ctx, and the reference track
+// without a lift table, at the yield call's entry; depth_yield_check the same and more than DEPTH_MAX_BINS bins, before the call's
+// GPU work.  depth_open, one track: the kernel's tables, this call's zeroed counters and (on_ref, once per layout) the copies
 void depth_check(scs_ctx* c);
-uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);
-// lift table and depth by reference bin (scs_lift.cpp): lift_install makes T the ctx's table (host and device), lift_drop forgets it
-// (every call that stages a genome); depth_ref_check refuses (SCS_EINVAL) a sharded or sliced ctx, and one without a table, at the yield call;
-// depth_ref_layout: the reference records' bins (SCS_EINVAL: no table, or beyond DEPTH_MAX_BINS); depth_ref_open: the kernel's
-// tables, this call's zeroed counters and (once per layout) the copies
+void depth_yield_check(scs_ctx* c);
+void depth_open(scs_ctx* c, bool on_ref);
+// lift table (scs_lift.cpp): lift_install makes T the ctx's table (host and device), lift_drop forgets it (every call that stages a
+// genome); need_lift refuses (SCS_EINVAL) in fn's name where there is none
 void lift_install(scs_ctx* c, LiftTable&& T);
 void lift_drop(scs_ctx* c);
-void depth_ref_check(scs_ctx* c);
-uint64_t depth_ref_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off);
-void depth_ref_open(scs_ctx* c);
+void need_lift(const scs_ctx* c, const char* fn);
 // site support (scs_support.cpp): refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the call's site table, positions and zeroed counters
 void support_check(scs_ctx* c);
 void support_open(scs_ctx* c);

@@ -2,10 +2,10 @@
 //
 // k_depth_lift: per bin of the ORIGINAL REFERENCE the reads and aligned bases of a batch, right after its base pass, from what
 // k_depth reads -- the pair records and the indel pass' events; no FASTQ text, no byte genome.  A thread per pair places its reads
-// (read_place), finds the segment of the leftmost aligned base by one bisection of the table and walks the truth CIGAR with a
+// (for_each_placed_read), finds the segment of the leftmost aligned base by one bisection of the table and walks the truth CIGAR with a
 // segment cursor (lift_read): every M run is cut at segment ends and reference bin boundaries; what lies in an inserted segment
 // goes to the pseudo-bin n_bins.  The table is small and read-only: plain loads that L2 keeps.  Aggregation is k_depth's
-// (DepthTable, scs_depth_table.h): an LDS table per workgroup, then one 64-bit atomic per used slot and counter; the pseudo-bin is
+// (DepthTable and depth_table_run, scs_depth_table.h): an LDS table per workgroup, then one 64-bit atomic per used slot and counter; the pseudo-bin is
 // an ordinary key.  The lanes diverge on the CIGAR walk and the segment cursor, as k_depth's do on the walk.
 // k_lift_copies: a workgroup per segment, its lanes over the reference bins the segment covers, one atomicAdd per (segment, bin).
 // k_lift_points: a thread per staged position, a bisection of the table, coalesced in and out.
@@ -19,43 +19,24 @@
 namespace scs {
 
 __device__ void depth_lift_pair(const LiftArgs& A, const LiftView& V, uint32_t pi, const DepthTable& T) {
-    const PairRec pr = A.pairs[pi];
-    if (pr.isz == 0) return;                               // hole: no FASTQ record
-    uint32_t ev[TRUTH_EVCAP];
-    for (uint32_t rd = 0; rd < (A.paired ? 2u : 1u); ++rd) {
-        TruthAln a; int n_out;
-        if (!read_place(A, pr, pi, rd, ev, a, n_out, (uint32_t)FLAG_LIFT)) continue;
-        uint32_t lo = 0, hi = A.n_rec;                     // the record: rec_off[lo] <= a.lo < rec_off[lo + 1]
-        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)A.rec_off[mid] <= a.lo) lo = mid; else hi = mid; }
+    for_each_placed_read(A, pi, (uint32_t)FLAG_LIFT, [&](const PairRec&, uint32_t, const TruthAln& a, int, uint32_t, int64_t r0, int64_t r1) {
         const uint32_t nb = (uint32_t)A.n_bins;            // (at most 2^27: the pseudo-bin is a uint32 key like the others)
-        const int err = lift_read(a, (int64_t)A.rec_off[lo], (int64_t)A.rec_off[lo + 1], V,
+        const int err = lift_read(a, r0, r1, V,
                                   [&](uint64_t bin) { if (bin <= nb) T.add((uint32_t)bin, 1u, 0u); else atomicOr(A.flags, (uint32_t)FLAG_LIFT); },
                                   [&](uint64_t bin, uint32_t n) { if (bin <= nb) T.add((uint32_t)bin, 0u, n); else atomicOr(A.flags, (uint32_t)FLAG_LIFT); });
         if (err) atomicOr(A.flags, (uint32_t)FLAG_LIFT);   // placed outside its record, off the table, or lifted outside the reference: the call fails
-    }
+    });
 }
 
 __global__ void __launch_bounds__(256) k_depth_lift(LiftArgs A) {
-    __shared__ uint32_t s_key[DEPTH_LDS_SLOTS], s_reads[DEPTH_LDS_SLOTS], s_bases[DEPTH_LDS_SLOTS];
-    for (uint32_t i = threadIdx.x; i < A.slots; i += 256u) { s_key[i] = DEPTH_EMPTY; s_reads[i] = 0u; s_bases[i] = 0u; }
-    __syncthreads();
     const uint32_t pi = blockIdx.x * 256u + threadIdx.x;
     const LiftView V{A.segs, A.n_seg, A.ref_len, A.ref_bin_off, A.n_ref, A.bin_width, A.n_bins};
-    if (pi < A.np) depth_lift_pair(A, V, pi, DepthTable{s_key, s_reads, s_bases, A.slots, A.reads, A.bases});   // (no lane leaves before the barriers)
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < A.slots; i += 256u) {
-        const uint32_t bin = s_key[i];
-        if (bin == DEPTH_EMPTY) continue;
-        if (s_reads[i]) atomicAdd(&A.reads[bin], (unsigned long long)s_reads[i]);
-        if (s_bases[i]) atomicAdd(&A.bases[bin], (unsigned long long)s_bases[i]);
-    }
+    depth_table_run(A.slots, A.reads, A.bases, [&](const DepthTable& T) { if (pi < A.np) depth_lift_pair(A, V, pi, T); });
 }
 
 void launch_depth_lift(hipStream_t s, const LiftArgs& a) {
     if (a.np == 0) return;
-    LiftArgs b = a;
-    b.slots = b.slots > DEPTH_LDS_SLOTS ? DEPTH_LDS_SLOTS : b.slots;
-    while (b.slots & (b.slots - 1u)) b.slots &= b.slots - 1u;                      // a power of two (the table's index mask), or 0
+    LiftArgs b = a; b.slots = table_slots(a.slots, DEPTH_LDS_SLOTS);
     hipLaunchKernelGGL(k_depth_lift, dim3(cdiv(a.np, 256)), dim3(256), 0, s, b);
     note_launch(hipGetLastError());
 }

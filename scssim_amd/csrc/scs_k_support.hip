@@ -3,7 +3,7 @@
 // summed over a batch's reads right after its base pass from what the device holds: the pair records, the indel pass' events and
 // the FASTQ text.
 //
-// k_support: a thread per pair places its reads (read_place: the truth passes' placement), finds their bases in the text (read_text)
+// k_support: a thread per pair places its reads (for_each_placed_read, scs_place.h: the truth passes' placement), finds their bases in the text (read_text)
 // and walks the truth CIGAR over the listed positions (support_read, scs_support.h).  Neighbouring pairs of the list are reads of
 // one amplicon, so the 256 pairs of a workgroup hit the same few positions: the workgroup first sums into an open-addressing table
 // in LDS (key = position index << 3 | class; one uint32 sum per slot, at most 512 reads each: no overflow) and then adds every used
@@ -43,19 +43,12 @@ struct SupportTable {
 };
 
 __device__ void support_pair(const SupportArgs& A, uint32_t pi, const SupportTable& T) {
-    const PairRec pr = A.pairs[pi];
-    if (pr.isz == 0) return;                               // hole: no FASTQ record
-    uint32_t ev[TRUTH_EVCAP];
-    for (uint32_t rd = 0; rd < (A.paired ? 2u : 1u); ++rd) {
-        TruthAln a; int n_out;
-        if (!read_place(A, pr, pi, rd, ev, a, n_out, (uint32_t)FLAG_SUPPORT)) continue;
-        uint32_t lo = 0, hi = A.n_rec;                     // the record: rec_off[lo] <= a.lo < rec_off[lo + 1]
-        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)A.rec_off[mid] <= a.lo) lo = mid; else hi = mid; }
-        if (a.lo < (int64_t)A.rec_off[lo] || a.hi >= (int64_t)A.rec_off[lo + 1]) { atomicOr(A.flags, (uint32_t)FLAG_SUPPORT); continue; }   // outside its record: the call fails
+    for_each_placed_read(A, pi, (uint32_t)FLAG_SUPPORT, [&](const PairRec& pr, uint32_t rd, const TruthAln& a, int n_out, uint32_t, int64_t r0, int64_t r1) {
+        if (a.lo < r0 || a.hi >= r1) { atomicOr(A.flags, (uint32_t)FLAG_SUPPORT); return; }   // outside its record: the call fails
         const char* rec; const char* s = read_text(A.off1, A.off2, A.fq1, A.fq2, A.paired, pr, pi, rd, &rec);
-        if (rec[0] != '@' || s[-1] != '\n' || s[n_out] != '\n') { atomicOr(A.flags, (uint32_t)FLAG_SUPPORT); continue; }   // the record is not where the offsets say
+        if (rec[0] != '@' || s[-1] != '\n' || s[n_out] != '\n') { atomicOr(A.flags, (uint32_t)FLAG_SUPPORT); return; }   // the record is not where the offsets say
         support_read(a, A.sp_pos, A.n_pos, [&](int i) { return s[i]; }, [&](uint64_t idx, uint32_t cls) { T.add((uint32_t)idx, cls); });
-    }
+    });
 }
 
 __global__ void __launch_bounds__(kSupportBlock) k_support(SupportArgs A) {
@@ -102,9 +95,7 @@ __global__ void __launch_bounds__(256) k_support_size(SiteArgs T, const SiteRec*
 
 void launch_support(hipStream_t s, const SupportArgs& a) {
     if (a.np == 0 || a.n_pos == 0) return;
-    SupportArgs b = a;
-    b.slots = b.slots > SUPPORT_LDS_SLOTS ? SUPPORT_LDS_SLOTS : b.slots;
-    while (b.slots & (b.slots - 1u)) b.slots &= b.slots - 1u;                      // rounded down to a power of two (the table's index mask), or 0
+    SupportArgs b = a; b.slots = table_slots(a.slots, SUPPORT_LDS_SLOTS);
     hipLaunchKernelGGL(k_support, dim3(cdiv(a.np, kSupportBlock)), dim3(kSupportBlock), 0, s, b);
     note_launch(hipGetLastError());
 }

@@ -186,6 +186,12 @@ __device__ __forceinline__ void block_add_u64(unsigned long long v, unsigned lon
 // 1.92 ms per pass at 600 Mb.  With the hardware's round-robin the eight XCDs work on ONE stretch of the genome at a time and share its
 // lines in the Infinity Cache; eight distant stretches at once cost more than the L2 hits bring.  profiles/r04_attach_ab_xcd.log)
 static inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
+// the slots a workgroup's LDS table is launched with: at most `max`, rounded down to a power of two (the table's index mask), or 0
+static inline uint32_t table_slots(uint32_t slots, uint32_t max) {
+    slots = slots > max ? max : slots;
+    while (slots & (slots - 1u)) slots &= slots - 1u;
+    return slots;
+}
 // launch errors are latched (scs_k_misc.hip) and surfaced by the pipeline at its next check (take_launch_error)
 void note_launch(hipError_t e);
 }  // namespace scs

@@ -1,7 +1,7 @@
-// scs_lift.cpp -- the lift table and the depth track by reference bin (include/scssim_hip.h: scs_write_lift, scs_load_lift,
-// scs_lift_info, scs_lift_segments, scs_lift_positions, scs_set_depth_ref ...).  The table itself -- built from
-// the simuvars plan, written, parsed -- is scs_lift.h's; here it becomes the ctx's (host vector + device copy), the ctx's entry
-// points run over it, and the host-only probes expose what they run.  The per-batch kernel is launched from scs_reads.cpp.
+// scs_lift.cpp -- the lift table (include/scssim_hip.h: scs_write_lift, scs_load_lift, scs_lift_info, scs_lift_segments,
+// scs_lift_positions).  The table itself -- built from the simuvars plan, written, parsed -- is scs_lift.h's;
+// here it becomes the ctx's (host vector + device copy), the ctx's entry points run over it, and the host-only probes expose what
+// they run.  The depth track over it is scs_depth.cpp's.
 #include "scs_textout.h"
 #include <cerrno>
 
@@ -10,7 +10,7 @@ namespace scs {
 void lift_drop(scs_ctx* c) {
     if (!c->have_lift && !c->d_lift.p) return;
     c->have_lift = false; c->lift.clear(); c->d_lift.release();
-    c->dref_valid = false; c->dref_copies = false; c->dref_bins = 0;
+    c->depth_ref.valid = false; c->dref_copies = false; c->depth_ref.bins = 0;   // (the reference track's layout was this table's)
 }
 void lift_install(scs_ctx* c, LiftTable&& T) {
     lift_drop(c);
@@ -21,46 +21,11 @@ void lift_install(scs_ctx* c, LiftTable&& T) {
     c->have_lift = true;
 }
 
-void depth_ref_check(scs_ctx* c) {
-    if (!c->dref_width) return;
-    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, "depth by reference bin (scs_set_depth_ref): not available for a sharded job (shard_count > 1); turn it off with scs_set_depth_ref(ctx, 0)");
-    if (!c->have_lift) throw ScsError(SCS_EINVAL, "depth by reference bin (scs_set_depth_ref): the staged genome has no lift table; stage it with scs_simuvars, or read its table with scs_load_lift after staging");
-}
-uint64_t depth_ref_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off) {
-    if (!c->have_lift) throw ScsError(SCS_EINVAL, "depth by reference bin (scs_set_depth_ref): the staged genome has no lift table (scs_simuvars, scs_load_lift)");
-    const size_t nr = c->lift.ref_lens.size(); uint64_t nb = 0; uint32_t min_w = 0;
-    if (bin_off) bin_off->assign(nr + 1, 0);
-    if (depth_layout(c->lift.ref_lens.data(), nr, c->dref_width, bin_off ? bin_off->data() : nullptr, &nb, &min_w)) return nb;
-    throw ScsError(SCS_EINVAL, "depth by reference bin (scs_set_depth_ref): bins of " + std::to_string(c->dref_width) + " bases give more than 2^27 bins for the reference; " +
-                   (min_w ? "the smallest bin width it admits is " + std::to_string(min_w) : std::string("no bin width below 2^32 is enough")));
-}
-void depth_ref_open(scs_ctx* c) {
-    const hipStream_t s = c->stream;
-    const size_t nr = c->recs.size(), nf = c->lift.ref_lens.size(); std::vector<uint64_t> boff;
-    const uint64_t nb = c->dref_bins = depth_ref_layout(c, &boff);
-    std::vector<uint64_t> tab = record_starts(c); tab.resize(nr + 1 + nf + nf + 1, 0);
-    std::copy(c->lift.ref_lens.begin(), c->lift.ref_lens.end(), tab.begin() + (long)(nr + 1));
-    std::copy(boff.begin(), boff.end(), tab.begin() + (long)(nr + 1 + nf));
-    upload(c->dr_tab, tab, s);
-    const size_t one = (size_t)(nb + 1) * 8;
-    c->dr_cnt.reserve(3 * one, s, c->dref_copies ? 3 * one : 0);                    // (a layout that stands keeps its size: nothing moves)
-    HIP_OK(hipMemsetAsync(c->dr_cnt.p, 0, (c->dref_copies ? 2 : 3) * one, s));
-    if (!c->dref_copies) {
-        const uint64_t* t = c->dr_tab.as<uint64_t>();
-        launch_lift_copies(s, c->d_lift.as<LiftSeg>(), (uint32_t)c->lift.segs.size(), t + nr + 1, t + nr + 1 + nf, (uint32_t)nf, c->dref_width, nb,
-                           c->dr_cnt.as<unsigned long long>() + 2 * (nb + 1), c->flags.as<uint32_t>());
-    }
-    HIP_OK(hipStreamSynchronize(s));                                               // (the host table goes)
-    if (!c->dref_copies) { check_flags(c); c->dref_copies = true; }
-}
-
-namespace {
 void need_lift(const scs_ctx* c, const char* fn) {
     if (!c->have_lift) throw ScsError(SCS_EINVAL, std::string(fn) + ": the staged genome has no lift table (scs_simuvars keeps one, scs_load_lift reads one)");
 }
-void need_dref(const scs_ctx* c, const char* fn) {
-    if (!c->dref_width || !c->dref_valid) throw ScsError(SCS_EINVAL, std::string(fn) + ": no yield call with the depth by reference bin on (scs_set_depth_ref) has finished");
-}
+
+namespace {
 // a table into a caller's arrays (any pointer may be NULL): SCS_EOVERFLOW when one is too small; names: the reference records'
 // then the staged records', each followed by a newline
 int export_table(const LiftTable& T, uint64_t* hap_off, uint64_t* len, uint64_t* ref_pos, uint32_t* ref_rec, uint32_t* kind, uint64_t seg_cap, uint64_t* n_seg,
@@ -152,66 +117,6 @@ int scs_lift_positions(scs_ctx* c, const uint32_t* rec, const uint64_t* pos, uin
         HIP_OK(hipMemcpyAsync(kind, d_k, n * 4, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s));
     });
 }
-
-// ---- depth by reference bin
-int scs_set_depth_ref(scs_ctx* c, uint32_t bin_width) {
-    return guarded(c, [&] {
-        if (bin_width == c->dref_width) return;
-        HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's counters go: nothing may still read them
-        c->dr_cnt.release(); c->dr_tab.release(); c->dref_valid = false; c->dref_copies = false; c->dref_bins = 0; c->dref_width = bin_width;
-        if (!bin_width) { c->tm_depth_ref.ev.clear(); c->tm_depth_ref.used = 0; c->tm_depth_ref.reset(); }
-    });
-}
-int scs_depth_ref_bins(const scs_ctx* c, uint64_t* n_bins, uint32_t* bin_width) {
-    if (!c) return SCS_EINVAL;
-    scs_ctx* m = const_cast<scs_ctx*>(c);                                          // (the error text is the only thing written)
-    try {
-        if (!c->dref_width) throw ScsError(SCS_EINVAL, "scs_depth_ref_bins: the depth by reference bin is off (scs_set_depth_ref)");
-        const uint64_t nb = depth_ref_layout(c, nullptr);
-        if (n_bins) *n_bins = nb; if (bin_width) *bin_width = c->dref_width;
-        return SCS_OK;
-    } catch (const ScsError& e) { m->err = e.what(); return e.code; }
-}
-int scs_depth_ref_record_bins(const scs_ctx* c, uint64_t* bin_off, uint64_t cap) {
-    if (!c || !bin_off) return SCS_EINVAL;
-    scs_ctx* m = const_cast<scs_ctx*>(c);
-    try {
-        if (!c->dref_width) throw ScsError(SCS_EINVAL, "scs_depth_ref_record_bins: the depth by reference bin is off (scs_set_depth_ref)");
-        std::vector<uint64_t> off; (void)depth_ref_layout(c, &off);
-        if (cap < off.size()) throw ScsError(SCS_EOVERFLOW, "scs_depth_ref_record_bins: reference records + 1 entries are needed");
-        std::copy(off.begin(), off.end(), bin_off);
-        return SCS_OK;
-    } catch (const ScsError& e) { m->err = e.what(); return e.code; }
-}
-int scs_download_depth_ref(scs_ctx* c, uint64_t* reads, uint64_t* bases, uint64_t* copies, uint64_t cap) {
-    return guarded(c, [&] {
-        need_dref(c, "scs_download_depth_ref");
-        const uint64_t n = c->dref_bins + 1;
-        if (cap < n) throw ScsError(SCS_EOVERFLOW, "scs_download_depth_ref: " + std::to_string(n) + " entries (the bins and the pseudo-bin), room for " + std::to_string(cap));
-        uint64_t* out[3] = {reads, bases, copies};
-        for (int k = 0; k < 3; ++k) if (out[k]) HIP_OK(hipMemcpyAsync(out[k], c->dr_cnt.as<uint64_t>() + k * n, n * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    });
-}
-int scs_write_depth_ref(scs_ctx* c, const char* path) {
-    return guarded(c, [&] {
-        if (!path || !*path) throw ScsError(SCS_EINVAL, "scs_write_depth_ref: no path");
-        need_dref(c, "scs_write_depth_ref"); need_lift(c, "scs_write_depth_ref");
-        const uint64_t nb = c->dref_bins, n = nb + 1, w = c->dref_width; std::vector<uint64_t> cnt(3 * n);
-        HIP_OK(hipMemcpyAsync(cnt.data(), c->dr_cnt.p, 3 * n * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        FILE* o = fopen(path, "w");
-        if (!o) throw ScsError(SCS_EIO, std::string("scs_write_depth_ref: can not open ") + path + ": " + strerror(errno));
-        bool okw = fputs("#record\tstart\tend\treads\tbases\tcopies\n", o) != EOF; uint64_t b = 0;
-        for (size_t r = 0; r < c->lift.ref_lens.size() && okw; ++r)
-            for (uint64_t x = 0; x < c->lift.ref_lens[r] && okw; x += w, ++b)
-                okw = fprintf(o, "%s\t%llu\t%llu\t%llu\t%llu\t%llu\n", c->lift.ref_names[r].c_str(), (unsigned long long)x, (unsigned long long)std::min<uint64_t>(x + w, c->lift.ref_lens[r]),
-                              (unsigned long long)cnt[b], (unsigned long long)cnt[n + b], (unsigned long long)cnt[2 * n + b]) > 0;
-        if (okw) okw = fprintf(o, "#unlifted\t%llu\t%llu\t%llu\n", (unsigned long long)cnt[nb], (unsigned long long)cnt[n + nb], (unsigned long long)cnt[2 * n + nb]) > 0;
-        if (fclose(o) != 0 || !okw || b != nb) throw ScsError(SCS_EIO, std::string("scs_write_depth_ref: writing ") + path + " failed");
-    });
-}
-int scs_depth_ref_kernel_time(const scs_ctx* c, uint64_t* launches, double* ms, uint64_t* units) { return kernel_time_of(c, &scs_ctx::tm_depth_ref, launches, ms, units); }
 
 // ---- host-only seams (no GPU, no ctx)
 // plan -> table -> optionally the file; subst_pos: the global haplotype indices the plan substitutes (SNP / SNV alleles)

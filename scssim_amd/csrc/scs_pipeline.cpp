@@ -329,63 +329,6 @@ int scs_set_truth_sam(scs_ctx* c, const char* path) { return set_truth(c, path, 
 int scs_set_truth_bam(scs_ctx* c, const char* path) { return set_truth(c, path, 1); }
 int scs_set_truth_ref_sam(scs_ctx* c, const char* path) { return set_truth(c, path, 2); }
 int scs_truth_bytes(const scs_ctx* c, uint64_t* bytes) { if (!c || !bytes) return SCS_EINVAL; *bytes = c->truth_bytes; return SCS_OK; }
-// ---- depth track
-int scs_set_depth(scs_ctx* c, uint32_t bin_width) {
-    return guarded(c, [&] {
-        if (bin_width == c->depth_width) return;
-        HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's counters go: nothing may still read them
-        c->dp_cnt.release(); c->dp_tab.release(); c->depth_valid = false; c->depth_bins = 0; c->depth_width = bin_width;
-    });
-}
-int scs_depth_bins(const scs_ctx* c, uint64_t* n_bins, uint32_t* bin_width) {
-    if (!c) return SCS_EINVAL;
-    scs_ctx* m = const_cast<scs_ctx*>(c);                                          // (the error text is the only thing written)
-    try {
-        if (!c->depth_width) throw ScsError(SCS_EINVAL, "scs_depth_bins: the depth track is off (scs_set_depth)");
-        if (!c->have_genome) throw ScsError(SCS_EINVAL, "scs_depth_bins: no genome is staged");
-        const uint64_t nb = depth_ctx_layout(c, nullptr);
-        if (n_bins) *n_bins = nb; if (bin_width) *bin_width = c->depth_width;
-        return SCS_OK;
-    } catch (const ScsError& e) { m->err = e.what(); return e.code; }
-}
-int scs_depth_record_bins(const scs_ctx* c, uint64_t* bin_off, uint64_t cap) {
-    if (!c || !bin_off) return SCS_EINVAL;
-    scs_ctx* m = const_cast<scs_ctx*>(c);
-    try {
-        if (!c->depth_width || !c->have_genome) throw ScsError(SCS_EINVAL, "scs_depth_record_bins: the depth track is off (scs_set_depth), or no genome is staged");
-        if (cap < c->rec_len.size() + 1) throw ScsError(SCS_EOVERFLOW, "scs_depth_record_bins: records + 1 entries are needed");
-        std::vector<uint64_t> off; (void)depth_ctx_layout(c, &off);
-        std::copy(off.begin(), off.end(), bin_off);
-        return SCS_OK;
-    } catch (const ScsError& e) { m->err = e.what(); return e.code; }
-}
-int scs_download_depth(scs_ctx* c, uint64_t* reads, uint64_t* bases, uint64_t cap) {
-    return guarded(c, [&] {
-        if (!c->depth_width || !c->depth_valid) throw ScsError(SCS_EINVAL, "scs_download_depth: no yield call with the depth track on (scs_set_depth) has finished");
-        const uint64_t nb = c->depth_bins;
-        if (cap < nb) throw ScsError(SCS_EOVERFLOW, "scs_download_depth: " + std::to_string(nb) + " bins, room for " + std::to_string(cap));
-        if (reads && nb) HIP_OK(hipMemcpyAsync(reads, c->dp_cnt.p, nb * 8, hipMemcpyDeviceToHost, c->stream));
-        if (bases && nb) HIP_OK(hipMemcpyAsync(bases, c->dp_cnt.as<uint64_t>() + nb, nb * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    });
-}
-int scs_write_depth(scs_ctx* c, const char* path) {
-    return guarded(c, [&] {
-        if (!path || !*path) throw ScsError(SCS_EINVAL, "scs_write_depth: no path");
-        if (!c->depth_width || !c->depth_valid) throw ScsError(SCS_EINVAL, "scs_write_depth: no yield call with the depth track on (scs_set_depth) has finished");
-        const uint64_t nb = c->depth_bins, w = c->depth_width; std::vector<uint64_t> cnt(std::max<uint64_t>(2 * nb, 1));
-        if (nb) HIP_OK(hipMemcpyAsync(cnt.data(), c->dp_cnt.p, nb * 16, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        FILE* o = fopen(path, "w");
-        if (!o) throw ScsError(SCS_EIO, std::string("scs_write_depth: can not open ") + path + ": " + strerror(errno));
-        bool okw = fputs("#record\tstart\tend\treads\tbases\n", o) != EOF; uint64_t b = 0;
-        for (size_t r = 0; r < c->rec_len.size() && okw; ++r)
-            for (uint64_t x = 0; x < c->rec_len[r] && okw; x += w, ++b)
-                okw = fprintf(o, "%s\t%llu\t%llu\t%llu\t%llu\n", c->recs[r].name.c_str(), (unsigned long long)x, (unsigned long long)std::min<uint64_t>(x + w, c->rec_len[r]),
-                              (unsigned long long)cnt[b], (unsigned long long)cnt[nb + b]) > 0;
-        if (fclose(o) != 0 || !okw || b != nb) throw ScsError(SCS_EIO, std::string("scs_write_depth: writing ") + path + " failed");
-    });
-}
 int scs_download_frags(scs_ctx* c, uint64_t* goff, uint32_t* len, int8_t* strand) {
     return guarded(c, [&] {
         if (!c->have_frags) throw ScsError(SCS_EINVAL, "scs_download_frags: call scs_create_frags first");

@@ -1,7 +1,8 @@
 // scs_place.h -- where a read of a batch lies on the genome: its indel events (the indel pass' packed ones, or drawn again for a
 // replayed read) and its placement (truth_place, scs_truth.h).  The one definition behind the truth passes (scs_k_truth.hip),
 // which go on to the read's FASTQ text (read_text), the site support pass (scs_k_support.hip), which reads its bases there, and the
-// depth pass (scs_k_depth.hip), which needs neither.
+// depth passes (scs_k_depth.hip, scs_k_lift.hip), which need neither.  The three side passes walk a pair's reads through one loop
+// (for_each_placed_read); the truth passes place a pair's two mates together and keep their own.
 // Needs scs_device.h and scs_kernels_common.h before it.
 #pragma once
 #include "scs_indel.h"
@@ -36,6 +37,25 @@ __device__ __forceinline__ bool read_place(const PlaceArgs& A, const PairRec& pr
     a.n = A.tb.L; a.nev = nev; a.ev = ev;
     if (!truth_place(a) || a.qlen != n_out) { atomicOr(A.flags, flag); return false; }
     return true;
+}
+
+// every placed read of pair pi (A: PlaceArgs with the staged record starts rec_off[n_rec + 1]): f(pr, rd, a, n, lo, r0, r1) with the
+// pair's record, the read's number, placement and length, and the staged record of its leftmost aligned base: lo, its first base r0
+// = rec_off[lo] <= a.lo and its end r1 = rec_off[lo + 1].  A hole and a read that read_place gives up on (it raises `flag`) are
+// passed over.  Whether the read ends inside [r0, r1) is not checked here: k_depth and k_support check before they use the record,
+// lift_read reports it itself
+template <class Args, class F>
+__device__ __forceinline__ void for_each_placed_read(const Args& A, uint32_t pi, uint32_t flag, F f) {
+    const PairRec pr = A.pairs[pi];
+    if (pr.isz == 0) return;                               // hole: no FASTQ record
+    uint32_t ev[TRUTH_EVCAP];
+    for (uint32_t rd = 0; rd < (A.paired ? 2u : 1u); ++rd) {
+        TruthAln a; int n_out;
+        if (!read_place(A, pr, pi, rd, ev, a, n_out, flag)) continue;
+        uint32_t lo = 0, hi = A.n_rec;
+        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)A.rec_off[mid] <= a.lo) lo = mid; else hi = mid; }
+        f(pr, rd, a, n_out, lo, (int64_t)A.rec_off[lo], (int64_t)A.rec_off[lo + 1]);
+    }
 }
 
 // where the bases of read rd of pair pi lie in the batch's FASTQ text: behind the record's name line "@amp#cnt[/r]\n" (off1 / off2:

@@ -1,9 +1,8 @@
 // scs_probes.cpp -- the test seams and kernel-level entry points of the C ABI: host-only probes of the formatters, parsers and
 // planners the product runs (truth SAM, FASTA, simuvars, BGZF, the profile tables), device probes of single kernels (BGZF, the
 // scans, DevBuf, Philox, det_log, Profile::predict), and the census of live device resources.  Nothing here is on a job's path.
-#include "scs_ctx.h"
+#include "scs_sitejob.h"
 #include "scs_amp.h"
-#include "scs_site.h"
 #include "scs_support.h"
 #include "scs_truth_ref.h"
 
@@ -216,6 +215,29 @@ int scs_artefact_probe(const uint64_t* amp_start, const uint32_t* amp_len, const
     const int rc = site_probe(amp_start, amp_len, amp_reads, n_amp, ed_amp, ed_x, ed_alt, n_ed, rec_len, names, genome, genome_len, min_reads, body);
     if (rc) return rc;
     if (flags & 1) body = site_header(names, rec_len) + body;
+    *n_out = body.size();
+    if (out) { if (body.size() > cap) return SCS_EOVERFLOW; memcpy(out, body.data(), body.size()); }
+    return SCS_OK;
+}
+
+// host-only: the reference table's body (flags & 1: behind its header) through the functions its kernels run (site_ref_probe, scs_site_ref.h)
+int scs_artefact_ref_probe(const uint64_t* amp_start, const uint32_t* amp_len, const uint32_t* amp_reads, uint64_t n_amp,
+                           const uint32_t* ed_amp, const uint64_t* ed_x, const uint8_t* ed_alt, uint64_t n_ed,
+                           const uint64_t* hap_len, uint32_t n_hap, const char* genome, uint64_t genome_len,
+                           const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                           const uint64_t* ref_len, const char* const* ref_names, uint32_t n_ref,
+                           uint32_t min_reads, uint64_t slab, int flags, char* out, size_t cap, size_t* n_out, uint64_t unlifted[2], int* lift_err) {
+    if (!n_out || !ref_names || !n_ref || !ref_len || (flags & ~1) || !n_seg || !seg_hap_off || !seg_len || !seg_ref_pos || !seg_ref_rec || !seg_kind) return SCS_EINVAL;
+    std::vector<std::string> names;
+    for (uint32_t r = 0; r < n_ref; ++r) { if (!ref_names[r]) return SCS_EINVAL; names.push_back(ref_names[r]); }
+    std::vector<LiftSeg> segs(n_seg);
+    for (uint32_t i = 0; i < n_seg; ++i) segs[i] = LiftSeg{seg_hap_off[i], seg_len[i], seg_ref_pos[i], seg_ref_rec[i], seg_kind[i]};
+    std::string body; uint64_t unl[2] = {0, 0};
+    const int rc = site_ref_probe(amp_start, amp_len, amp_reads, n_amp, ed_amp, ed_x, ed_alt, n_ed, hap_len, n_hap, genome, genome_len, segs.data(), n_seg, ref_len, names,
+                                  min_reads, slab ? slab : kSiteSlab, body, unl, lift_err);
+    if (unlifted) { unlifted[0] = unl[0]; unlifted[1] = unl[1]; }
+    if (rc) return rc;
+    if (flags & 1) body = site_ref_header(names, ref_len, unl[0], unl[1]) + body;
     *n_out = body.size();
     if (out) { if (body.size() > cap) return SCS_EOVERFLOW; memcpy(out, body.data(), body.size()); }
     return SCS_OK;

@@ -165,7 +165,7 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth_width != 0, depth_ref = c->dref_width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth.width != 0, depth_ref = c->depth_ref.width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, bi = 0;                           // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
@@ -174,6 +174,11 @@ struct Yield {               // the state of one do_yield call
     // shard index: the pair index at which each list segment starts (pair_off at the segment's first amplicon); the byte offset of
     // that record = the bytes of the batches before its batch (known once every batch is made) + its offset inside the batch
     std::vector<uint64_t> bpair, bb[2]; std::vector<SegAt> seg_at;
+    // what every pass that places reads takes (PlaceArgs): of the job, and of a batch
+    void place_job(PlaceArgs& a) const { a.paired = paired; a.tb = c->dtb; a.key = c->key; a.slot = slot; a.flags = c->flags.as<uint32_t>(); }
+    static void place_batch(PlaceArgs& a, const Batch& b) { a.pairs = b.pr; a.np = b.np; a.ev_hdr = b.B->ev_hdr; a.ev_dat = b.B->ev_dat; }
+    // a test seam that holds a number (SCS_TEST_*_SLOTS: a small LDS table overflows, 0 = no table), or what the product runs with
+    static uint32_t seam_u32(const char* name, uint32_t product) { return seam_env(name) ? (uint32_t)atoi(seam_env(name)) : product; }
     void truth_open() {
         // the header first, then the batches' records from the pipe's writer; the kernels' record table: starts, name offsets, names
         truth_fd.open(tname, c->truth_path, bam);
@@ -193,7 +198,7 @@ struct Yield {               // the state of one do_yield call
         c->h_t.reserve(64, hipHostMallocDefault); c->ev_t.ensure(hipEventDisableTiming | hipEventBlockingSync);
         rt.make(c, s, &c->t_recs);                                                 // (in the ctx's buffer: it stays allocated between yield calls)
         ta.g = c->genome.as<uint8_t>(); ta.rec_off = rt.rec_off; ta.name_off = rt.name_off; ta.names = rt.names; ta.n_rec = nr;
-        ta.paired = paired; ta.tb = c->dtb; ta.key = c->key; ta.slot = slot; ta.flags = c->flags.as<uint32_t>();
+        place_job(ta);
         if (tref) {                                                                // the reference's table, made as RecTable is: lengths (nf), name offsets (nf + 1), names, 16 bytes of slack
             const uint32_t nf = (uint32_t)c->lift.ref_lens.size(); std::vector<uint32_t> noff(nf + 1, 0); std::string text;
             for (uint32_t r = 0; r < nf; ++r) { text += c->lift.ref_names[r]; noff[r + 1] = (uint32_t)text.size(); }
@@ -206,36 +211,32 @@ struct Yield {               // the state of one do_yield call
         }
     }
     void depth_open() {
-        // the kernel's record table (record starts, first bins) and this call's counters, zeroed on the ctx stream
-        static const uint32_t slots = seam_env("SCS_TEST_DEPTH_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_DEPTH_SLOTS")) : DEPTH_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
-        const uint32_t nr = (uint32_t)c->recs.size(); std::vector<uint64_t> tab = record_starts(c), boff;
-        const uint64_t nb = c->depth_bins = depth_ctx_layout(c, &boff);
-        tab.insert(tab.end(), boff.begin(), boff.end());
-        upload(c->dp_tab, tab, s);
-        c->dp_cnt.reserve(std::max<size_t>((size_t)nb * 16, 16), s); HIP_OK(hipMemsetAsync(c->dp_cnt.p, 0, std::max<size_t>((size_t)nb * 16, 16), s));
-        HIP_OK(hipStreamSynchronize(s));                                           // (the host table goes)
-        da.rec_off = c->dp_tab.as<uint64_t>(); da.bin_off = da.rec_off + nr + 1; da.n_rec = nr; da.bin_width = c->depth_width; da.slots = slots;
-        da.reads = c->dp_cnt.as<unsigned long long>(); da.bases = da.reads + nb;
-        da.paired = paired; da.tb = c->dtb; da.key = c->key; da.slot = slot; da.flags = c->flags.as<uint32_t>();
+        // the kernel's record table (record starts, first bins) and this call's counters, zeroed on the ctx stream (scs_depth.cpp)
+        static const uint32_t slots = seam_u32("SCS_TEST_DEPTH_SLOTS", DEPTH_LDS_SLOTS);
+        scs::depth_open(c, false);
+        const uint32_t nr = (uint32_t)c->recs.size(); const uint64_t nb = c->depth.bins;
+        da.rec_off = c->depth.tab.as<uint64_t>(); da.bin_off = da.rec_off + nr + 1; da.n_rec = nr; da.bin_width = c->depth.width; da.slots = slots;
+        da.reads = c->depth.cnt.as<unsigned long long>(); da.bases = da.reads + nb;
+        place_job(da);
     }
     void depth_ref_open() {
         // the kernel's tables (staged record starts, the reference's lengths and first bins), this call's counters zeroed on the ctx
-        // stream, the copies where the layout is new (scs_lift.cpp)
-        static const uint32_t slots = seam_env("SCS_TEST_LIFT_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_LIFT_SLOTS")) : DEPTH_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
-        scs::depth_ref_open(c);
-        const uint32_t nr = (uint32_t)c->recs.size(), nf = (uint32_t)c->lift.ref_lens.size(); const uint64_t nb = c->dref_bins;
-        la.rec_off = c->dr_tab.as<uint64_t>(); la.n_rec = nr; la.ref_len = la.rec_off + nr + 1; la.ref_bin_off = la.ref_len + nf; la.n_ref = nf;
-        la.segs = c->d_lift.as<LiftSeg>(); la.n_seg = (uint32_t)c->lift.segs.size(); la.bin_width = c->dref_width; la.slots = slots; la.n_bins = nb;
-        la.reads = c->dr_cnt.as<unsigned long long>(); la.bases = la.reads + nb + 1;
-        la.paired = paired; la.tb = c->dtb; la.key = c->key; la.slot = slot; la.flags = c->flags.as<uint32_t>();
+        // stream, the copies where the layout is new (scs_depth.cpp)
+        static const uint32_t slots = seam_u32("SCS_TEST_LIFT_SLOTS", DEPTH_LDS_SLOTS);
+        scs::depth_open(c, true);
+        const uint32_t nr = (uint32_t)c->recs.size(), nf = (uint32_t)c->lift.ref_lens.size(); const uint64_t nb = c->depth_ref.bins;
+        la.rec_off = c->depth_ref.tab.as<uint64_t>(); la.n_rec = nr; la.ref_len = la.rec_off + nr + 1; la.ref_bin_off = la.ref_len + nf; la.n_ref = nf;
+        la.segs = c->d_lift.as<LiftSeg>(); la.n_seg = (uint32_t)c->lift.segs.size(); la.bin_width = c->depth_ref.width; la.slots = slots; la.n_bins = nb;
+        la.reads = c->depth_ref.cnt.as<unsigned long long>(); la.bases = la.reads + nb + 1;
+        place_job(la);
     }
     void support_open() {
         // the call's site table, its distinct positions and this call's counters, zeroed on the ctx stream (scs_support.cpp)
-        static const uint32_t slots = seam_env("SCS_TEST_SUPPORT_SLOTS") ? (uint32_t)atoi(seam_env("SCS_TEST_SUPPORT_SLOTS")) : SUPPORT_LDS_SLOTS;   // tests: a small table overflows, 0 = no table
+        static const uint32_t slots = seam_u32("SCS_TEST_SUPPORT_SLOTS", SUPPORT_LDS_SLOTS);
         scs::support_open(c);
         sa.rec_off = c->sp_tab.as<uint64_t>(); sa.n_rec = (uint32_t)c->recs.size(); sa.sp_pos = c->sp_pos.as<uint64_t>(); sa.n_pos = c->sp_n_pos;
         sa.counts = c->sp_cnt.as<uint32_t>(); sa.slots = slots;
-        sa.paired = paired; sa.tb = c->dtb; sa.key = c->key; sa.slot = slot; sa.flags = c->flags.as<uint32_t>();
+        place_job(sa);
     }
     void setup() {           // the batches' bounds; the truth file; the pipe's writers; the BGZF totals' pinned words and events, the BGZF kernels' CRC tables; the batches' two buffer sets; the pre-pass' stream; the shard index
         // The pairs are planned (k_plan_pairs: insert sizes, positions, the amplicon resolved to an index map) batch by batch, at the
@@ -363,9 +364,9 @@ struct Yield {               // the state of one do_yield call
     void truth_batch(Batch& b) {
         // the batch's SAM: sizing pass + 64-bit offsets, the total to the host (it sizes the output), emit pass.  Before ev_free: the
         // passes read the batch's indel events and record offsets
-        static const uint32_t bam_lds = seam_env("SCS_TEST_TRUTH_LDS") ? (uint32_t)atoi(seam_env("SCS_TEST_TRUTH_LDS")) : 0u;   // tests: the BAM and the reference SAM's emit passes cut their runs
+        static const uint32_t bam_lds = seam_u32("SCS_TEST_TRUTH_LDS", 0u);   // tests: the BAM and the reference SAM's emit passes cut their runs
         const uint32_t np = b.np; const uint64_t fq_bytes = b.n.bytes[0] + b.n.bytes[1];
-        ta.pairs = b.pr; ta.np = np; ta.ev_hdr = b.B->ev_hdr; ta.ev_dat = b.B->ev_dat; ta.off1 = b.B->off[0]; ta.off2 = b.B->off[1]; ta.fq1 = b.out[0]; ta.fq2 = b.out[1];
+        place_batch(ta, b); ta.off1 = b.B->off[0]; ta.off2 = b.B->off[1]; ta.fq1 = b.out[0]; ta.fq2 = b.out[1];
         c->tm[TM_TRUTH].begin(s);
         if (bam) launch_truth_bam_size(s, ta, c->t_sizes.as<uint32_t>()); else if (tref) launch_truth_ref_size(s, ta, c->t_sizes.as<uint32_t>()); else launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
         exclusive_scan_u32_to_u64(s, c->t_sizes.as<uint32_t>(), c->t_offs.as<uint64_t>(), np, c->t_scan.p, c->t_scan.cap);
@@ -390,14 +391,14 @@ struct Yield {               // the state of one do_yield call
     }
     void depth_batch(const Batch& b) {
         // the batch's reads into the depth counters, from its pair records and indel events alone.  Before ev_free, as truth_batch
-        da.pairs = b.pr; da.np = b.np; da.ev_hdr = b.B->ev_hdr; da.ev_dat = b.B->ev_dat;
+        place_batch(da, b);
         c->tm[TM_DEPTH].begin(s);
         launch_depth(s, da);
         c->tm[TM_DEPTH].end(s); c->tm[TM_DEPTH].add_units(b.np);
     }
     void depth_ref_batch(const Batch& b) {
         // the batch's reads into the reference's bins through the lift table, from what depth_batch reads.  Before ev_free, as truth_batch
-        la.pairs = b.pr; la.np = b.np; la.ev_hdr = b.B->ev_hdr; la.ev_dat = b.B->ev_dat;
+        place_batch(la, b);
         c->tm_depth_ref.begin(s);
         launch_depth_lift(s, la);
         c->tm_depth_ref.end(s); c->tm_depth_ref.add_units(b.np);
@@ -405,7 +406,7 @@ struct Yield {               // the state of one do_yield call
     void support_batch(const Batch& b) {
         // the batch's reads into the site counters, from its pair records, indel events and FASTQ text.  Before ev_free, as truth_batch,
         // and before the sink takes the text
-        sa.pairs = b.pr; sa.np = b.np; sa.ev_hdr = b.B->ev_hdr; sa.ev_dat = b.B->ev_dat; sa.off1 = b.B->off[0]; sa.off2 = b.B->off[1]; sa.fq1 = b.out[0]; sa.fq2 = b.out[1];
+        place_batch(sa, b); sa.off1 = b.B->off[0]; sa.off2 = b.B->off[1]; sa.fq1 = b.out[0]; sa.fq2 = b.out[1];
         c->tm_support.begin(s);
         launch_support(s, sa);
         c->tm_support.end(s); c->tm_support.add_units(b.np);
@@ -455,8 +456,8 @@ struct Yield {               // the state of one do_yield call
         mail_wait(c); flags_eval(c);
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];
-        c->tm[TM_READS].collect(); c->tm[TM_INDELS].collect(); c->tm[TM_TRUTH].collect(); c->tm[TM_DEPTH].collect(); c->tm_support.collect(); c->tm_depth_ref.collect();
-        c->depth_valid = depth; c->support_valid = support; c->dref_valid = depth_ref;
+        for (KernelTimer* t : c->yield_timers()) t->collect();
+        c->depth.valid = depth; c->support_valid = support; c->depth_ref.valid = depth_ref;
         c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
         for (int m = 0; m < 2; ++m) { c->st.fastq_bytes[m] = tot[m]; c->st.sink_bytes[m] = to_sink ? sunk[m] : 0; }
         // 1526 B per created amplicon + per pair (insert size + FASTQ bytes of both records)
@@ -474,10 +475,9 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     Yield y{c, tg}; const hipStream_t s = y.s; const uint64_t P = y.P;
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
-    c->tm[TM_READS].reset(); c->tm[TM_INDELS].reset(); c->tm[TM_TRUTH].reset(); c->tm[TM_DEPTH].reset(); c->tm_support.reset(); c->tm_depth_ref.reset();
-    c->depth_valid = false; c->support_valid = false; c->dref_valid = false;
-    if (c->depth_width) (void)depth_ctx_layout(c, nullptr);   // more than 2^27 bins: refused before any GPU work
-    if (c->dref_width) { depth_ref_check(c); (void)depth_ref_layout(c, nullptr); }   // no lift table, or more than 2^27 bins: the same
+    for (KernelTimer* t : c->yield_timers()) t->reset();
+    c->depth.valid = false; c->support_valid = false; c->depth_ref.valid = false;
+    depth_yield_check(c);                                  // more than 2^27 bins, no lift table: refused before any GPU work
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
     // (Profile.cpp:1482-1485 -> Config.cpp:85-93) -- after the amplification, with the output files opened and empty.  Same here, as an error code.
@@ -534,19 +534,6 @@ void truth_ref_release(scs_ctx* c) {
     c->h_t.release(); c->ev_t.release();
     c->tm[TM_TRUTH].ev.clear(); c->tm[TM_TRUTH].used = 0; c->tm[TM_TRUTH].reset();
     if (c->pipe) for (auto& sl : c->pipe->slots) sl.h[2].release();                // (no writer runs between two yield calls)
-}
-
-void depth_check(scs_ctx* c) {
-    depth_ref_check(c);                                                            // (depth by reference bin: refused at the same place)
-    if (!c->depth_width) return;
-    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, "depth track (scs_set_depth): not available for a sharded job (shard_count > 1); turn it off with scs_set_depth(ctx, 0)");
-}
-uint64_t depth_ctx_layout(const scs_ctx* c, std::vector<uint64_t>* bin_off) {
-    const size_t nr = c->rec_len.size(); uint64_t nb = 0; uint32_t min_w = 0;
-    if (bin_off) bin_off->assign(nr + 1, 0);
-    if (depth_layout(c->rec_len.data(), nr, c->depth_width, bin_off ? bin_off->data() : nullptr, &nb, &min_w)) return nb;
-    throw ScsError(SCS_EINVAL, "depth track (scs_set_depth): bins of " + std::to_string(c->depth_width) + " bases give more than 2^27 bins for the staged genome; " +
-                   (min_w ? "the smallest bin width it admits is " + std::to_string(min_w) : std::string("no bin width below 2^32 is enough")));
 }
 
 }  // namespace scs

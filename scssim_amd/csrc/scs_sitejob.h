@@ -1,7 +1,6 @@
-// scs_sitejob.h -- private to the host files of the artefact table (scs_sites.cpp), of the site support table (scs_support.cpp),
-// which is the same table with the reads' counters, and of the artefact table on the original reference (scs_sites_ref.cpp), which
-// is the same scheme over the reference axis: one call's pass over the amplicons slab by slab (SiteJob) and what turns a
-// run of sites into bytes of a file (SiteOut).  Every buffer, stream and event belongs to the struct that holds it and goes with it.
+// scs_sitejob.h -- private to the host files of the artefact table, on the staged genome and on the original reference (scs_sites.cpp:
+// the same scheme over either axis), and of the site support table (scs_support.cpp), which is the same table with the reads'
+// counters: one call's pass over the amplicons slab by slab (SiteJob) and what turns a run of sites into bytes of a file (SiteOut).  Every buffer, stream and event belongs to the struct that holds it and goes with it.
 #pragma once
 #include "scs_textout.h"
 #include "scs_site.h"
@@ -15,8 +14,9 @@ const uint64_t kSiteSlab = 1ull << 28;                     // genome indices per
 const uint64_t kSitePiece = 32ull << 20;                   // bytes of the file that cross to the host at a time
 const uint64_t kSiteMaxEntries = 0x7FFFFF00ull;            // edit entries (and amplicons) one slab may hold
 
-inline void site_check(scs_ctx* c, const char* fn) {              // (amp_check's refusals, scs_amplicons.cpp)
+inline void site_check(scs_ctx* c, const char* fn, bool on_ref) {   // (amp_check's refusals, scs_amplicons.cpp; on_ref: and no lift table)
     if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, std::string(fn) + ": not available for a sharded job (shard_count > 1)");
+    if (on_ref && !c->have_lift) throw ScsError(SCS_EINVAL, std::string(fn) + ": the staged genome has no lift table; stage it with scs_simuvars, or read its table with scs_load_lift after staging");
     if (!c->allocated) throw ScsError(SCS_EINVAL, std::string(fn) + ": call scs_allocate_reads first (the table states every site's read support)");
 }
 
@@ -71,14 +71,14 @@ struct SiteOut {
 
 // One call's work: the kernels' arguments over the ctx's tables, the per-slab counts, and everything the call allocates.  Its
 // destructor ends every way out of the call: both streams drained; the members then release themselves.
-// on_ref (scs_sites_ref.cpp): the slabs are slabs of REFERENCE indices, the counting, fill and reduce passes are
+// on_ref: the slabs are slabs of REFERENCE indices, the counting, fill and reduce passes are
 // scs_k_sites_ref.hip's over the lift table (v), `amplicons` reads `pieces of amplicons`, t names the reference records, and the
 // counting pass also finds the two unlifted totals and is followed by a check of the flags.  Everything else is one code
 struct SiteJob {
     scs_ctx* const c; const hipStream_t s; const bool on_ref; const char* const what; KernelTimer idle{"k_sites"}; KernelTimer& tm; AmpArgs a{}; SiteArgs t{};   // tm: the ctx's timer (scs_write_artefacts / _ref), or one that is off
     uint32_t chunk = kSiteChunk, min_reads = 0; uint64_t slab = kSiteSlab, bases = 0; uint32_t n_slabs = 0;   // bases: of the axis the slabs cut
     std::vector<uint64_t> cnt;                             // [2 k]: edit entries of slab k, [2 k + 1]: amplicons (pieces) that overlap it; on_ref: behind them the two unlifted totals
-    SiteRefView v{}; DevBuf ref_tab; uint64_t unlifted[2] = {0, 0};   // on_ref: the walk's view of the lift table; the reference records' starts, name offsets and names
+    SiteRefView v{}; RecTable ref_rt; uint64_t unlifted[2] = {0, 0};   // on_ref: the walk's view of the lift table; the reference records' table
     uint64_t max_e = 0, max_a = 0; size_t sort_bytes = 0, scan_bytes = 0;
     Event ev_n; RecTable rt; SiteOut em;                   // em: the file's bytes (scs_write_artefacts)
     DevBuf d_cnt, cur, keys[2], kreads[2], starts[2], ends[2], areads[3], ps_start, ps_end, sort_tmp, scan_tmp, site_recs, sizes, offs, keep, keep_pos, packed;
@@ -108,22 +108,19 @@ struct SiteJob {
         tm.ev.clear(); tm.used = 0;                        // (the timer's events were this call's too; its sums stay)
     }
 
-    // on_ref: the reference records as the kernels read them -- starts (nf + 1), name offsets (nf + 1), names, 16 bytes of slack -- take
-    // the staged records' place in t, and the slabs cut the reference
+    // on_ref: the reference records' table (RecTable, over the lift table's names and lengths) takes the staged records' place in
+    // t, and the slabs cut the reference
     void reference() {
         const LiftTable& L = c->lift; const uint32_t nf = (uint32_t)L.ref_lens.size();
-        std::vector<uint64_t> roff(nf + 1, 0); std::vector<uint32_t> noff(nf + 1, 0); std::string text;
+        std::vector<uint64_t> roff(nf + 1, 0);
         for (uint32_t r = 0; r < nf; ++r) {
-            roff[r + 1] = roff[r] + L.ref_lens[r]; text += L.ref_names[r]; noff[r + 1] = (uint32_t)text.size();
+            roff[r + 1] = roff[r] + L.ref_lens[r];
             if ((L.ref_lens[r] >> 58) || (roff[r + 1] >> 58)) throw ScsError(SCS_EOVERFLOW, "artefact table on the reference: the reference exceeds 2^58 bases");
         }
-        bases = roff[nf];
-        const size_t o_name = (size_t)(nf + 1) * 8, o_text = o_name + (size_t)(nf + 1) * 4; std::vector<uint8_t> blob(o_text + text.size() + 16, 0);
-        memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nf + 1) * 4); memcpy(blob.data() + o_text, text.data(), text.size());
-        upload(ref_tab, blob, s); HIP_OK(hipStreamSynchronize(s));                    // (the host blob goes)
-        const uint8_t* tb = ref_tab.as<uint8_t>();
-        v.segs = c->d_lift.as<LiftSeg>(); v.n_seg = (uint32_t)L.segs.size(); v.ref_off = (const uint64_t*)tb; v.n_ref = nf;
-        t.rec_off = v.ref_off; t.name_off = (const uint32_t*)(tb + o_name); t.names = (const char*)(tb + o_text); t.n_rec = nf;
+        ref_rt.make(roff, [&](uint32_t r) -> const std::string& { return L.ref_names[r]; }, s);
+        bases = ref_rt.bases;
+        v.segs = c->d_lift.as<LiftSeg>(); v.n_seg = (uint32_t)L.segs.size(); v.ref_off = ref_rt.rec_off; v.n_ref = nf;
+        t.rec_off = ref_rt.rec_off; t.name_off = ref_rt.name_off; t.names = ref_rt.names; t.n_rec = nf;
     }
 
     template <class F> void chunks(F f) {                  // the amplicon list, a chunk at a time
@@ -161,6 +158,15 @@ struct SiteJob {
     void compact(uint64_t e, uint64_t kept) {
         packed.reserve(std::max<uint64_t>(kept, 1) * sizeof(SiteRec), s);
         launch_site_compact(s, site_recs.as<SiteRec>(), keep.as<uint32_t>(), keep_pos.as<uint32_t>(), e, packed.as<SiteRec>());
+    }
+
+    // every slab with work, in order: made (make), then f(e, kept) -- its edit entries and its reported sites (h_n[0]: its text bytes)
+    template <class F> void slabs(F f) {
+        for (uint32_t k = 0; k < n_slabs; ++k) {
+            if (!cnt[2 * k]) continue;                     // a slab without an entry has no site: nothing is launched for it
+            const uint64_t e = make(k);
+            f(e, (uint64_t)(uint32_t)h_n[1]);
+        }
     }
 
     // slab k with work: its sorted entries, its sites and their line sizes, the text offsets and the reported sites' positions;

@@ -34,16 +34,14 @@ void support_open(scs_ctx* c) {
     uint64_t n = 0;
     {
         SiteJob J(c, c->support_min_reads, false);
-        for (uint32_t k = 0; k < J.n_slabs; ++k) {
-            if (!J.cnt[2 * k]) continue;
-            const uint64_t e = J.make(k), kept = (uint32_t)J.h_n[1];
-            if (!kept) continue;
+        J.slabs([&](uint64_t e, uint64_t kept) {
+            if (!kept) return;
             if (n + kept > 3ull * SUPPORT_MAX_POS) throw ScsError(SCS_EOVERFLOW, "site support (scs_set_site_support): more than 2^29 - 1 distinct positions; raise min_reads");
             J.compact(e, kept);
             c->sp_sites.reserve((n + kept) * sizeof(SiteRec), s, n * sizeof(SiteRec));
             HIP_OK(hipMemcpyAsync(c->sp_sites.as<SiteRec>() + n, J.packed.p, kept * sizeof(SiteRec), hipMemcpyDeviceToDevice, s));
             n += kept;
-        }
+        });
         // the record starts for the kernels of this call (the job's own table goes with it)
         const std::vector<uint64_t> roff = record_starts(c);
         upload(c->sp_tab, roff, s); HIP_OK(hipStreamSynchronize(s));

@@ -15,15 +15,16 @@ inline std::vector<uint64_t> record_starts(const scs_ctx* c) {
     return roff;
 }
 
-// the kernels' record table on the device: record starts (nr + 1), name offsets (nr + 1), names, 16 bytes of slack.  It lies in the
-// table's own buffer, which goes with it, or in `into` (the truth passes' t_recs, which the ctx keeps between yield calls)
+// the kernels' record table on the device: record starts (n + 1), name offsets (n + 1), names, 16 bytes of slack.  It lies in the
+// table's own buffer, which goes with it, or in `into` (the truth passes' t_recs, which the ctx keeps between yield calls).  Over
+// any records -- roff: their n + 1 starts, name(r): record r's name -- or over the staged ones
 struct RecTable {
     DevBuf tab; const uint64_t* rec_off = nullptr; const uint32_t* name_off = nullptr; const char* names = nullptr; uint32_t n_rec = 0; uint64_t bases = 0;
-    void make(const scs_ctx* c, hipStream_t s, DevBuf* into = nullptr) {
+    template <class Name> void make(const std::vector<uint64_t>& roff, Name name, hipStream_t s, DevBuf* into = nullptr) {
         DevBuf& d = into ? *into : tab;
-        const uint32_t nr = (uint32_t)c->recs.size();
-        const std::vector<uint64_t> roff = record_starts(c); std::vector<uint32_t> noff(nr + 1, 0); std::string text;
-        for (uint32_t r = 0; r < nr; ++r) { text += c->recs[r].name; noff[r + 1] = (uint32_t)text.size(); }
+        const uint32_t nr = (uint32_t)roff.size() - 1u;
+        std::vector<uint32_t> noff(nr + 1, 0); std::string text;
+        for (uint32_t r = 0; r < nr; ++r) { text += name(r); noff[r + 1] = (uint32_t)text.size(); }
         bases = roff[nr];
         const size_t o_name = (size_t)(nr + 1) * 8, o_text = o_name + (size_t)(nr + 1) * 4; std::vector<uint8_t> blob(o_text + text.size() + 16, 0);
         memcpy(blob.data(), roff.data(), o_name); memcpy(blob.data() + o_name, noff.data(), (size_t)(nr + 1) * 4); memcpy(blob.data() + o_text, text.data(), text.size());
@@ -31,6 +32,7 @@ struct RecTable {
         const uint8_t* tb = d.as<uint8_t>();
         rec_off = (const uint64_t*)tb; name_off = (const uint32_t*)(tb + o_name); names = (const char*)(tb + o_text); n_rec = nr;
     }
+    void make(const scs_ctx* c, hipStream_t s, DevBuf* into = nullptr) { make(record_starts(c), [&](uint32_t r) -> const std::string& { return c->recs[r].name; }, s, into); }
 };
 
 // the BGZF kernels' CRC tables in `crc`: uploaded (and waited for) where it holds none yet
@@ -52,7 +54,7 @@ inline void bgzf_in_place(hipStream_t s, BgzfLane& z, const DevBuf& crc, const c
     HIP_OK(hipMemcpyAsync(h_total, z.offs.as<uint32_t>() + nblk, 4, hipMemcpyDeviceToHost, s));
 }
 
-// what the four scs_*_kernel_time entry points answer from their timer
+// what the scs_*_kernel_time entry points answer from their timer
 inline int kernel_time_of(const scs_ctx* c, const KernelTimer scs_ctx::* tm, uint64_t* launches, double* ms, uint64_t* units) {
     if (!c) return SCS_EINVAL;
     const KernelTimer& t = c->*tm;

@@ -377,3 +377,70 @@ def test_refusals_and_ownership(g1_reference, models, golden_inputs, tmp_path):
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     _, res = g1_reference
     assert res["live_end"] == [0, 0, 0, 0]
+
+
+# the four per-batch side outputs of one ctx: leg "all" has them on together, then each alone after set_seed
+_SIDE = r'''
+import json, sys
+sys.path.insert(0, %(root)r)
+import numpy as np
+import scssim_amd
+out = %(out)r
+g = scssim_amd.GenReads(profile=%(prof)r, coverage=3.0, layout="PE", seed=41)
+g.simuvars(%(fa)r)                                          # no variant files: the identity lift table
+g.create_frags(); g.amplify(); g.allocate_reads(0)
+res = {}
+for name in ("all", "sam", "depth", "depth_ref", "support"):
+    on = lambda k: name in ("all", k)
+    g.set_seed(41)
+    g.set_truth_sam(out + "_" + name + ".sam" if on("sam") else None)
+    g.set_depth(100 if on("depth") else 0); g.set_depth_ref(100 if on("depth_ref") else 0); g.set_site_support(on("support"), 0)
+    f1, f2 = g.yield_reads()
+    open(out + "_" + name + "_1.fq", "wb").write(f1); open(out + "_" + name + "_2.fq", "wb").write(f2)
+    a = {}
+    if on("depth"):
+        a["hreads"], a["hbases"], _ = g.depth()
+    if on("depth_ref"):
+        a["reads"], a["bases"], a["copies"], _ = g.depth_ref()
+    if on("support"):
+        a["counts"] = g.site_support()["counts"]
+    np.savez(out + "_" + name + ".npz", **a)
+    res[name] = dict(reads_written=g.stats()["reads_written"], batches=g.kernel_times()["k_reads"]["launches"], k_depth=g.kernel_times()["k_depth"]["launches"],
+                     k_truth=g.kernel_times()["k_truth"]["launches"], k_depth_lift=g.depth_ref_kernel_time()["launches"], k_support=g.site_support_kernel_time()["launches"])
+g.close()
+res["live_end"] = scssim_amd.live_resources()
+print("RESULT " + json.dumps(res))
+'''
+
+
+def test_all_side_outputs_in_one_yield_equal_each_alone(models, golden_inputs, tmp_path):
+    """The truth SAM, both depth tracks and the site support share the code that hands a batch to their kernels: g1 as the reference
+    of an identity lift table, batches of 256 pairs (many batches, both buffer sets), one yield with all four on and, after set_seed,
+    one with each alone.  The SAM's bytes, both haplotype depth arrays, the three reference arrays and the support counters of
+    the combined call equal the single calls'; the FASTQ text is the same five times; nothing is left after close()."""
+    out = str(tmp_path / "side")
+    r = subprocess.run([sys.executable, "-c", _SIDE % dict(root=ROOT, out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"])],
+                       env=seams_env(SCS_TEST_BATCH_SHIFT="8"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    print(res)
+    every, singles = np.load(out + "_all.npz"), {"depth": ("hreads", "hbases"), "depth_ref": ("reads", "bases", "copies"), "support": ("counts",)}
+    n = res["all"]["batches"]
+    assert n >= 4 and res["all"]["reads_written"] > 1000                       # at least two batches through each buffer set
+    assert [res["all"][k] for k in ("k_depth", "k_depth_lift", "k_support")] == [n, n, n] and res["all"]["k_truth"] >= n   # one event pair per batch and kernel
+    for name, k in (("sam", "k_truth"), ("depth", "k_depth"), ("depth_ref", "k_depth_lift"), ("support", "k_support")):
+        assert [res[name][j] > 0 for j in ("k_truth", "k_depth", "k_depth_lift", "k_support")] == [j == k for j in ("k_truth", "k_depth", "k_depth_lift", "k_support")], name
+        assert res[name]["reads_written"] == res["all"]["reads_written"] and res[name]["batches"] == n
+    for name, keys in singles.items():
+        one = np.load(out + "_" + name + ".npz")
+        assert sorted(one.files) == sorted(keys)
+        for k in keys:
+            assert every[k].shape == one[k].shape and (every[k] == one[k]).all() and every[k].sum() > 1000, (name, k)
+    sam = open(out + "_all.sam", "rb").read()
+    assert len(sam) > 100000 and open(out + "_sam.sam", "rb").read() == sam
+    for f in ("_1.fq", "_2.fq"):
+        want = open(out + "_all" + f, "rb").read()
+        assert len(want) > 100000
+        for name in ("sam",) + tuple(singles):
+            assert open(out + "_" + name + f, "rb").read() == want, (name, f)
+    assert res["live_end"] == [0, 0, 0, 0]
