@@ -682,6 +682,18 @@ int         scs_bgzf_device_probe(int device, const void* text, uint64_t nbytes,
  * out0[0..n0] and out1[0..n1] (n + 1 entries each, out[n] = the total mod 2^32) come back.  A scan that writes behind out[n] is
  * reported as SCS_EDEVICE.  Errors as for scs_devbuf_probe. */
 int         scs_scan_probe(int device, const uint32_t* in0, uint64_t n0, const uint32_t* in1, uint64_t n1, uint32_t* out0, uint32_t* out1);
+/* Test seams of the read allocation (scs_k_allocate.hip, scs_alloc_plan.h).  scs_alloc_plan_probe: host-only, the plan of shard `rank`
+ * of R over counts[r * 40 + slot] amplicons (slot = cycle * 8 + 7 - pass).  scalars: total, chunks, n_interior, n_boundary, n_ranges,
+ * n_gseg, the shard's amplicons, scratch doubles; all arrays NULL: the scalars alone (the sizes of a second call); ranges: 3 words
+ * each (q0, c0, local0); bchunks: 3 (chunk, length, owner); gsegs: 5 (go, lo, n, owner, slot); my_seg: 40 x 4 (go, lo, n, order).
+ * scs_alloc_sums_probe (needs a GPU): the fixed-shape sum (which = 0: one double) or scan (which = 1: n doubles) of n doubles with the
+ * scratch a job reserves for n chunks.  scs_alloc_probe (needs a GPU): the whole allocation behind the weights on a ctx that was never
+ * amplified, over n_local given weights cut into segments of seg_counts[40]; layout, seed, shard and collectives are the ctx's;
+ * rn_out[n_local], pair_off_out[n_local + 1]; the ctx stays not allocated.  In contract: finite weights >= 0 whose sum over the
+ * whole job is at least 1e-3. */
+int         scs_alloc_plan_probe(const uint64_t* counts, int R, int rank, uint64_t scalars[8], uint32_t* ranges, uint32_t* bchunks, uint64_t* gsegs, uint64_t* my_seg);
+int         scs_alloc_sums_probe(int device, const double* in, uint64_t n, int which, double* out);
+int         scs_alloc_probe(scs_ctx* ctx, const double* w_local, uint64_t n_local, const uint32_t* seg_counts, uint64_t reads, uint32_t* rn_out, uint32_t* pair_off_out);
 /* Test seam of the library's resource ownership (no ctx; process-wide): what its owning handles hold at this moment --
  * out[0] = bytes of device buffers, out[1] = streams it created (a caller's cfg.stream is not one), out[2] = events, out[3] = bytes
  * of pinned host memory.  Counted by the handles themselves as they allocate and free, not asked of the driver, so other

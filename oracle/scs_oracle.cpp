@@ -1225,7 +1225,9 @@ inline unsigned first_le(const double* cdf, unsigned n, double u) {             
 }
 
 // allocation over a weight vector in (global) list order -> read numbers
-void allocate_reads(Sim& S, std::vector<double>& w, long reads, std::vector<unsigned>& readNumbers) {
+// diag (scso_allocate_reads; null in a job): what the rule computed on the way -- recorded, never read back
+struct AllocDiag { double total = 0; unsigned long residual = 0, leftover = 0; std::vector<unsigned> quota; };
+void allocate_reads(Sim& S, std::vector<double>& w, long reads, std::vector<unsigned>& readNumbers, AllocDiag* diag = nullptr) {
     const size_t ac = w.size();
     const unsigned chunk = (unsigned)std::max<size_t>(1, std::min<size_t>(1000, ac / 1));   // loadPerThread at -t 1
     const bool ctr = S.prm.counter;
@@ -1275,6 +1277,7 @@ void allocate_reads(Sim& S, std::vector<double>& w, long reads, std::vector<unsi
         }
     });
     for (size_t c = 0; c < nch; ++c) count += quota[c];
+    if (diag) { diag->total = total; diag->residual = n; diag->quota = quota; diag->leftover = n - count; }
     n -= count;
     if (n > 0 && nch) {
         std::vector<double> probs(nch);
@@ -1852,6 +1855,33 @@ int scso_gc_factor_batch(void* h, int gc, int count, int counter, uint64_t seed,
         struct Lend { Sim& s; ~Lend() { s.prof = nullptr; } } lend{S};               // (the profile stays the caller's)
         for (int l = 0; l < 101; ++l) { S.gcGen.emplace_back((unsigned)seed); S.gcDist.emplace_back(S.prof->gcMeans[l], S.prof->gcStd); }
         for (int i = 0; i < count; ++i) out[i] = gc_factor(S, gc, (uint64_t)i);
+        return 0;
+    } catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+
+// ---- the read allocation's rule on given inputs (tests/test_alloc_host.py, tests/test_gpu_alloc.py): the counter-mode functions above
+int scso_tree_sum(const double* v, uint64_t n, double* out) {
+    try { if (!out || (n && !v)) fail("scso_tree_sum: null argument"); *out = tree_sum(v, (size_t)n); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+int scso_scan_all(const double* v, uint64_t n, double* out) {
+    try { if (n && (!v || !out)) fail("scso_scan_all: null argument"); scan_all(v, (size_t)n, out); return 0; }
+    catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// diag_out (nullable; 4 + ceil(n / 1000) words): the total's bits, the residual reads after the floors, the leftover after the per-chunk
+// quotas (the top draws), the chunk count, then every chunk's quota before the top draws
+int scso_allocate_reads(const double* w, uint64_t n, uint64_t reads, int paired, uint64_t seed, int threads, uint32_t* rn_out, uint64_t* diag_out) {
+    try {
+        if (!n || !w || !rn_out || reads > 0x7FFFFFFFFFFFFFFFull) fail("scso_allocate_reads: bad argument");
+        Sim S; S.prm.counter = true; S.prm.paired = paired != 0; S.prm.threads = std::max(1, threads); S.prm.seed = seed;
+        S.rng.counter = true; S.rng.key[0] = (uint32_t)seed; S.rng.key[1] = (uint32_t)(seed >> 32);
+        std::vector<double> wv(w, w + n); std::vector<unsigned> rn; AllocDiag d;
+        allocate_reads(S, wv, (long)reads, rn, &d);
+        std::copy(rn.begin(), rn.end(), rn_out);
+        if (diag_out) {
+            memcpy(&diag_out[0], &d.total, 8); diag_out[1] = d.residual; diag_out[2] = d.leftover; diag_out[3] = d.quota.size();
+            for (size_t c = 0; c < d.quota.size(); ++c) diag_out[4 + c] = d.quota[c];
+        }
         return 0;
     } catch (const std::exception& e) { g_err = e.what(); return -1; }
 }

@@ -96,4 +96,11 @@ int scso_predict_counter_batch(void* h, const uint8_t* windows, int n, int count
 // empty template (tries used, 51 = gave up; position and length of the try that fit) and the GC factor of one GC percentage
 int scso_attach_tries_batch(unsigned length, int amin, int amax, int count, int counter, uint64_t seed, uint32_t* tries, uint32_t* spos, uint32_t* alen);
 int scso_gc_factor_batch(void* h, int gc, int count, int counter, uint64_t seed, double* out);
+// the read allocation's rule on given inputs, counter mode (tree_sum / scan_all / allocate_reads as the pipeline runs them).
+// scso_allocate_reads: n weights in whole-job list order -> rn_out[n]; diag_out (nullable, 4 + ceil(n / 1000) words): the bits of
+// the total, the residual reads after the floors, the leftover after the per-chunk quotas, the chunk count, every chunk's quota
+// before the leftover's draws
+int scso_tree_sum(const double* v, uint64_t n, double* out);
+int scso_scan_all(const double* v, uint64_t n, double* out);
+int scso_allocate_reads(const double* w, uint64_t n, uint64_t reads, int paired, uint64_t seed, int threads, uint32_t* rn_out, uint64_t* diag_out);
 }

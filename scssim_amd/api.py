@@ -289,6 +289,47 @@ def scan_probe(a0, a1=None, device=0):
     return o0 if a1 is None else (o0, o1)
 
 
+ALLOC_SLOTS = 40
+ALLOC_CHUNK = 1000
+
+
+def alloc_plan_probe(counts, rank):
+    """Host-only: the read allocation's plan of shard `rank` over counts[R][40] amplicons per (shard, slot), as do_allocate builds it:
+    dict of total, nch, n_interior, n_boundary, n_ranges, n_gseg, ac, scratch and the arrays ranges [n, 3] (q0, c0, local0),
+    bchunks [n, 3] (chunk, length, owner), gsegs [n, 5] (go, lo, n, owner, slot), my_seg [40, 4] (go, lo, n, order)."""
+    import numpy as np
+    L = load_library()
+    L.scs_alloc_plan_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    counts = np.ascontiguousarray(counts, np.uint64)
+    assert counts.ndim == 2 and counts.shape[1] == ALLOC_SLOTS
+    sc = (C.c_uint64 * 8)()
+    rc = L.scs_alloc_plan_probe(counts.ctypes.data, counts.shape[0], int(rank), sc, None, None, None, None)
+    if rc:
+        raise ScsError(rc, "scs_alloc_plan_probe")
+    out = dict(zip(("total", "nch", "n_interior", "n_boundary", "n_ranges", "n_gseg", "ac", "scratch"), (int(v) for v in sc)))
+    rng, bch = np.zeros((out["n_ranges"], 3), np.uint32), np.zeros((out["n_boundary"], 3), np.uint32)
+    gseg, mine = np.zeros((out["n_gseg"], 5), np.uint64), np.zeros((ALLOC_SLOTS, 4), np.uint64)
+    rc = L.scs_alloc_plan_probe(counts.ctypes.data, counts.shape[0], int(rank), sc, rng.ctypes.data, bch.ctypes.data, gseg.ctypes.data, mine.ctypes.data)
+    if rc:
+        raise ScsError(rc, "scs_alloc_plan_probe")
+    out.update(ranges=rng, bchunks=bch, gsegs=gseg, my_seg=mine)
+    return out
+
+
+def alloc_sums_probe(values, which, device=0):
+    """Test seam (needs a GPU): the allocation's fixed-shape sum (which = 0: a float) or inclusive scan (which = 1: an array) of the
+    float64 array `values`, with the scratch a job reserves for that many chunk partials."""
+    import numpy as np
+    L = load_library()
+    L.scs_alloc_sums_probe.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    v = np.ascontiguousarray(values, np.float64)
+    out = np.empty(v.size if which else 1, np.float64)
+    rc = L.scs_alloc_sums_probe(device, v.ctypes.data, v.size, int(which), out.ctypes.data)
+    if rc:
+        raise ScsError(rc, "scs_alloc_sums_probe: " + (L.scs_last_error(None) or b"").decode())
+    return out if which else float(out[0])
+
+
 def _truth_probe(fn, seq, qual, genome, pos0, n, events, reverse, genome_start, rname, amp, cnt, paired, is_read2, mate):
     L = load_library()
     f = getattr(L, fn)
@@ -786,6 +827,19 @@ class GenReads:
 
     def allocate_reads(self, reads=0):      # Malbac::setReadCounts
         self._ck(self._L.scs_allocate_reads(self._ctx, reads))
+
+    def alloc_probe(self, weights, seg_counts, reads):
+        """Test seam: the read allocation behind the weights on this (never amplified) ctx, over `weights` as this shard's list cut into
+        segments of seg_counts[40] amplicons; layout, seed, shard and collectives are the ctx's.  Returns (read numbers, pair offsets
+        [n + 1]); the ctx stays not allocated."""
+        np = self._np
+        self._L.scs_alloc_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        w = np.ascontiguousarray(weights, np.float64)
+        sc = np.ascontiguousarray(seg_counts, np.uint32)
+        assert sc.shape == (ALLOC_SLOTS,)
+        rn, po = np.zeros(max(1, w.size), np.uint32), np.zeros(w.size + 1, np.uint32)
+        self._ck(self._L.scs_alloc_probe(self._ctx, w.ctypes.data if w.size else None, w.size, sc.ctypes.data, int(reads), rn.ctypes.data, po.ctypes.data))
+        return rn[:w.size], po
 
     def yield_reads(self, collect=True):    # Malbac::yieldReads -> (fastq1, fastq2) bytes
         parts1, parts2 = [], []

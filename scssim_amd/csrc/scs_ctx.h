@@ -373,6 +373,7 @@ void do_create_frags(scs_ctx* c);
 void do_amplify(scs_ctx* c);
 // ---- scs_reads.cpp
 void do_allocate(scs_ctx* c, uint64_t reads);
+void allocate_weighted(scs_ctx* c, uint64_t reads, uint32_t ac);   // everything of do_allocate behind the weights: over the ac weights in c->weights
 struct CallbackSink : BatchSink {           // a caller's scs_sink_fn as a BatchSink: one region, the batches in record order
     scs_sink_fn fn; void* user;
     CallbackSink(scs_sink_fn f, void* u) : fn(f), user(u) {}

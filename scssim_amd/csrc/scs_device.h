@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "scs_common.h"
 #include "scs_simuvars.h"
+#include "scs_alloc_plan.h"
 
 namespace scs {
 
@@ -85,16 +86,8 @@ enum { DS_SEMI_LEN = 4, DS_SEMIS_N = 5, DS_REPORTED_LEN = 6, DS_G_SEMIS_N = 8, D
 enum { SHARD_TAIL_WORDS = 16 };                       // u32 words behind the 65536 primer decrements that ride on the same all-reduce
 struct AllocState { double total; unsigned long long sum_rn, sum_quota; };
 
-// ---- read allocation over the whole job's amplicon list, computed by the shards (scs_k_allocate.hip, K3) ---------------
-// The list is cut into chunks of 1000 (randIndx_hp's chunks, MyDefine.cpp:203-253).  A shard's local list is the
-// concatenation of its segments (cycle ascending, fragment pass descending: slot = cycle * 8 + (7 - pass)); the whole
-// job's list interleaves the shards' segments slot by slot (order = slot * shards + rank).
-#define ALLOC_CHUNK 1000u
-enum { ALLOC_SLOTS = 40 };
-struct AllocRange { uint32_t q0, c0, local0; };            // work chunks q0.. (up to the next range) = whole-job chunks c0.., in place at local0 + 1000 (q - q0)
-struct AllocBChunk { uint32_t c, n, owner; };              // a chunk that straddles a segment boundary: materialised row; owner: this shard holds its first amplicon
-struct AllocGSeg { unsigned long long go; uint32_t lo, n, owner, slot; };   // every non-empty segment of every shard, in list order
-struct AllocMySeg { unsigned long long go; uint32_t lo, n, order, pad; };  // this shard's segment of slot s
+// ---- read allocation over the whole job's amplicon list, computed by the shards (scs_k_allocate.hip, K3): chunks, segments and the
+// host plan are in scs_alloc_plan.h; what the kernels take of it:
 struct AllocPlan {
     unsigned long long total;                              // amplicons of the whole job
     uint32_t rank, n_interior, n_boundary, n_ranges, n_gseg;
@@ -132,11 +125,12 @@ void launch_poisson(hipStream_t s, DevFrags fr, DevAmps semis, uint32_t n_semis,
 void launch_alloc_bpack(hipStream_t s, const double* w, const AllocPlan& pl, double* send);
 void launch_alloc_bgather(hipStream_t s, const double* w, const AllocPlan& pl, const double* gathered, double* brow, int* bmap);
 void launch_alloc_chunk_sum(hipStream_t s, const double* w, const double* brow, const AllocPlan& pl, double* part);
-void launch_tree_sum(hipStream_t s, const double* part, uint32_t nch, double* scratch, double* total);     // scratch: nch/1000 + 1024 doubles
+void launch_tree_sum(hipStream_t s, const double* part, uint32_t nch, double* scratch, double* total);     // scratch: alloc_tree_scratch(nch) doubles
+void launch_scan_all(hipStream_t s, const double* in, uint32_t n, double* out, double* scratch);           // scan_all as launch_alloc_quota runs it over tp[]; scratch: the same
 void launch_alloc_norm(hipStream_t s, double* w, double* brow, const int* bmap, const AllocPlan& pl, const double* total, unsigned long long reads,
                        uint32_t* rn, double* tp, uint32_t* crn, unsigned long long* sum_rn);
 void launch_alloc_quota(hipStream_t s, const double* tp, uint32_t nch, unsigned long long reads, const unsigned long long* sum_rn, unsigned long long* sum_quota,
-                        uint32_t* quota, double* probs, double* scratch, RngKey key);   // scratch: 3 * (nch / 1000) + 4096 doubles
+                        uint32_t* quota, double* probs, double* scratch, RngKey key);   // scratch: alloc_tree_scratch(nch) doubles
 void launch_alloc_sample(hipStream_t s, const double* w, const double* brow, const int* bmap, const AllocPlan& pl, const double* tp, const uint32_t* quota, RngKey key, uint32_t* rn);
 void launch_alloc_odd_scan(hipStream_t s, const uint32_t* rn, uint32_t ac, uint32_t* odd_before, void* temp, size_t temp_bytes);
 void launch_alloc_odd_counts(hipStream_t s, const uint32_t* odd_before, const AllocPlan& pl, unsigned long long* table);

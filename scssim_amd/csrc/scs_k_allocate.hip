@@ -229,9 +229,9 @@ __global__ void __launch_bounds__(64) k_scan1000(const double* __restrict__ in, 
 #pragma unroll
         for (int d = 1; d < WAVE; d <<= 1) { const double t = shfl_up_f64(s, d); if ((int)lane >= d) s = s + t; }
         if (r + lane < m) out[b + r + lane] = carry + s;
+        if (last && r + lane == m - 1) last[g] = carry + s;                             // out[b + m - 1] itself: in a short last row, lane 63's sum over the zeros beyond m is the same terms in another association
         carry = carry + shfl_f64(s, 63);
     }
-    if (lane == 0 && last) last[g] = carry;                                         // == out[b + m - 1]: zeros beyond m add nothing
 }
 // scan_all, fix-up: out[i] = pre[g-1] + out[i] for the groups g >= 1
 __global__ void __launch_bounds__(256) k_scan_fix(double* __restrict__ out, uint32_t n, const double* __restrict__ pre) {
@@ -388,6 +388,7 @@ static void scan_all_dev(hipStream_t s, const double* in, uint32_t n, double* ou
     scan_all_dev(s, last, ng, pre, scratch + 2 * (size_t)ng);
     hipLaunchKernelGGL(k_scan_fix, dim3(cdiv(n, 256)), dim3(256), 0, s, out, n, pre);
 }
+void launch_scan_all(hipStream_t s, const double* in, uint32_t n, double* out, double* scratch) { if (n) scan_all_dev(s, in, n, out, scratch); }
 // per-chunk quotas of the residual reads, the CDF over the chunks and the leftover draws (MyDefine.cpp:225-245): every
 // shard computes them for ALL chunks of the job from the all-reduced tp[] (8 B per 1000 amplicons)
 void launch_alloc_quota(hipStream_t s, const double* tp, uint32_t nch, unsigned long long reads, const unsigned long long* sum_rn, unsigned long long* sum_quota,

@@ -460,6 +460,73 @@ int scs_scan_probe(int device, const uint32_t* in0, uint64_t n0, const uint32_t*
         return SCS_OK;
     } catch (const std::exception& e) { create_error() = e.what(); return SCS_EDEVICE; }
 }
+// host-only test seam: the read allocation's plan of shard `rank` (alloc_plan_build, scs_alloc_plan.h: what do_allocate runs) over the
+// table counts[r * 40 + slot], R shards.  scalars: total, chunks of the job, n_interior, n_boundary, n_ranges, n_gseg, this shard's
+// amplicons, the scratch doubles reserved for that many chunks.  The arrays (all NULL: the scalars alone; else each at least as long
+// as the scalars say): ranges as q0, c0, local0; bchunks as c, n, owner; gsegs as go, lo, n, owner, slot; my_seg[40] as go, lo, n, order
+int scs_alloc_plan_probe(const uint64_t* counts, int R, int rank, uint64_t scalars[8], uint32_t* ranges, uint32_t* bchunks, uint64_t* gsegs, uint64_t* my_seg) {
+    if (!counts || !scalars || R < 1 || R > 4096 || rank < 0 || rank >= R) return SCS_EINVAL;
+    AllocHostPlan P;
+    if (!alloc_plan_build(counts, R, rank, P)) return SCS_EOVERFLOW;
+    scalars[0] = P.total; scalars[1] = P.nch; scalars[2] = P.n_interior; scalars[3] = P.bch.size(); scalars[4] = P.rng.size(); scalars[5] = P.gseg.size();
+    scalars[6] = P.ac; scalars[7] = alloc_tree_scratch(P.nch);
+    if (ranges) for (size_t i = 0; i < P.rng.size(); ++i) { ranges[3 * i] = P.rng[i].q0; ranges[3 * i + 1] = P.rng[i].c0; ranges[3 * i + 2] = P.rng[i].local0; }
+    if (bchunks) for (size_t i = 0; i < P.bch.size(); ++i) { bchunks[3 * i] = P.bch[i].c; bchunks[3 * i + 1] = P.bch[i].n; bchunks[3 * i + 2] = P.bch[i].owner; }
+    if (gsegs) for (size_t i = 0; i < P.gseg.size(); ++i) { const AllocGSeg& g = P.gseg[i]; gsegs[5 * i] = g.go; gsegs[5 * i + 1] = g.lo; gsegs[5 * i + 2] = g.n; gsegs[5 * i + 3] = g.owner; gsegs[5 * i + 4] = g.slot; }
+    if (my_seg) for (int sl = 0; sl < ALLOC_SLOTS; ++sl) { const AllocMySeg& m = P.my_seg[sl]; my_seg[4 * sl] = m.go; my_seg[4 * sl + 1] = m.lo; my_seg[4 * sl + 2] = m.n; my_seg[4 * sl + 3] = m.order; }
+    return SCS_OK;
+}
+// device test seam: the allocation's fixed-shape sums over n uploaded doubles, with the scratch do_allocate reserves for n chunk
+// partials (alloc_tree_scratch) and guards behind it and behind the output.  which = 0: launch_tree_sum, one double out;
+// which = 1: launch_scan_all, n doubles out
+int scs_alloc_sums_probe(int device, const double* in, uint64_t n, int which, double* out) {
+    if (!in || !out || !n || n > 0x7FFFFFF0ull || (which != 0 && which != 1)) return SCS_EINVAL;
+    try {
+        HIP_OK(hipSetDevice(device));
+        ProbeMem mem;
+        const size_t n_out = which ? (size_t)n : 1, n_scr = alloc_tree_scratch((size_t)n), guard = kProbeGuard / 8;
+        double* d_in = (double*)mem.get((size_t)n * 8); double* d_out = (double*)mem.get((n_out + guard) * 8); double* d_scr = (double*)mem.get((n_scr + guard) * 8);
+        HIP_OK(hipMemcpy(d_in, in, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(d_out, kProbeFill, (n_out + guard) * 8)); HIP_OK(hipMemset(d_scr, kProbeFill, (n_scr + guard) * 8));
+        HIP_OK(hipDeviceSynchronize());
+        if (which) launch_scan_all(nullptr, d_in, (uint32_t)n, d_out, d_scr);
+        else launch_tree_sum(nullptr, d_in, (uint32_t)n, d_scr, d_out);
+        probe_sync();
+        std::vector<uint64_t> h(n_out + guard), g(guard);
+        HIP_OK(hipMemcpy(h.data(), d_out, h.size() * 8, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(g.data(), d_scr + n_scr, guard * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < guard; ++i) if (h[n_out + i] != 0xA5A5A5A5A5A5A5A5ull || g[i] != 0xA5A5A5A5A5A5A5A5ull) throw ScsError(SCS_EDEVICE, "allocation sums probe: a kernel wrote behind its output or behind the scratch");
+        memcpy(out, h.data(), n_out * 8);
+        return SCS_OK;
+    } catch (const std::exception& e) { create_error() = e.what(); return SCS_EDEVICE; }
+}
+// device test seam: the allocation (allocate_weighted: everything of scs_allocate_reads behind the weights) over n_local given weights as
+// this shard's list, cut into segments of seg_counts[slot] amplicons, on a ctx that was never amplified -- its layout, seed, shard rank
+// and collectives are the job's.  rn_out[n_local], pair_off_out[n_local + 1].  The ctx is left as it was: not allocated
+int scs_alloc_probe(scs_ctx* c, const double* w_local, uint64_t n_local, const uint32_t* seg_counts, uint64_t reads, uint32_t* rn_out, uint32_t* pair_off_out) {
+    return guarded(c, [&] {
+        if (!seg_counts || !pair_off_out || (n_local && (!w_local || !rn_out)) || n_local > 0xFFFFFFF0ull || reads > 0x7FFFFFFFFFFFFFFFull) throw ScsError(SCS_EINVAL, "scs_alloc_probe: bad argument");
+        if (c->amplified || c->allocated) throw ScsError(SCS_EINVAL, "scs_alloc_probe: the ctx holds a job");
+        uint64_t sum = 0; for (int sl = 0; sl < ALLOC_SLOTS; ++sl) sum += seg_counts[sl];
+        if (sum != n_local) throw ScsError(SCS_EINVAL, "scs_alloc_probe: the segments do not add up to n_local");
+        hipStream_t s = c->stream; const uint32_t ac = (uint32_t)n_local;
+        struct Keep {                                                              // what allocate_weighted leaves on the ctx, put back on every way out
+            scs_ctx* c; std::vector<scs_ctx::Seg> segs; SegMap gmap; uint64_t pairs; uint32_t seg_lo[ALLOC_SLOTS + 1];
+            explicit Keep(scs_ctx* x) : c(x), segs(x->full_segs), gmap(x->gmap), pairs(x->n_pairs_planned) { memcpy(seg_lo, x->seg_lo, sizeof seg_lo); }
+            ~Keep() { c->full_segs.swap(segs); c->gmap = gmap; c->n_pairs_planned = pairs; memcpy(c->seg_lo, seg_lo, sizeof seg_lo); }
+        } keep(c);
+        c->full_segs.clear();
+        for (int sl = 0; sl < ALLOC_SLOTS; ++sl) if (seg_counts[sl]) c->full_segs.push_back(scs_ctx::Seg{sl / 8, 7 - sl % 8, seg_counts[sl]});
+        c->weights.reserve(std::max<size_t>((size_t)ac * 8, 16), s);
+        c->read_numbers.reserve(((size_t)ac + 1) * 4, s); c->pair_off.reserve(((size_t)ac + 1) * 4, s);
+        if (ac) HIP_OK(hipMemcpyAsync(c->weights.p, w_local, (size_t)ac * 8, hipMemcpyHostToDevice, s));
+        allocate_weighted(c, reads, ac);
+        if (ac) HIP_OK(hipMemcpyAsync(rn_out, c->read_numbers.p, (size_t)ac * 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(pair_off_out, c->pair_off.p, ((size_t)ac + 1) * 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        const hipError_t le = take_launch_error();
+        if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("scs_alloc_probe: kernel launch failed: ") + hipGetErrorString(le));
+    });
+}
 int scs_profile_open(const char* path, int paired, int isize, void** handle, char* errbuf, size_t errlen) {
     if (!path || !handle) return SCS_EINVAL;
     ProfileTables* T = new ProfileTables;

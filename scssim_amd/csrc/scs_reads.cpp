@@ -19,45 +19,31 @@ void do_allocate(scs_ctx* c, uint64_t reads) {
     c->weights.reserve(std::max<size_t>((size_t)ac * 8, 16), s);
     c->read_numbers.reserve(((size_t)ac + 1) * 4, s); c->pair_off.reserve(((size_t)ac + 1) * 4, s);
     launch_weights(s, c->fulls.view(), ac, c->dtb, c->key, (uint32_t)c->cfg.frag_size, c->weights.as<double>());
+    allocate_weighted(c, reads, ac);
+    c->st.t_stage[3] = 0; c->st.t_stage[4] = now_s() - t0;
+    c->allocated = true;
+}
+
+// the allocation over the weights already in c->weights (ac of them, this shard's list segments in c->full_segs): everything of
+// setReadCounts behind the weights.  do_allocate runs it on a job's weights, scs_alloc_probe on given ones
+void allocate_weighted(scs_ctx* c, uint64_t reads, uint32_t ac) {
+    hipStream_t s = c->stream;
     double* d_w = c->weights.as<double>(); uint32_t* d_rn = c->read_numbers.as<uint32_t>();
 
-    // ---- the plan: where the chunks of the whole job's list lie relative to this shard's list.
+    // ---- the plan: where the chunks of the whole job's list lie relative to this shard's list (alloc_plan_build, scs_alloc_plan.h).
     // slot = cycle * 8 + (7 - fragment pass): this shard's segments in local order; the whole job's list takes the
     // shards' segments slot by slot, shard by shard
     const int R = c->cfg.shard_count, me = c->cfg.shard_rank; const bool multi = c->sharded();
     std::vector<uint64_t> segc((size_t)R * ALLOC_SLOTS, 0);
     for (auto& sg : c->full_segs) { if (sg.c < 0 || sg.c >= 5 || sg.p < 0 || sg.p >= 8) throw ScsError(SCS_EINVAL, "allocation: segment out of range"); segc[(size_t)me * ALLOC_SLOTS + sg.c * 8 + (7 - sg.p)] += sg.count; }
     if (multi) c->reduce(segc.data(), segc.size());
-    std::vector<AllocGSeg> gseg; std::vector<uint32_t> loff(R, 0); uint64_t total = 0;
+    AllocHostPlan hp;
+    if (!alloc_plan_build(segc.data(), R, me, hp)) throw ScsError(SCS_EOVERFLOW, "more than 2^32 amplicons in the whole job");
+    if (hp.ac != ac) throw ScsError(SCS_EINVAL, "sharded allocation: segment bookkeeping mismatch");
+    const std::vector<AllocRange>& rng = hp.rng; const std::vector<AllocBChunk>& bch = hp.bch; const std::vector<AllocGSeg>& gseg = hp.gseg;
+    const uint64_t total = hp.total; const uint32_t nch = hp.nch, nq = hp.n_interior;
     AllocPlan pl{}; pl.rank = (uint32_t)me;
-    for (int sl = 0; sl < ALLOC_SLOTS; ++sl) for (int r = 0; r < R; ++r) {
-        const uint64_t n = segc[(size_t)r * ALLOC_SLOTS + sl];
-        if (r == me) pl.my_seg[sl] = AllocMySeg{total, loff[r], (uint32_t)n, (uint32_t)(sl * R + r), 0};
-        if (!n) continue;
-        gseg.push_back(AllocGSeg{total, loff[r], (uint32_t)n, (uint32_t)r, (uint32_t)sl});
-        loff[r] += (uint32_t)n; total += n;
-    }
-    if (loff[me] != ac) throw ScsError(SCS_EINVAL, "sharded allocation: segment bookkeeping mismatch");
-    if (total > 0xFFFFFFF0ull) throw ScsError(SCS_EOVERFLOW, "more than 2^32 amplicons in the whole job");
-    const uint32_t nch = (uint32_t)((total + ALLOC_CHUNK - 1) / ALLOC_CHUNK);
-    std::vector<AllocRange> rng; std::vector<AllocBChunk> bch; uint32_t nq = 0;
-    {
-        auto owner_of = [&](uint64_t gi) { size_t lo = 0, hi = gseg.size(); while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if (gseg[mid].go <= gi) lo = mid; else hi = mid; } return gseg[lo].owner; };
-        auto add_boundary = [&](uint32_t ch) { for (auto& b : bch) if (b.c == ch) return; bch.push_back(AllocBChunk{ch, (uint32_t)std::min<uint64_t>(ALLOC_CHUNK, total - (uint64_t)ch * ALLOC_CHUNK), owner_of((uint64_t)ch * ALLOC_CHUNK) == (uint32_t)me ? 1u : 0u}); };
-        for (size_t k = 0; k < gseg.size();) {                                    // my segments, merged while they are contiguous in the whole list
-            if (gseg[k].owner != (uint32_t)me) { ++k; continue; }
-            uint64_t go = gseg[k].go, n = gseg[k].n; const uint32_t lo = gseg[k].lo; size_t j = k + 1;
-            while (j < gseg.size() && gseg[j].owner == (uint32_t)me && gseg[j].go == go + n) { n += gseg[j].n; ++j; }
-            k = j;
-            const uint64_t cA = (go + ALLOC_CHUNK - 1) / ALLOC_CHUNK, cB = go + n == total ? nch : (go + n) / ALLOC_CHUNK;   // whole chunks inside [go, go+n)
-            if (cA < cB) { rng.push_back(AllocRange{nq, (uint32_t)cA, (uint32_t)(lo + (cA * ALLOC_CHUNK - go))}); nq += (uint32_t)(cB - cA); }
-            if (cA >= cB) { for (uint64_t ch = go / ALLOC_CHUNK; ch <= (go + n - 1) / ALLOC_CHUNK; ++ch) add_boundary((uint32_t)ch); }   // shorter than a chunk (or two partial ones)
-            else {
-                if (go % ALLOC_CHUNK) add_boundary((uint32_t)(go / ALLOC_CHUNK));
-                if (cB * ALLOC_CHUNK < go + n) add_boundary((uint32_t)cB);
-            }
-        }
-    }
+    for (int sl = 0; sl < ALLOC_SLOTS; ++sl) pl.my_seg[sl] = hp.my_seg[sl];
     pl.total = total; pl.n_interior = nq; pl.n_boundary = (uint32_t)bch.size(); pl.n_ranges = (uint32_t)rng.size(); pl.n_gseg = (uint32_t)gseg.size();
     const uint32_t nwork = pl.n_interior + pl.n_boundary;
     {   // the plan's arrays: one small upload
@@ -76,7 +62,7 @@ void do_allocate(scs_ctx* c, uint64_t reads) {
     if (multi) { uint32_t k = 0; for (int sl = 0; sl < ALLOC_SLOTS; ++sl) if (pl.my_seg[sl].n) { c->gmap.lo[k] = pl.my_seg[sl].lo; c->gmap.cnt[k] = pl.my_seg[sl].n; c->gmap.go[k] = pl.my_seg[sl].go; ++k; } c->gmap.n = k; }
 
     // ---- buffers: per-chunk partials of the WHOLE job (8 B per 1000 amplicons), per-work-chunk partials of this shard
-    const size_t tree_scratch = (size_t)nch / ALLOC_CHUNK * 3 + 4096;
+    const size_t tree_scratch = alloc_tree_scratch(nch);
     c->a_part.reserve(((size_t)nch + 2) * 8, s); c->a_tp.reserve(((size_t)nch + 2) * 8, s); c->a_probs.reserve(((size_t)nch + 2) * 8, s);
     c->a_quota.reserve(((size_t)nch + 2) * 4, s); c->a_crn.reserve(((size_t)nwork + 2) * 4, s); c->a_scratch.reserve(tree_scratch * 8, s);
     c->a_brow.reserve(std::max<size_t>((size_t)pl.n_boundary * ALLOC_CHUNK * 8, 16), s); c->a_bmap.reserve(std::max<size_t>((size_t)pl.n_boundary * ALLOC_CHUNK * 4, 16), s);
@@ -116,8 +102,6 @@ void do_allocate(scs_ctx* c, uint64_t reads) {
     { Mail m; m.add(ac ? (const void*)(c->pair_off.as<uint32_t>() + ac) : nullptr, 4, 0); mail_post(c, m, true); }
     mail_wait(c);
     c->n_pairs_planned = (uint32_t)c->h_rb[0];
-    c->st.t_stage[3] = 0; c->st.t_stage[4] = now_s() - t0;
-    c->allocated = true;
 }
 
 // ---------------------------------------------------------------- a10/a11/a13/a16: yieldReads
