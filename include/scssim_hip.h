@@ -559,6 +559,49 @@ int         scs_support_read_probe(int n, int64_t pos0, int reverse, const int32
                                    const uint64_t* positions, uint64_t n_pos, uint64_t* index, uint8_t* cls, int cap, int* n_out);
 int         scs_site_support_line_probe(const char* name, uint64_t pos, uint32_t ref, uint32_t alt, uint32_t na, uint32_t ta, uint64_t nr, uint64_t tr,
                                         const uint32_t* counts, char* out, size_t cap, size_t* n_out);
+/* ---- site support on the original reference: the same counters at the sites of scs_artefact_ref_sites, by reference position -----
+ * scs_set_site_support_ref(ctx, 1, min_reads): every later yield call makes the site table scs_artefact_ref_sites(ctx, min_reads, ..)
+ * reports (same sites, order, REF, ALT, NA / TA / NR / TR and unlifted totals; kept on the device), the distinct reference positions
+ * X = ref_off[ref_rec] + pos of its sites, and every staged index g that lies in an R segment of the lift table and lifts to one of
+ * them -- on every haplotype record and tandem copy, with or without an artefact there (at most 2^29 - 1 staged positions,
+ * SCS_EOVERFLOW beyond -- raise min_reads).  The batches count at the staged positions exactly as scs_set_site_support's do; after the
+ * last batch the six counters of a reference position are the sums over the staged positions under it.  So a read that covers two
+ * tandem copies of X counts once per copy (as its pieces count in TA); a read on a haplotype where X is deleted by a planted variant
+ * or lies in a CN-0 stretch has no staged base under X and counts nowhere, not in DL either (DL: sequencing deletions only); bases in
+ * inserted sequence count nowhere; bases the truth SAM on the reference soft-clips still count.  Needs a lift table and an unsharded
+ * ctx: otherwise the yield call fails with SCS_EINVAL naming this setter; 2^32 planned reads or more: SCS_EINVAL.  A segment that
+ * lifts outside its reference record, staged positions that do not ascend or a reference counter that would pass 2^32 - 1 fail the
+ * call with SCS_EOVERFLOW, never a wrong or wrapped count.  One table per yield call: switching this one on while
+ * scs_set_site_support is on, or the other way round, is SCS_EINVAL naming both setters; switching one off does not touch the other.
+ * Lifetime, ownership and where it works: as scs_set_site_support; (ctx, 0, ..) releases every buffer of it.
+ * scs_site_support_ref: as scs_site_support (ref_rec: the reference record); unlifted (may be NULL) as scs_artefact_ref_sites.
+ * scs_write_site_support_ref: scs_write_artefacts_ref's file at the same min_reads with the three ##INFO lines DP, AD, DL behind its
+ * four and ";DP=d;AD=r,a;DL=x" at the end of every line; flags and errors as scs_write_site_support.
+ * scs_site_support_ref_kernel_time: the last yield call's k_support launches, as scs_site_support_kernel_time.
+ * scs_site_support_ref_step_time: step 0 the expansion behind the site table (position list, ranges, scan, fill; units: staged
+ * positions) -- ONE event pair around the whole stretch, with the host's waits for its two totals and its stream synchronisations
+ * inside it, so its milliseconds are an upper bound of the kernels' time, not their sum; step 1 the gather, one launch (units:
+ * staged positions); any other step is SCS_EINVAL.
+ * Memory: beside what scs_set_site_support holds per site, 36 bytes per STAGED position (its index, its reference position, six
+ * counters) and 32 per reference position stay allocated from the first yield call until the feature is switched off. */
+int         scs_set_site_support_ref(scs_ctx* ctx, int on, uint32_t min_reads);
+int         scs_site_support_ref(scs_ctx* ctx, uint32_t* ref_rec, uint64_t* pos, uint8_t* ref, uint8_t* alt, uint32_t* na, uint32_t* ta, uint64_t* nr, uint64_t* tr,
+                                 uint32_t* counts /* 6 per site */, uint64_t cap, uint64_t* n, uint64_t unlifted[2]);
+int         scs_write_site_support_ref(scs_ctx* ctx, const char* path, int flags, uint64_t* sites, uint64_t* bytes);
+int         scs_site_support_ref_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+int         scs_site_support_ref_step_time(const scs_ctx* ctx, int step, uint64_t* launches, double* ms, uint64_t* units);
+/* Host-only test seams of that table (no GPU, no ctx).  scs_support_ref_probe: the expansion and the gather through the functions the
+ * kernels run: the lift table as five arrays, the staged and the reference records' lengths, x = the n_x listed reference positions
+ * (ascending, distinct), chunk = output slots per fill pass (0: all), g_counts = six counters per staged index of the whole genome
+ * (or NULL: no gather).  sp_pos / sp_pos_x receive the staged positions and the index of each one's reference position (cap entries;
+ * *n_staged their number, SCS_EOVERFLOW when cap is too small), ref_counts 6 n_x sums.  SCS_EINVAL with *why: 2 a segment that does not
+ * follow the last, holds no base or leaves its staged record, 3 a segment past its reference record, 4 listed positions out of order or
+ * outside the reference, 5 staged positions that do not ascend, 6 a counter past 2^32 - 1.  scs_support_ref_header_probe: the file's
+ * header. */
+int         scs_support_ref_probe(const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                                  const uint64_t* hap_len, uint32_t n_hap, const uint64_t* ref_len, uint32_t n_ref, const uint64_t* x, uint64_t n_x, uint64_t chunk, const uint32_t* g_counts,
+                                  uint64_t* sp_pos, uint32_t* sp_pos_x, uint64_t cap, uint64_t* n_staged, uint32_t* ref_counts, int* why);
+int         scs_support_ref_header_probe(const uint64_t* ref_len, const char* const* ref_names, uint32_t n_ref, uint64_t unl_entries, uint64_t unl_reads, char* out, size_t cap, size_t* n_out);
 /* The fragments of scs_create_frags (Fragment, lib/fragment/Fragment.h:20-31): genome offset of each slice (records concatenated
  * in staging order), its length and strand (+1 / -1); arrays of scs_stats.fragments entries, any pointer may be NULL. */
 int         scs_download_frags(scs_ctx* ctx, uint64_t* goff, uint32_t* len, int8_t* strand);

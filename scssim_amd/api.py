@@ -675,6 +675,60 @@ def artefact_ref_probe(starts, lens, reads, edits, hap_lens, genome, table, ref_
     return out.raw[:n.value].decode(), (int(unl[0]), int(unl[1]))
 
 
+def support_ref_probe(table, hap_lens, ref_lens, x, chunk=0, g_counts=None):
+    """Host-only: the expansion of the site support table on the reference (and, with g_counts, its gather) through the functions
+    the kernels run.  table: a LiftTable (or any object with its five arrays); hap_lens / ref_lens: the staged and the reference
+    records; x: the listed reference positions X, ascending and distinct; chunk: output slots per fill pass (0: all at once);
+    g_counts: uint32 [staged bases, 6], the counters of every staged index.  Returns (staged positions, the index into x of each,
+    uint32 [len(x), 6] sums or None).  A refused input raises ScsError (SCS_EINVAL) whose .why says which check failed."""
+    import numpy as np
+    L = load_library()
+    L.scs_support_ref_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_int)]
+    seg = [np.ascontiguousarray(getattr(table, k), t) for k, t in (("hap_off", np.uint64), ("len", np.uint64), ("ref_pos", np.uint64), ("ref_rec", np.uint32), ("kind", np.uint32))]
+    h_l, r_l = np.ascontiguousarray(list(hap_lens), np.uint64), np.ascontiguousarray(list(ref_lens), np.uint64)
+    xs = np.ascontiguousarray(x, np.uint64).reshape(-1)
+    gc = None if g_counts is None else np.ascontiguousarray(g_counts, np.uint32)
+    if gc is not None and gc.shape != (int(h_l.sum()), 6):
+        raise ValueError("g_counts is [staged bases, 6]")
+    head = [a.ctypes.data for a in seg] + [len(seg[0]), h_l.ctypes.data, len(h_l), r_l.ctypes.data, len(r_l), xs.ctypes.data if len(xs) else None, len(xs), int(chunk),
+                                           None if gc is None else gc.ctypes.data]
+    n, why = C.c_uint64(), C.c_int()
+
+    def refuse(rc):
+        e = ScsError(rc, "scs_support_ref_probe: " + {2: "a segment that does not follow the last, holds no base or leaves its staged record", 3: "a segment past its reference record",
+                                                      4: "listed positions out of order or outside the reference", 5: "staged positions that do not ascend",
+                                                      6: "a counter past 2^32 - 1"}.get(why.value, "tables that do not fit each other"))
+        e.why = why.value
+        return e
+    rc = L.scs_support_ref_probe(*head, None, None, 0, C.byref(n), None, C.byref(why))
+    if rc and not (rc == SCS_EOVERFLOW and n.value):
+        raise refuse(rc)
+    pos, pos_x = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+    out = None if gc is None else np.zeros((len(xs), 6), np.uint32)
+    rc = L.scs_support_ref_probe(*head, pos.ctypes.data, pos_x.ctypes.data, n.value, C.byref(n), None if out is None else out.ctypes.data, C.byref(why))
+    if rc:
+        raise refuse(rc)
+    return pos, pos_x, out
+
+
+def support_ref_header_probe(ref_names, ref_lens, unlifted=(0, 0)):
+    """Host-only: the header of the site support table on the reference, as write_site_support_ref writes it."""
+    import numpy as np
+    L = load_library()
+    L.scs_support_ref_header_probe.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    r_l = np.ascontiguousarray(list(ref_lens), np.uint64)
+    names = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
+    n = C.c_size_t()
+    args = [r_l.ctypes.data, names, len(ref_names), int(unlifted[0]), int(unlifted[1])]
+    if L.scs_support_ref_header_probe(*args, None, 0, C.byref(n)):
+        raise ScsError(SCS_EINVAL, "scs_support_ref_header_probe")
+    out = C.create_string_buffer(max(1, n.value))
+    if L.scs_support_ref_header_probe(*args, out, n.value, C.byref(n)):
+        raise ScsError(SCS_EINVAL, "scs_support_ref_header_probe")
+    return out.raw[:n.value].decode()
+
+
 def fasta_probe(path):
     """Host-only: (names, total bases, FNV-1a checksum of the upper-cased sequence) as the library stages the file."""
     L = load_library()
@@ -1078,6 +1132,40 @@ class GenReads:
         n, b = C.c_uint64(), C.c_uint64()
         self._ck(self._L.scs_write_site_support(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n), C.byref(b)))
         return dict(sites=n.value, bytes=b.value)
+
+    def set_site_support_ref(self, on, min_reads=0):
+        """Site support by site of the ORIGINAL REFERENCE on / off (needs a lift table at the yield call): every later yield call
+        counts, on the GPU, what its reads show at every staged position that lifts to a reference position of
+        artefact_ref_sites(min_reads), and sums the six counters by reference position.  Not together with set_site_support."""
+        self._L.scs_set_site_support_ref.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        self._ck(self._L.scs_set_site_support_ref(self._ctx, 1 if on else 0, int(min_reads)))
+
+    def site_support_ref(self):
+        """The last yield call's sites and counters as a dict of numpy arrays, one entry per site in file order: artefact_ref_sites'
+        arrays (unlifted included) and counts, uint32 [sites, 6], summed over every haplotype record and copy of the site."""
+        u = (C.c_uint64 * 2)()
+        a = self._sites_into_arrays("scs_site_support_ref", "ref_rec", counts=True, tail=(u,))
+        a["unlifted"] = (int(u[0]), int(u[1]))
+        return a
+
+    def write_site_support_ref(self, path, bgzf=False):
+        """write_artefacts_ref's file of the same min_reads with DP / AD / DL of the last yield call's reads at the end of every
+        line, made on the GPU.  Returns dict(sites=, bytes=)."""
+        self._L.scs_write_site_support_ref.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        n, b = C.c_uint64(), C.c_uint64()
+        self._ck(self._L.scs_write_site_support_ref(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n), C.byref(b)))
+        return dict(sites=n.value, bytes=b.value)
+
+    def site_support_ref_kernel_time(self, step=None):
+        """Event pairs (one per batch), milliseconds and pairs of the last yield call's k_support launches with the table on the
+        reference on; step=0: the expansion behind the site table, step=1: the gather (units: staged positions)."""
+        if step is None:
+            return self._kernel_time("scs_site_support_ref_kernel_time")
+        fn = self._L.scs_site_support_ref_step_time
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(fn(self._ctx, int(step), C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
 
     # ---- lift table and depth by reference bin
     def write_lift(self, path):

@@ -284,6 +284,14 @@ struct scs_ctx {
     // of every call; support_valid: a call with it on has finished) and the kernel's record starts
     bool support_on = false, support_valid = false; uint32_t support_min_reads = 0; uint64_t sp_n_sites = 0, sp_n_pos = 0;
     DevBuf sp_sites, sp_site_pos, sp_pos, sp_cnt, sp_tab;
+    // the same table on the original reference (scs_set_site_support_ref): support_on with support_ref.  The
+    // sites are then the reference table's (rec = reference record), sp_site_pos indexes the distinct reference positions spr_x
+    // (sp_n_x of them, six counters each in spr_cnt, summed after the last batch), and sp_pos / sp_cnt are the staged positions
+    // that lift to them (sp_n_pos) and their counters, sp_pos_x every staged position's reference position; spr_tab: the
+    // reference records' starts; sp_unlifted: the reference table's two unlifted totals (its header states them)
+    bool support_ref = false; uint64_t sp_n_x = 0, sp_unlifted[2] = {0, 0};
+    DevBuf spr_x, spr_cnt, sp_pos_x, spr_tab;
+    KernelTimer tm_support_ref_open{"k_support_ref_open"}, tm_support_ref_gather{"k_support_ref_gather"};   // the last yield call's expansion (heads .. fill) and gather (scs_site_support_ref_step_time)
     KernelTimer tm_support{"k_support"};                  // the last yield call's k_support launches (scs_site_support_kernel_time; not one of tm[])
     KernelTimer tm_site{"k_sites"};                       // the last scs_write_artefacts call's kernels (scs_artefact_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
     KernelTimer tm_site_ref{"k_sites_ref"};               // the last scs_write_artefacts_ref call's kernels (scs_artefact_ref_kernel_time); the call's buffers live and die with it (scs_sites.cpp)
@@ -336,7 +344,7 @@ struct scs_ctx {
     scs_stats st{};
     KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}, {"k_depth"}};
     // the timers a yield call runs: reset at its start, collected at its end.  A new side output's timer is one more entry here
-    std::array<KernelTimer*, 6> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref}; }
+    std::array<KernelTimer*, 8> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref, &tm_support_ref_open, &tm_support_ref_gather}; }
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
@@ -407,6 +415,10 @@ void need_lift(const scs_ctx* c, const char* fn);
 // site support (scs_support.cpp): refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call; the call's site table, positions and zeroed counters
 void support_check(scs_ctx* c);
 void support_open(scs_ctx* c);
+// the table on the reference alone, after the last batch: the staged counters summed by reference position, on the ctx stream
+void support_close(scs_ctx* c);
+// "site support (scs_set_site_support)", or the reference table's name: what the yield call's refusals open with
+std::string support_name(const scs_ctx* c);
 std::vector<int> gpu_local_cpus(int device);   // scs_sink.cpp
 
 template <class F>

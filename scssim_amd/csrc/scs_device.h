@@ -353,4 +353,14 @@ void launch_support_scatter(hipStream_t s, const SiteRec* sites, uint64_t n, con
 // bytes of every site's line with its counters (site_line through a counting sink); offsets: exclusive_scan_u32_to_u64
 void launch_support_size(hipStream_t s, const SiteArgs& t, const SiteRec* sites, const uint32_t* site_pos, const uint32_t* counts, uint32_t* sizes);
 
+// ---- site support on the original reference (scs_k_support_ref.hip; scs_set_site_support_ref; scs_support_ref.h, DESIGN.md section
+// 19): the listed REFERENCE positions expanded to the staged positions launch_support counts at -- per segment of the lift table
+// the run of listed positions inside it (seg_a, seg_n; FLAG_LIFT: a segment that does not fit), then (off = the exclusive scan of
+// seg_n) the output slots [t0, t0 + n) of `total`: the staged index and the reference position's index of each -- and, after the
+// last batch, the staged counters added to their reference positions' (FLAG_SUPPORT: a counter past 2^32 - 1)
+struct SupportRefView;
+void launch_support_ref_ranges(hipStream_t s, const SupportRefView& v, uint64_t* seg_a, uint32_t* seg_n, uint32_t* flags);
+void launch_support_ref_fill(hipStream_t s, const SupportRefView& v, const uint64_t* off, const uint64_t* seg_a, uint64_t t0, uint64_t n, uint64_t total, uint64_t* sp_pos, uint32_t* sp_pos_x, uint32_t* flags);
+void launch_support_ref_gather(hipStream_t s, const uint32_t* cnt, const uint32_t* sp_pos_x, uint64_t n, uint64_t n_x, uint32_t* ref_cnt, uint32_t* flags);
+
 }  // namespace scs

@@ -4,6 +4,7 @@
 #include "scs_sitejob.h"
 #include "scs_amp.h"
 #include "scs_support.h"
+#include "scs_support_ref.h"
 #include "scs_truth_ref.h"
 
 // host-only: one read's record through the formatter the truth kernels run (scs_truth.h), as SAM text or as a BAM record
@@ -240,6 +241,36 @@ int scs_artefact_ref_probe(const uint64_t* amp_start, const uint32_t* amp_len, c
     if (flags & 1) body = site_ref_header(names, ref_len, unl[0], unl[1]) + body;
     *n_out = body.size();
     if (out) { if (body.size() > cap) return SCS_EOVERFLOW; memcpy(out, body.data(), body.size()); }
+    return SCS_OK;
+}
+
+// host-only: the expansion of the site support table on the reference and its gather through the functions the kernels run
+// (support_ref_probe, scs_support_ref.h)
+int scs_support_ref_probe(const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                          const uint64_t* hap_len, uint32_t n_hap, const uint64_t* ref_len, uint32_t n_ref, const uint64_t* x, uint64_t n_x, uint64_t chunk, const uint32_t* g_counts,
+                          uint64_t* sp_pos, uint32_t* sp_pos_x, uint64_t cap, uint64_t* n_staged, uint32_t* ref_counts, int* why) {
+    if (why) *why = 0;
+    if (!n_staged || !n_seg || !seg_hap_off || !seg_len || !seg_ref_pos || !seg_ref_rec || !seg_kind) return SCS_EINVAL;
+    std::vector<LiftSeg> segs(n_seg);
+    for (uint32_t i = 0; i < n_seg; ++i) segs[i] = LiftSeg{seg_hap_off[i], seg_len[i], seg_ref_pos[i], seg_ref_rec[i], seg_kind[i]};
+    std::vector<uint64_t> pos; std::vector<uint32_t> pos_x, rc;
+    const int rv = support_ref_probe(segs.data(), n_seg, hap_len, n_hap, ref_len, n_ref, x, n_x, chunk ? chunk : ~0ull, g_counts, pos, pos_x, rc, why);
+    if (rv) return rv;
+    *n_staged = pos.size();
+    if (pos.size() > cap) return SCS_EOVERFLOW;
+    if (sp_pos && !pos.empty()) memcpy(sp_pos, pos.data(), pos.size() * 8);
+    if (sp_pos_x && !pos.empty()) memcpy(sp_pos_x, pos_x.data(), pos.size() * 4);
+    if (ref_counts && g_counts && !rc.empty()) memcpy(ref_counts, rc.data(), rc.size() * 4);
+    return SCS_OK;
+}
+// host-only: the header of the site support table on the reference (site_ref_header with the three more lines)
+int scs_support_ref_header_probe(const uint64_t* ref_len, const char* const* ref_names, uint32_t n_ref, uint64_t unl_entries, uint64_t unl_reads, char* out, size_t cap, size_t* n_out) {
+    if (!n_out || !ref_names || !ref_len) return SCS_EINVAL;
+    std::vector<std::string> names;
+    for (uint32_t r = 0; r < n_ref; ++r) { if (!ref_names[r]) return SCS_EINVAL; names.push_back(ref_names[r]); }
+    const std::string h = site_ref_header(names, ref_len, unl_entries, unl_reads, true);
+    *n_out = h.size();
+    if (out) { if (h.size() > cap) return SCS_EOVERFLOW; memcpy(out, h.data(), h.size()); }
     return SCS_OK;
 }
 

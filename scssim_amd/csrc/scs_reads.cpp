@@ -475,7 +475,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     }
     if (y.support) {                                                               // refused before any GPU work: a 32-bit counter could wrap
         support_check(c);
-        if ((y.paired ? 2 * P : P) >> 32) throw ScsError(SCS_EINVAL, "site support (scs_set_site_support): 2^32 reads or more are planned (the counters are 32 bits wide)");
+        if ((y.paired ? 2 * P : P) >> 32) throw ScsError(SCS_EINVAL, support_name(c) + ": 2^32 reads or more are planned (the counters are 32 bits wide)");
     }
     static const int batch_shift = seam_env("SCS_TEST_BATCH_SHIFT") ? atoi(seam_env("SCS_TEST_BATCH_SHIFT")) : 0;   // tests: many small batches
     y.plan = plan_batches(P, y.L, y.to_sink, y.to_sink ? tg.sink->writers : 1, y.to_sink ? tg.sink->regions : 1, batch_shift);
@@ -499,6 +499,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         for (int m = 0; m < 2; ++m) y.tot[m] += b.n.bytes[m];
     }
     if (y.have_pending) y.ship(y.pending);
+    if (y.support) support_close(c);                                               // (the table on the reference: the staged counters summed by reference position)
     y.finish(n1_out, n2_out, pairs_out);
 }
 

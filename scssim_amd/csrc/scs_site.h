@@ -75,6 +75,10 @@ SCS_HD void site_line(Out& o, const char* name, uint32_t name_len, const SiteRec
 }
 
 // ---- host-only
+// the three ##INFO lines both site support tables (DESIGN.md sections 15 and 19) add behind the artefact table's four
+#define SITE_SUPPORT_INFO "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"reads of the job with a base aligned at the site\">\n" \
+                          "##INFO=<ID=AD,Number=2,Type=Integer,Description=\"reads that show the reference base, reads that show the alternate base\">\n" \
+                          "##INFO=<ID=DL,Number=1,Type=Integer,Description=\"reads whose alignment deletes the site\">\n"
 // the file's header: one contig line per staged record, in staging order (support: the site support table's, three more INFO lines)
 inline std::string site_header(const std::vector<std::string>& names, const uint64_t* rec_len, bool support = false) {
     std::string h = "##fileformat=VCFv4.2\n##source=scssim\n";
@@ -83,10 +87,7 @@ inline std::string site_header(const std::vector<std::string>& names, const uint
          "##INFO=<ID=TA,Number=1,Type=Integer,Description=\"full amplicons that cover the site\">\n"
          "##INFO=<ID=NR,Number=1,Type=Integer,Description=\"reads allotted to the NA amplicons\">\n"
          "##INFO=<ID=TR,Number=1,Type=Integer,Description=\"reads allotted to the TA amplicons\">\n";
-    if (support)                                           // the site support table's three (scs_write_site_support)
-        h += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"reads of the job with a base aligned at the site\">\n"
-             "##INFO=<ID=AD,Number=2,Type=Integer,Description=\"reads that show the reference base, reads that show the alternate base\">\n"
-             "##INFO=<ID=DL,Number=1,Type=Integer,Description=\"reads whose alignment deletes the site\">\n";
+    if (support) h += SITE_SUPPORT_INFO;                   // the site support table's three (scs_write_site_support)
     h += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
     return h;
 }

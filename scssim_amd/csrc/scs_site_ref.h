@@ -101,16 +101,18 @@ SCS_HD bool site_ref_make(const uint64_t* keys, const uint32_t* reads, uint64_t 
 
 // ---- host-only
 #define SITE_REF_NOTE "the base of the haplotype the amplicon copied (the template the polymerase misread); it differs from the reference FASTA where a substitution was planted"
-// the file's header: the unlifted totals, one contig line per REFERENCE record of the lift table, in its order
-inline std::string site_ref_header(const std::vector<std::string>& ref_names, const uint64_t* ref_len, uint64_t unl_entries, uint64_t unl_reads) {
+// the file's header: the unlifted totals, one contig line per REFERENCE record of the lift table, in its order (support: the site
+// support table's on the reference, three more INFO lines)
+inline std::string site_ref_header(const std::vector<std::string>& ref_names, const uint64_t* ref_len, uint64_t unl_entries, uint64_t unl_reads, bool support = false) {
     std::string h = "##fileformat=VCFv4.2\n##source=scssim\n##scssim_coordinates=reference\n##scssim_REF=<" SITE_REF_NOTE ">\n";
     h += "##scssim_unlifted=<entries=" + std::to_string(unl_entries) + ",reads=" + std::to_string(unl_reads) + ">\n";
     for (size_t r = 0; r < ref_names.size(); ++r) h += "##contig=<ID=" + ref_names[r] + ",length=" + std::to_string(ref_len[r]) + ">\n";
     h += "##INFO=<ID=NA,Number=1,Type=Integer,Description=\"edit entries (full amplicon, haplotype position) that carry the alternate base and lift to the site\">\n"
          "##INFO=<ID=TA,Number=1,Type=Integer,Description=\"pieces of full amplicons, of any haplotype and copy, that cover the site\">\n"
          "##INFO=<ID=NR,Number=1,Type=Integer,Description=\"reads allotted to the amplicons of the NA entries\">\n"
-         "##INFO=<ID=TR,Number=1,Type=Integer,Description=\"reads allotted to the amplicons of the TA pieces\">\n"
-         "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+         "##INFO=<ID=TR,Number=1,Type=Integer,Description=\"reads allotted to the amplicons of the TA pieces\">\n";
+    if (support) h += SITE_SUPPORT_INFO;                   // (scs_write_site_support_ref)
+    h += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
     return h;
 }
 
