@@ -247,10 +247,22 @@ struct TruthArgs : PlaceArgs {
     // records' lengths (n_ref) and names (offsets: n_ref + 1)
     const LiftSeg* segs; uint32_t n_seg; const uint64_t* ref_len; uint32_t n_ref; const uint32_t* ref_name_off; const char* ref_names;
 };
-void launch_truth_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);                 // SAM bytes per pair (both mates); offsets: exclusive_scan_u32_to_u64
-uint32_t truth_pairs_per_block(uint64_t fq_bytes, uint32_t np);                             // the emit pass' LDS run, from the batch's FASTQ bytes
-void launch_truth_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, char* out);
-// the same passes for the truth BAM: BAM bytes per pair; the records (lds: the emit pass' LDS run in bytes, 0 = all it has)
+// the emit passes (scs_emit.h) on the host's side.  The `lds` a test asks for (0: none) against the pass' own: the wave passes
+// take any size, the windowed passes whole 16-byte chunks, at least one
+inline uint32_t emit_runs_lds(uint32_t lds, uint32_t full) { return lds ? std::min(lds, full) : full; }
+inline uint32_t emit_windows_lds(uint32_t lds, uint32_t full) { return lds ? std::max(std::min(lds, full) & ~15u, 16u) : full; }
+// pairs per workgroup of a wave pass, 1 .. 64, from the batch's FASTQ bytes: a pair's records are taken as num / den of its FASTQ
+// records plus `extra` bytes, and that many fit lds_bytes
+inline uint32_t pairs_per_block(uint64_t fq_bytes, uint32_t np, uint32_t lds_bytes, uint32_t num, uint32_t den, uint32_t extra) {
+    const uint64_t est = (np ? fq_bytes / np : 0) * num / den + extra;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(64, lds_bytes / est));
+}
+// the three truth outputs share one shape: *_size counts the bytes per pair (both mates; offsets: exclusive_scan_u32_to_u64),
+// *_pairs_per_block sizes the emit pass' workgroups, *_emit writes the records (lds: the emit pass' LDS run in bytes, 0 = all it has)
+void launch_truth_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);
+uint32_t truth_pairs_per_block(uint64_t fq_bytes, uint32_t np);
+void launch_truth_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, uint32_t lds, char* out);
+// the same passes for the truth BAM
 void launch_truth_bam_size(hipStream_t s, const TruthArgs& a, uint32_t* sizes);
 uint32_t truth_bam_pairs_per_block(uint64_t fq_bytes, uint32_t np);
 void launch_truth_bam_emit(hipStream_t s, const TruthArgs& a, const uint64_t* offs, uint32_t pairs_per_block, uint32_t lds, char* out);

@@ -4,14 +4,12 @@
 // (amp_resolve: k_plan_pairs' resolution), finds its record by bisection and walks its edits (scs_amp.h).
 //
 // k_amp_place writes the binary form.  The text takes two passes over a chunk of amplicons, both running amp_line: the SIZING
-// pass counts each line's bytes, a 64-bit exclusive scan gives the offsets, and the EMIT pass writes the lines.  The emit pass
-// builds a workgroup's contiguous run of lines in LDS and copies it out in whole 16-byte aligned stores (a lane writing its ~45-byte
-// line byte by byte would leave partial sectors all over the text: the cost k_reads pays for its lane-private records).  The run is
-// a WINDOW of `lds` bytes over the workgroup's text: a lane formats its line once per window the line touches and keeps the bytes
-// that fall inside, so a line may straddle two windows and no line is too long for the LDS.
+// pass counts each line's bytes, a 64-bit exclusive scan gives the offsets, and the EMIT pass writes the ~45-byte lines by the
+// windowed scheme of scs_emit.h (emit_windows): a line may straddle two windows and no line is too long for the LDS.
 #include "scs_device.h"
 #include "scs_kernels_common.h"
 #include "scs_amp.h"
+#include "scs_emit.h"
 
 namespace scs {
 
@@ -24,8 +22,7 @@ __device__ bool amp_load(const AmpArgs& A, uint32_t j, AmpPlace& p, AmpLine& li,
     const uint32_t fsl = A.fulls.sl[i], sm = A.fulls.parent[i], ssl = A.semis.sl[sm], f = A.semis.parent[sm];
     if (!amp_resolve(A.fr.goff[f], A.fr.len[f], A.fr.strand[f], sl_spos(ssl), sl_len(ssl), sl_spos(fsl), sl_len(fsl), p) || !amp_strand(p)) { atomicOr(A.flags, (uint32_t)FLAG_AMP); return false; }
     const int64_t x0 = amp_lo(p);
-    uint32_t lo = 0, hi = A.n_rec;                         // the record: rec_off[lo] <= x0 < rec_off[lo + 1]
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)A.rec_off[mid] <= x0) lo = mid; else hi = mid; }
+    const uint32_t lo = rec_of(A.rec_off, A.n_rec, x0);
     const int64_t r0 = (int64_t)A.rec_off[lo], r1 = (int64_t)A.rec_off[lo + 1];
     if (x0 < r0 || x0 + (int64_t)p.len > r1) { atomicOr(A.flags, (uint32_t)FLAG_AMP); return false; }   // a fragment never straddles records
     rec = lo;
@@ -55,40 +52,14 @@ __global__ void __launch_bounds__(256) k_amp_size(AmpArgs A, uint32_t* __restric
     sizes[j] = (uint32_t)c.n;
 }
 
-// a line into the window [w0, w1) of the chunk's text, which lies in LDS from s on: the bytes outside are counted, not kept
-struct AmpWinOut {
-    char* s; uint64_t pos, w0, w1;
-    __device__ void put(char ch) { if (pos >= w0 && pos < w1) s[pos - w0] = ch; ++pos; }
-};
-
-// one workgroup per 256 amplicons: window by window (wa: 16-byte aligned, so aligned text is aligned in LDS) the lanes format the
-// lines that touch the window, then the workgroup copies the window's part of its text out: whole aligned 16-byte chunks, single
-// bytes at the two ends (shared with the neighbouring workgroups' text).  One window for most workgroups (256 lines of ~45 bytes)
+// one workgroup per 256 amplicons (emit_windows): lane i formats the line of amplicon j0 + i
 __global__ void __launch_bounds__(256) k_amp_emit(AmpArgs A, const uint64_t* __restrict__ offs, uint32_t lds, char* __restrict__ out) {
     extern __shared__ uint4 s_run4[];
-    char* s_run = reinterpret_cast<char*>(s_run4);
-    const uint32_t j0 = blockIdx.x * 256u, j1 = min(j0 + 256u, A.n), j = j0 + threadIdx.x;
-    const bool mine = j < j1;
-    const uint64_t b0 = offs[j0], b1 = offs[j1], my0 = mine ? offs[j] : 0ull, my1 = mine ? offs[j + 1] : 0ull;
+    const uint32_t j0 = blockIdx.x * 256u;
+    const EmitSpan sp = emit_span(offs, j0, min(j0 + 256u, A.n));
     AmpPlace p; AmpLine li; AmpErrs e1, e2; uint32_t r = 0;
-    const bool ok = mine && my1 > my0 && amp_load(A, j, p, li, e1, e2, r);
-    for (uint64_t wa = b0 & ~15ull; wa < b1; wa += lds) {  // (b0, b1 and lds are the workgroup's: every lane takes every turn)
-        const uint64_t c0 = wa > b0 ? wa : b0, c1 = wa + lds < b1 ? wa + lds : b1;
-        if (ok && my0 < c1 && my1 > c0) {
-            AmpWinOut o{s_run, my0, wa, wa + lds};
-            amp_line(o, li, p, e1, e2, AmpGen{A.g});
-            if (o.pos != my1) atomicOr(A.flags, (uint32_t)FLAG_AMP);   // (the sizing pass and the formatter disagree: never a silent wrong file)
-        }
-        __syncthreads();
-        const uint64_t a0 = (c0 + 15u) & ~15ull, a1 = c1 & ~15ull;
-        if (a0 >= a1) { for (uint64_t x = c0 + threadIdx.x; x < c1; x += 256u) out[x] = s_run[x - wa]; }
-        else {
-            for (uint64_t x = c0 + threadIdx.x; x < a0; x += 256u) out[x] = s_run[x - wa];
-            for (uint64_t x = a1 + threadIdx.x; x < c1; x += 256u) out[x] = s_run[x - wa];
-            for (uint64_t x = a0 + 16u * threadIdx.x; x < a1; x += 4096u) *reinterpret_cast<uint4*>(out + x) = s_run4[(x - wa) >> 4];
-        }
-        __syncthreads();                                   // (the next turn writes the LDS this one has just read)
-    }
+    const bool ok = sp.my1 > sp.my0 && amp_load(A, j0 + threadIdx.x, p, li, e1, e2, r);
+    emit_windows(s_run4, sp, ok, lds, out, A.flags, (uint32_t)FLAG_AMP, [&](WinOut& o) { amp_line(o, li, p, e1, e2, AmpGen{A.g}); });
 }
 
 void launch_amp_place(hipStream_t s, const AmpArgs& a, uint32_t* rec, uint64_t* start, uint32_t* len, int8_t* strand, uint32_t* n_edits) {
@@ -103,9 +74,7 @@ void launch_amp_size(hipStream_t s, const AmpArgs& a, uint32_t* sizes) {
 }
 void launch_amp_emit(hipStream_t s, const AmpArgs& a, const uint64_t* offs, uint32_t lds, char* out) {
     if (a.n == 0) return;
-    lds = lds ? std::min(lds, AMP_LDS) & ~15u : AMP_LDS;   // whole 16-byte chunks, at least one
-    if (lds < 16u) lds = 16u;
-    hipLaunchKernelGGL(k_amp_emit, dim3(cdiv(a.n, 256)), dim3(256), AMP_LDS, s, a, offs, lds, out);
+    hipLaunchKernelGGL(k_amp_emit, dim3(cdiv(a.n, 256)), dim3(256), AMP_LDS, s, a, offs, emit_windows_lds(lds, AMP_LDS), out);
     note_launch(hipGetLastError());
 }
 

@@ -7,13 +7,14 @@
 //                  its end and its reads.  The order is free: a wave adds its total to the cursor once and its lanes write behind it.
 //   (rocPRIM)      radix sort of the keys, the starts and the ends, each with the reads; 64-bit scans of the reads in start and end order
 //   k_site_reduce  a thread per sorted entry; the one that opens a run makes the site (site_make, scs_site.h) and sizes its line
-//   k_site_emit    the lines, by k_amp_emit's scheme: a workgroup's run built in an LDS window, copied out in aligned 16-byte stores
+//   k_site_emit    the lines, by the windowed scheme of scs_emit.h (emit_windows), as k_amp_emit
 //   k_site_compact the kept sites packed for the binary form
 #include "scs_device.h"
 #include "scs_kernels_common.h"
 #include "scs_amp.h"
 #include "scs_site.h"
 #include "scs_site_load.h"
+#include "scs_emit.h"
 #include <rocprim/rocprim.hpp>
 
 namespace scs {
@@ -90,43 +91,18 @@ __global__ void __launch_bounds__(256) k_site_reduce(SiteArgs T, SiteRec* __rest
     sizes[i] = size; keep[i] = kept;
 }
 
-// a line into the window [w0, w1) of the slab's text, which lies in LDS from s on: the bytes outside are counted, not kept
-struct SiteWinOut {
-    char* s; uint64_t pos, w0, w1;
-    __device__ void put(char ch) { if (pos >= w0 && pos < w1) s[pos - w0] = ch; ++pos; }
-};
-
-// one workgroup per 256 entries (k_amp_emit's scheme): window by window the lanes whose entry is a reported site format the
-// lines that touch the window, then the workgroup copies the window's part of its text out: whole aligned 16-byte chunks, single
-// bytes at the two ends.  counts (the site support table; else null): the line ends with the six counters of the entry's position
+// one workgroup per 256 entries (emit_windows): the lanes whose entry is a reported site format its line.  counts (the site
+// support table; else null): the line ends with the six counters of the entry's position
 __global__ void __launch_bounds__(256) k_site_emit(SiteArgs T, const SiteRec* __restrict__ recs, const uint64_t* __restrict__ offs, uint32_t lds, char* __restrict__ out,
                                                    const uint32_t* __restrict__ site_pos, const uint32_t* __restrict__ counts) {
     extern __shared__ uint4 s_run4[];
-    char* s_run = reinterpret_cast<char*>(s_run4);
-    const uint64_t j0 = (uint64_t)blockIdx.x * 256u, j1 = j0 + 256u < T.n ? j0 + 256u : T.n, j = j0 + threadIdx.x;
-    const bool mine = j < j1;
-    const uint64_t b0 = offs[j0], b1 = offs[j1], my0 = mine ? offs[j] : 0ull, my1 = mine ? offs[j + 1] : 0ull;
-    const bool ok = mine && my1 > my0;
+    const uint64_t j0 = (uint64_t)blockIdx.x * 256u, j = j0 + threadIdx.x;
+    const EmitSpan sp = emit_span(offs, j0, j0 + 256u < T.n ? j0 + 256u : T.n);
+    const bool ok = sp.my1 > sp.my0;
     SiteRec r; const char* name = nullptr; uint32_t name_len = 0;
     if (ok) { r = recs[j]; if (r.rec < T.n_rec) { name = T.names + T.name_off[r.rec]; name_len = T.name_off[r.rec + 1] - T.name_off[r.rec]; } }
     const uint32_t* cnt = ok && counts ? counts + 6ull * site_pos[j] : nullptr;
-    for (uint64_t wa = b0 & ~15ull; wa < b1; wa += lds) {  // (b0, b1 and lds are the workgroup's: every lane takes every turn)
-        const uint64_t c0 = wa > b0 ? wa : b0, c1 = wa + lds < b1 ? wa + lds : b1;
-        if (ok && my0 < c1 && my1 > c0) {
-            SiteWinOut o{s_run, my0, wa, wa + lds};
-            site_line(o, name, name_len, r, cnt);
-            if (o.pos != my1) atomicOr(T.flags, (uint32_t)FLAG_SITE);   // (the sizing pass and the formatter disagree: never a silent wrong file)
-        }
-        __syncthreads();
-        const uint64_t a0 = (c0 + 15u) & ~15ull, a1 = c1 & ~15ull;
-        if (a0 >= a1) { for (uint64_t x = c0 + threadIdx.x; x < c1; x += 256u) out[x] = s_run[x - wa]; }
-        else {
-            for (uint64_t x = c0 + threadIdx.x; x < a0; x += 256u) out[x] = s_run[x - wa];
-            for (uint64_t x = a1 + threadIdx.x; x < c1; x += 256u) out[x] = s_run[x - wa];
-            for (uint64_t x = a0 + 16u * threadIdx.x; x < a1; x += 4096u) *reinterpret_cast<uint4*>(out + x) = s_run4[(x - wa) >> 4];
-        }
-        __syncthreads();                                   // (the next turn writes the LDS this one has just read)
-    }
+    emit_windows(s_run4, sp, ok, lds, out, T.flags, (uint32_t)FLAG_SITE, [&](WinOut& o) { site_line(o, name, name_len, r, cnt); });
 }
 
 // the reported sites packed in order: out[pos[i]] = recs[i] where keep[i] (pos: the exclusive scan of keep)
@@ -164,9 +140,7 @@ void launch_site_reduce(hipStream_t s, const SiteArgs& t, SiteRec* recs, uint32_
 }
 void launch_site_emit(hipStream_t s, const SiteArgs& t, const SiteRec* recs, const uint64_t* offs, uint32_t lds, char* out, const uint32_t* site_pos, const uint32_t* counts) {
     if (t.n == 0) return;
-    lds = lds ? std::min(lds, SITE_LDS) & ~15u : SITE_LDS; // whole 16-byte chunks, at least one
-    if (lds < 16u) lds = 16u;
-    hipLaunchKernelGGL(k_site_emit, dim3(cdiv(t.n, 256)), dim3(256), SITE_LDS, s, t, recs, offs, lds, out, site_pos, counts);
+    hipLaunchKernelGGL(k_site_emit, dim3(cdiv(t.n, 256)), dim3(256), SITE_LDS, s, t, recs, offs, emit_windows_lds(lds, SITE_LDS), out, site_pos, counts);
     note_launch(hipGetLastError());
 }
 void launch_site_compact(hipStream_t s, const SiteRec* recs, const uint32_t* keep, const uint32_t* pos, uint64_t n, SiteRec* out) {

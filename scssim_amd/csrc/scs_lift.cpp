@@ -173,8 +173,7 @@ int scs_lift_read_probe(int n, int64_t pos0, int reverse, const int32_t* events,
     std::vector<uint64_t> roff(n_hap + 1, 0), rl(ref_lens, ref_lens + n_ref), boff(n_ref + 1, 0); uint64_t nb = 0;
     for (uint32_t r = 0; r < n_hap; ++r) roff[r + 1] = roff[r] + hap_lens[r];
     if (!depth_layout(rl.data(), n_ref, bin_width, boff.data(), &nb, nullptr)) return SCS_EINVAL;
-    uint32_t lo = 0, hi = n_hap;                                                       // the record, as the kernel finds it
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)roff[mid] <= a.lo) lo = mid; else hi = mid; }
+    const uint32_t lo = rec_of(roff.data(), n_hap, a.lo);                              // the record, as the kernel finds it
     const LiftView V{segs.data(), n_seg, rl.data(), boff.data(), n_ref, bin_width, nb};
     std::vector<std::pair<uint64_t, uint32_t>> runs; uint64_t first = 0;
     const int err = lift_read(a, (int64_t)roff[lo], (int64_t)roff[lo + 1], V, [&](uint64_t b) { first = b; }, [&](uint64_t b, uint32_t k) { runs.push_back({b, k}); });

@@ -52,8 +52,7 @@ __device__ __forceinline__ void for_each_placed_read(const Args& A, uint32_t pi,
     for (uint32_t rd = 0; rd < (A.paired ? 2u : 1u); ++rd) {
         TruthAln a; int n_out;
         if (!read_place(A, pr, pi, rd, ev, a, n_out, flag)) continue;
-        uint32_t lo = 0, hi = A.n_rec;
-        while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)A.rec_off[mid] <= a.lo) lo = mid; else hi = mid; }
+        const uint32_t lo = rec_of(A.rec_off, A.n_rec, a.lo);
         f(pr, rd, a, n_out, lo, (int64_t)A.rec_off[lo], (int64_t)A.rec_off[lo + 1]);
     }
 }
@@ -65,6 +64,16 @@ __device__ __forceinline__ const char* read_text(const uint64_t* off1, const uin
     const char* r = (rd ? fq2 : fq1) + ((rd ? off2 : off1)[pi] & OFF_MASK);
     if (rec) *rec = r;
     return r + 1u + truth_digits(pr.amp) + 1u + truth_digits(pr.att + 1u) + (paired ? 2u : 0u) + 1u;
+}
+
+// read rd of pair pi for a truth pass: its events into ev and its placement (read_place), then its FASTQ text: s its bases, q its
+// qualities.  false: it has no record (a read the indel pass flagged), or it cannot be made right (FLAG_TRUTH)
+__device__ inline bool truth_load(const TruthArgs& A, const PairRec& pr, uint32_t pi, uint32_t rd, uint32_t* ev, TruthAln& a, const char*& s, const char*& q) {
+    int n_out;
+    if (!read_place(A, pr, pi, rd, ev, a, n_out, (uint32_t)FLAG_TRUTH)) return false;
+    s = read_text(A.off1, A.off2, A.fq1, A.fq2, A.paired, pr, pi, rd);
+    q = s + n_out + 3;
+    return true;
 }
 
 }  // namespace scs

@@ -104,9 +104,7 @@ int scs_truth_ref_record_probe(int paired, int is_read2, uint32_t amp, uint32_t 
     for (uint32_t i = 0; i < n_seg; ++i) segs[i] = LiftSeg{seg_hap_off[i], seg_len[i], seg_ref_pos[i], seg_ref_rec[i], seg_kind[i]};
     std::vector<uint64_t> roff(n_hap + 1, 0);
     for (uint32_t r = 0; r < n_hap; ++r) roff[r + 1] = roff[r] + hap_lens[r];
-    uint32_t lo = 0, hi = n_hap;                                                       // the staged record, as the kernel finds it (read 1's; the mate must lie there too)
-    const int64_t first_lo = paired && is_read2 ? m.lo : a.lo;
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)roff[mid] <= first_lo) lo = mid; else hi = mid; }
+    const uint32_t lo = rec_of(roff.data(), n_hap, paired && is_read2 ? m.lo : a.lo);  // the staged record, as the kernel finds it (read 1's; the mate must lie there too)
     const int64_t r0 = (int64_t)roff[lo], r1 = (int64_t)roff[lo + 1];
     const LiftTab T{segs.data(), n_seg, ref_lens, n_ref};
     LiftAln la{}, lm{};

@@ -348,11 +348,18 @@ struct Yield {               // the state of one do_yield call
     void truth_batch(Batch& b) {
         // the batch's SAM: sizing pass + 64-bit offsets, the total to the host (it sizes the output), emit pass.  Before ev_free: the
         // passes read the batch's indel events and record offsets
-        static const uint32_t bam_lds = seam_u32("SCS_TEST_TRUTH_LDS", 0u);   // tests: the BAM and the reference SAM's emit passes cut their runs
+        static const uint32_t lds = seam_u32("SCS_TEST_TRUTH_LDS", 0u);       // tests: the emit pass cuts its runs
+        struct Pass {                                                            // the three truth outputs' passes (scs_device.h)
+            void (*size)(hipStream_t, const TruthArgs&, uint32_t*); uint32_t (*ppb)(uint64_t, uint32_t);
+            void (*emit)(hipStream_t, const TruthArgs&, const uint64_t*, uint32_t, uint32_t, char*);
+        };
+        static const Pass passes[3] = {{launch_truth_size, truth_pairs_per_block, launch_truth_emit}, {launch_truth_bam_size, truth_bam_pairs_per_block, launch_truth_bam_emit},
+                                       {launch_truth_ref_size, truth_ref_pairs_per_block, launch_truth_ref_emit}};
+        const Pass& P = passes[bam ? 1 : tref ? 2 : 0];
         const uint32_t np = b.np; const uint64_t fq_bytes = b.n.bytes[0] + b.n.bytes[1];
         place_batch(ta, b); ta.off1 = b.B->off[0]; ta.off2 = b.B->off[1]; ta.fq1 = b.out[0]; ta.fq2 = b.out[1];
         c->tm[TM_TRUTH].begin(s);
-        if (bam) launch_truth_bam_size(s, ta, c->t_sizes.as<uint32_t>()); else if (tref) launch_truth_ref_size(s, ta, c->t_sizes.as<uint32_t>()); else launch_truth_size(s, ta, c->t_sizes.as<uint32_t>());
+        P.size(s, ta, c->t_sizes.as<uint32_t>());
         exclusive_scan_u32_to_u64(s, c->t_sizes.as<uint32_t>(), c->t_offs.as<uint64_t>(), np, c->t_scan.p, c->t_scan.cap);
         HIP_OK(hipMemcpyAsync(c->h_t, c->t_offs.as<uint64_t>() + np, 8, hipMemcpyDeviceToHost, s)); HIP_OK(hipEventRecord(c->ev_t, s));
         c->tm[TM_TRUTH].end(s);
@@ -361,13 +368,10 @@ struct Yield {               // the state of one do_yield call
         DevBuf& to = c->t_out[b.dsl]; const uint64_t t_n = *c->h_t, need = std::max<uint64_t>(t_n, 16), room = std::max<uint64_t>(t_n + t_n / 16, 16);
         reserve_slot(&to, 1, &need, &room, b.dsl, false);
         c->tm[TM_TRUTH].begin(s);
-        if (!bam) {
-            if (tref) launch_truth_ref_emit(s, ta, c->t_offs.as<uint64_t>(), truth_ref_pairs_per_block(fq_bytes, np), bam_lds, to.as<char>());
-            else launch_truth_emit(s, ta, c->t_offs.as<uint64_t>(), truth_pairs_per_block(fq_bytes, np), to.as<char>());
-            b.t_text = to.as<char>(); b.t_n = t_n; truth_fd.total += t_n;
-        } else if (t_n) {
-            // the batch's records, then BGZF over them where they lie (the FASTQ blocks' kernels); ship reads n[2] from h_z[dsl][2], behind ev_z
-            launch_truth_bam_emit(s, ta, c->t_offs.as<uint64_t>(), truth_bam_pairs_per_block(fq_bytes, np), bam_lds, to.as<char>());
+        if (!bam || t_n) P.emit(s, ta, c->t_offs.as<uint64_t>(), P.ppb(fq_bytes, np), lds, to.as<char>());
+        if (!bam) { b.t_text = to.as<char>(); b.t_n = t_n; truth_fd.total += t_n; }
+        else if (t_n) {
+            // BGZF over the batch's records where they lie (the FASTQ blocks' kernels); ship reads n[2] from h_z[dsl][2], behind ev_z
             b.t_text = bgzf_in_place(2, to.as<char>(), t_n, b.dsl, "truth BAM: a batch's records exceed 4 GB");
             if (!bgzf) HIP_OK(hipEventRecord(c->ev_z[b.dsl], s));
         }

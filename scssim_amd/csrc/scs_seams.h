@@ -7,7 +7,7 @@
 //   SCS_READS_SERIAL / SCS_READS_SPLIT / SCS_ERRS_INLINE  launch orders of earlier rounds     SCS_ATTACH_G / SCS_ATTACH_GROUPS  the semi pass as lane groups per template (and how wide)
 //   SCS_VMM_FROM_MB / SCS_NO_VMM  where device buffers switch to mapped ranges                SCS_HOST_FASTA / SCS_STAGE_WHOLE  staging paths
 //   SCS_TEST_FAIL_AT / SCS_TEST_FAIL_RANK  a CLI rank that dies at a given place
-//   SCS_TEST_TRUTH_LDS  bytes of LDS the truth BAM's emit pass fills before it copies a run out (small: several runs per workgroup)
+//   SCS_TEST_TRUTH_LDS  bytes of LDS the emit pass of all three truth outputs (SAM, BAM, reference SAM) fills before it copies a run out (small: several runs per workgroup; below a pair: the SAM writes the pair directly, the other two refuse it)
 //   SCS_TEST_DEPTH_SLOTS  entries of the depth kernel's LDS table (a power of two up to 512; 4: it overflows into direct adds, 0: no table, every add goes to memory)
 //   SCS_TEST_AMP_CHUNK  amplicons per chunk of the amplicon table (scs_amplicons.cpp)       SCS_TEST_AMP_LDS  bytes of its emit pass' LDS run (small: lines straddle two runs)
 //   SCS_TEST_SITE_SLAB  genome indices per slab of the artefact table (scs_sites.cpp; small: amplicons and sites on both sides of slab borders; its fill and counting passes also take SCS_TEST_AMP_CHUNK)

@@ -31,13 +31,6 @@ SCS_HD uint64_t site_rank_le(const uint64_t* v, uint64_t n, uint64_t x) {
     return lo;
 }
 
-// the record of genome index x: rec_off[r] <= x < rec_off[r + 1] (n_rec + 1 ascending starts; n_rec >= 1, x inside the genome)
-SCS_HD uint32_t site_record(const uint64_t* rec_off, uint32_t n_rec, uint64_t x) {
-    uint32_t lo = 0, hi = n_rec;
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (rec_off[mid] <= x) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // one site.  pos: 0-based record coordinate; ref 0..4, alt 0..3
 struct SiteRec { uint64_t pos, nr, tr; uint32_t rec, na, ta; uint8_t ref, alt, pad[2]; };
 
@@ -50,7 +43,7 @@ SCS_HD bool site_make(const uint64_t* keys, const uint32_t* reads, uint64_t n, u
     uint32_t na = 0; uint64_t nr = 0;
     for (uint64_t j = i; j < n && keys[j] == key; ++j) { ++na; nr += reads[j]; }
     const uint64_t rs = site_rank_le(starts, m, x), re = site_rank_le(ends, m, x);
-    r.rec = site_record(rec_off, n_rec, x); r.pos = x - rec_off[r.rec]; r.ref = (uint8_t)ref; r.alt = (uint8_t)site_key_alt(key); r.pad[0] = r.pad[1] = 0;
+    r.rec = rec_of(rec_off, n_rec, x); r.pos = x - rec_off[r.rec]; r.ref = (uint8_t)ref; r.alt = (uint8_t)site_key_alt(key); r.pad[0] = r.pad[1] = 0;
     r.na = na; r.nr = nr; r.ta = (uint32_t)(rs - re); r.tr = ps_start[rs] - ps_end[re];
     return rs >= re && rs - re >= na && ps_start[rs] >= ps_end[re] && r.tr >= nr && x < rec_off[n_rec];
 }
@@ -107,7 +100,7 @@ inline int site_probe(const uint64_t* amp_start, const uint32_t* amp_len, const 
     if (rec_off[n_rec] != genome_len || genome_len >> 60) return SCS_EINVAL;
     for (uint64_t a = 0; a < n_amp; ++a) {
         if (!amp_len[a] || amp_start[a] >= genome_len || amp_start[a] + amp_len[a] > genome_len) return SCS_EINVAL;
-        const uint32_t r = site_record(rec_off.data(), n_rec, amp_start[a]);
+        const uint32_t r = rec_of(rec_off.data(), n_rec, amp_start[a]);
         if (amp_start[a] + amp_len[a] > rec_off[r + 1]) return SCS_EINVAL;       // a fragment never straddles records
     }
     std::vector<std::pair<uint64_t, uint32_t>> ent(n_ed), st(n_amp), en(n_amp);

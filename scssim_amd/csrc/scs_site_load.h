@@ -18,7 +18,7 @@ __device__ inline bool site_load(const AmpArgs& A, uint32_t j, AmpPlace& p, AmpE
     if (!amp_resolve(A.fr.goff[f], A.fr.len[f], A.fr.strand[f], sl_spos(ssl), sl_len(ssl), sl_spos(fsl), sl_len(fsl), p) || !amp_strand(p)) { atomicOr(A.flags, (uint32_t)FLAG_SITE); return false; }
     const int64_t x0 = amp_lo(p);
     if (x0 < 0 || (uint64_t)x0 >= A.rec_off[A.n_rec]) { atomicOr(A.flags, (uint32_t)FLAG_SITE); return false; }
-    const uint32_t r = site_record(A.rec_off, A.n_rec, (uint64_t)x0);
+    const uint32_t r = rec_of(A.rec_off, A.n_rec, x0);
     if ((uint64_t)x0 < A.rec_off[r] || (uint64_t)x0 + p.len > A.rec_off[r + 1]) { atomicOr(A.flags, (uint32_t)FLAG_SITE); return false; }   // a fragment never straddles records
     rec = r;
     reads = A.read_numbers[i];

@@ -94,7 +94,7 @@ SCS_HD bool site_ref_make(const uint64_t* keys, const uint32_t* reads, uint64_t 
     uint32_t na = 0; uint64_t nr = 0;
     for (uint64_t j = i; j < n && keys[j] == key; ++j) { ++na; nr += reads[j]; }
     const uint64_t rs = site_rank_le(starts, m, x), re = site_rank_le(ends, m, x);
-    r.rec = site_record(ref_off, n_ref, x); r.pos = x - ref_off[r.rec]; r.ref = (uint8_t)site_ref_key_ref(key); r.alt = (uint8_t)site_ref_key_alt(key); r.pad[0] = r.pad[1] = 0;
+    r.rec = rec_of(ref_off, n_ref, x); r.pos = x - ref_off[r.rec]; r.ref = (uint8_t)site_ref_key_ref(key); r.alt = (uint8_t)site_ref_key_alt(key); r.pad[0] = r.pad[1] = 0;
     r.na = na; r.nr = nr; r.ta = (uint32_t)(rs - re); r.tr = ps_start[rs] - ps_end[re];
     return rs >= re && rs - re >= na && rs - re <= 0xFFFFFFFFull && ps_start[rs] >= ps_end[re] && r.tr >= nr && r.ref <= 4u;
 }
@@ -152,7 +152,7 @@ inline int site_ref_probe(const uint64_t* amp_start, const uint32_t* amp_len, co
     std::vector<uint64_t> a_rec0(n_amp), a_rec1(n_amp);
     for (uint64_t a = 0; a < n_amp; ++a) {
         if (!amp_len[a] || amp_start[a] >= genome_len || amp_start[a] + amp_len[a] > genome_len) return SCS_EINVAL;
-        const uint32_t r = site_record(rec_off.data(), n_hap, amp_start[a]);
+        const uint32_t r = rec_of(rec_off.data(), n_hap, amp_start[a]);
         if (amp_start[a] + amp_len[a] > rec_off[r + 1]) return SCS_EINVAL;         // a fragment never straddles records
         a_rec0[a] = rec_off[r]; a_rec1[a] = rec_off[r + 1];
     }

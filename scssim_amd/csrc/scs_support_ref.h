@@ -28,7 +28,7 @@ SCS_HD int support_ref_range(const SupportRefView& V, uint32_t si, uint64_t& a, 
     const uint64_t before = si ? V.segs[si - 1u].hap_off + V.segs[si - 1u].len : 0ull;
     if (s.len == 0 || s.hap_off + s.len < s.hap_off || s.hap_off != before) return LIFT_ETABLE;
     if (V.n_rec == 0 || s.hap_off >= V.rec_off[V.n_rec]) return LIFT_ETABLE;
-    if (s.hap_off + s.len > V.rec_off[site_record(V.rec_off, V.n_rec, s.hap_off) + 1u]) return LIFT_ETABLE;
+    if (s.hap_off + s.len > V.rec_off[rec_of(V.rec_off, V.n_rec, s.hap_off) + 1u]) return LIFT_ETABLE;
     if (s.kind != 0u) return LIFT_OK;
     if (s.ref_rec >= V.n_ref || s.ref_pos + s.len < s.ref_pos || s.ref_pos + s.len > V.ref_off[s.ref_rec + 1u] - V.ref_off[s.ref_rec]) return LIFT_EREF;
     const uint64_t x0 = V.ref_off[s.ref_rec] + s.ref_pos;

@@ -63,6 +63,14 @@ SCS_HD bool truth_place(TruthAln& a) {
     return true;
 }
 
+// which staged record holds genome index x: rec_off[r] <= x < rec_off[r + 1] (n_rec + 1 ascending starts, n_rec >= 1).  An x outside
+// the genome gives record 0 or n_rec - 1: the caller checks x against the record's bounds before it trusts the answer
+SCS_HD uint32_t rec_of(const uint64_t* rec_off, uint32_t n_rec, int64_t x) {
+    uint32_t lo = 0, hi = n_rec;
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if ((int64_t)rec_off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+
 // the CIGAR ops genome-forward, leading / trailing D dropped, neighbours of one kind merged: f(kind, len)
 template <class F>
 SCS_HD void truth_cigar_walk(const TruthAln& a, F f) {

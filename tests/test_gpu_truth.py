@@ -104,7 +104,7 @@ def _md_nm(seq, gen, pos0, ops):
     return md + "%d" % run, nm
 
 
-def check_sam(sam, fq_files, fasta, paired, isize=None, exact=False, lineage=None):
+def check_sam(sam, fq_files, fasta, paired, isize=None, exact=False, lineage=None, min_records=1000):
     """Checks 2 (and 4 / 3 when asked): header, one record per FASTQ record in order, SEQ / QUAL, CIGAR, mate fields, NM / MD
     against the FASTA.  exact: SEQ equals the genome under the CIGAR (no substitution anywhere).  Returns the records."""
     hdr, recs = _sam(sam)
@@ -113,7 +113,7 @@ def check_sam(sam, fq_files, fasta, paired, isize=None, exact=False, lineage=Non
     assert hdr[1:-1] == ["@SQ\tSN:%s\tLN:%d" % (k, len(v)) for k, v in gen.items()]
     fqs = [_fastq(f) for f in fq_files]
     fq = [r for pair in zip(*fqs) for r in pair] if paired else fqs[0]
-    assert len(recs) == len(fq) > 1000
+    assert len(recs) == len(fq) > min_records
     rec_off, o = {}, 0
     for k, v in gen.items():
         rec_off[k] = o; o += len(v)
@@ -279,6 +279,63 @@ def test_many_batches_and_ns(sink, models, tmp_path):
                   sink=sink, bgzf=True, lineage=True)
     fqs = [out + m + (".fq.gz" if sink == "files" else ".fq") for m in ("_1", "_2")]
     check_sam(out + ".sam", fqs, fa, True, isize=260, lineage=out + "_lineage.npz")
+
+
+# ---- the emit pass under a cut LDS (SCS_TEST_TRUTH_LDS).  The job: test_gpu_truth_bam.py::test_frequent_indels' genome and
+# profile (insertion and deletion rates 0.01, no substitution anywhere), PE, at a coverage of 0.2: 350 kb / (2 x 125) x 0.2 = 280 pairs
+CUT_JOB = dict(cov=0.2, layout="PE", seed=7, sink="callback", ber=0.0)
+CUT_LDS = 256                                             # bytes: below any pair of the job (pair_floor)
+
+
+def cut_job_inputs(d, models):
+    fa = str(d / "g.fa")
+    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "200000,150000", "--seed", "17", "--simu-out", fa])
+    return fa, _exact_profile(models["Illumina_HiSeq2500"], str(d / "x.profile"), 0.01, 0.01)
+
+
+def pair_floor(probe, rname, **kw):
+    """Bytes of the smallest pair of records a job can hold, on the CPU, through the formatter the kernels run (`probe`: one of the
+    record probes of scssim_amd).  The shortest read the profile admits has n + delta = 50 bases (fewer: the events are rolled
+    back); its smallest record has every field at its narrowest: amplicon 0, count 1, a one-digit POS and PNEXT, FLAG 99, TLEN 50,
+    the 75 deleted bases at the window's end (dropped from the CIGAR: "50M"), no mismatch.  A pair is two records, read 2's FLAG
+    (147) a digit wider."""
+    ev = [(50, 1, 75)]
+    rec = probe(seq="A" * 50, qual="I" * 50, pos0=0, n=125, events=ev, reverse=False, rname=rname, amp=0, cnt=1, paired=True, is_read2=False, mate=(49, True, ev), **kw)
+    return 2 * len(rec)
+
+
+@pytest.fixture(scope="module")
+def cut_reference(models, tmp_path_factory):
+    """The job with the emit pass as shipped: its SAM checked against the genome, its FASTQ against a yield without the SAM."""
+    d = tmp_path_factory.mktemp("cut")
+    fa, prof = cut_job_inputs(d, models)
+    out, so = _run(d, prof=prof, fa=fa, plain=True, **CUT_JOB)
+    pairs = int(so.split()[3])
+    print("pairs: %d" % pairs)
+    assert 200 <= pairs <= 400
+    for m in ("_1.fq", "_2.fq"):
+        assert open(out + m, "rb").read() == open(out + "_plain" + m, "rb").read()
+    recs, _, n_indel = check_sam(out + ".sam", [out + "_1.fq", out + "_2.fq"], fa, True, exact=True, min_records=2 * 200 - 1)
+    assert len(recs) == 2 * pairs and n_indel > 0.2 * len(recs)
+    return dict(fa=fa, prof=prof, sam=open(out + ".sam", "rb").read(), fq=[open(out + m, "rb").read() for m in ("_1.fq", "_2.fq")], names=[r[2] for r in recs])
+
+
+@pytest.mark.parametrize("knobs", [dict(SCS_TEST_TRUTH_LDS="4096"), dict(SCS_TEST_TRUTH_LDS="1024"), dict(SCS_TEST_TRUTH_LDS=str(CUT_LDS)),
+                                   dict(SCS_TEST_TRUTH_LDS="24576", SCS_TEST_BATCH_SHIFT="5"), dict(SCS_TEST_BATCH_SHIFT="5")],
+                         ids=["lds4096", "lds1024", "lds256", "lds24576_batch32", "batch32"])
+def test_sam_under_a_cut_lds(knobs, cut_reference, tmp_path):
+    """The truth SAM does not depend on the LDS its emit pass may fill, nor on how the job is cut into batches: the file and the
+    FASTQ are the plain run's, byte for byte (cut_reference checks that one against the genome with check_sam(exact=True)).
+    k_truth_emit builds a workgroup's run (64 pairs of this job, about 40 KB) in LDS in one turn, or, where the run outgrows the
+    LDS, has every lane write its pair straight to memory; it refuses no pair.  lds4096, lds1024, lds256: every run outgrows the
+    LDS, every pair takes the direct write -- 256 is below any single pair: pair_floor gives 306 bytes for this job (asserted
+    here).  batch32: batches of 32 pairs, fewer lanes with a pair than the wave has, a short last batch, all in LDS.
+    lds24576_batch32: the 32-pair runs (about 20 KB) fit, so both paths meet in one file only where a batch's run is longer; the
+    bytes are the same either way."""
+    assert pair_floor(scssim_amd.truth_record_probe, min(cut_reference["names"], key=len), genome="A" * 60) > CUT_LDS
+    out, _ = _run(tmp_path, env=seams_env(**knobs), prof=cut_reference["prof"], fa=cut_reference["fa"], **CUT_JOB)
+    assert open(out + ".sam", "rb").read() == cut_reference["sam"]
+    assert [open(out + m, "rb").read() for m in ("_1.fq", "_2.fq")] == cut_reference["fq"]
 
 
 _ERR = r'''

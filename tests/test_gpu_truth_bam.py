@@ -13,6 +13,9 @@ import pytest
 from conftest import ROOT, seams_env
 
 from bam_cases import read_bam, reg2bin
+from test_gpu_truth import CUT_JOB, CUT_LDS, cut_job_inputs, pair_floor
+
+import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
@@ -161,6 +164,73 @@ def test_a_batch_smaller_than_one_block(models, tmp_path):
     bam = _check_job(out, res, True, min_records=100)
     batches = res["bam"]["k_truth"]["launches"] // 2
     assert batches > 1 and bam["members"] == 1 + batches + 1     # header, one block per batch, end of file
+
+
+# the job with the truth BAM or the truth SAM on the reference set: the yield must fail with SCS_EOVERFLOW and name the truth output
+_REFUSED = r'''
+import json, os, sys
+sys.path.insert(0, %(root)r)
+import numpy as np
+import scssim_amd
+from scssim_amd import ScsError, SCS_EOVERFLOW
+a = json.loads(%(args)r)
+out = a["out"]
+if a["kind"] == "bam":
+    g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a["ber"])
+    g.set_truth_bam(out + ".bam")
+else:
+    g = scssim_amd.GenReads(profile=a["prof"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a["ber"])
+    g.simuvars(a["ref"], None, None, None)
+    t = g.lift_segments()
+    np.savez(out + "_segs.npz", hap_off=t.hap_off, len=t.len, ref_pos=t.ref_pos, ref_rec=t.ref_rec, kind=t.kind, ref_lens=t.ref_lens)
+    g.set_truth_ref_sam(out + ".sam")
+g.create_frags(); g.amplify(); g.allocate_reads(0)
+res = dict(reads_requested=g.stats()["reads_requested"])
+try:
+    g.yield_reads(); raise SystemExit("a pair larger than the emit pass' LDS: no error")
+except ScsError as e:
+    res["code"], res["message"], res["overflow"] = e.code, str(e), SCS_EOVERFLOW
+g.close()
+res["live"] = list(scssim_amd.live_resources())
+print("RESULT " + json.dumps(res))
+'''
+
+
+@pytest.mark.parametrize("kind", ["bam", "ref"])
+def test_a_pair_larger_than_the_lds_is_refused(kind, models, tmp_path):
+    """The emit passes of the truth BAM and of the truth SAM on the reference refuse a pair that alone outgrows their LDS: with
+    SCS_TEST_TRUTH_LDS=256 the yield fails with SCS_EOVERFLOW, the message names the truth output, and the ctx closes with nothing
+    left alive.  bam: the 280-pair job of test_gpu_truth.py::test_sam_under_a_cut_lds.  ref: the variant-free simuvars genome of
+    test_gpu_truth_ref.py::test_plain_genome (100.5 kb reference) at 0.7x, 281 pairs.  256 is below any pair (pair_floor, on the
+    CPU, asserted here): the smallest pair of BAM records is 264 bytes, of records on the reference 324."""
+    if kind == "bam":
+        fa, prof = cut_job_inputs(tmp_path, models)
+        a = dict(CUT_JOB, kind=kind, fa=fa, prof=prof)
+    else:
+        ref = str(tmp_path / "ref.fa")
+        subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40500", "--seed", "17", "--ref-out", ref])
+        prof = _exact_profile(models["Illumina_HiSeq2500"], str(tmp_path / "x.profile"), 0.01, 0.01)
+        a = dict(CUT_JOB, kind=kind, ref=ref, prof=prof, cov=0.7)
+    a["out"] = str(tmp_path / "job")
+    r = subprocess.run([sys.executable, "-c", _REFUSED % dict(root=ROOT, args=json.dumps(a))], env=seams_env(SCS_TEST_TRUTH_LDS=str(CUT_LDS)),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    res = json.loads(r.stdout.split("RESULT ")[1])
+    print(res)
+    assert 200 <= res["reads_requested"] // 2 <= 400
+    assert res["code"] == res["overflow"] and "truth SAM / BAM" in res["message"], res
+    assert res["live"] == [0, 0, 0, 0]
+    if kind == "bam":
+        floor = pair_floor(scssim_amd.truth_bam_record_probe, "20_1_200000", genome="A" * 60)
+    else:
+        import numpy as np
+        from types import SimpleNamespace
+        t = np.load(a["out"] + "_segs.npz")
+        hap_lens = [60000, 60000, 40500, 40500]
+        assert t["len"].tolist() == hap_lens and t["ref_lens"].tolist() == [60000, 40500]      # one R segment per staged record
+        floor = pair_floor(scssim_amd.truth_ref_record_probe, "20_1_60000", table=SimpleNamespace(**{k: t[k] for k in ("hap_off", "len", "ref_pos", "ref_rec", "kind")}), hap_lens=hap_lens, ref_lens=t["ref_lens"], ref_names=["chr20", "chr21"])
+    print("smallest pair: %d bytes" % floor)
+    assert floor > CUT_LDS
 
 
 _ERR = r'''

@@ -71,10 +71,12 @@ def main():
             g.yield_reads_files(os.path.join(td, "reads_warm"), 1)
         for leg in [l for _ in range(a.repeats) for l in legs]:
             out = os.path.join(td, "reads_" + leg)
+            if have_ref:                                    # (one truth output per ctx: the last leg's is cleared before this leg's is set)
+                g.set_truth_ref_sam(None)
             g.set_truth_sam(out + ".sam" if leg == "on" else None)
             g.set_truth_bam(out + ".bam" if leg == "bam" else None)
-            if have_ref:
-                g.set_truth_ref_sam(out + ".ref.sam" if leg == "ref" else None)
+            if have_ref and leg == "ref":
+                g.set_truth_ref_sam(out + ".ref.sam")
             t = time.time()
             g.yield_reads_files(out, 1)
             wall = time.time() - t
