@@ -4,59 +4,47 @@ SAM of the same job lies inside the amplicon its name states, on its strand, and
 edges; BGZF; the CLI; the refusals and the ownership of the buffers.  Each job runs in a child process under its own time limit;
 the checks run here.  Run with `-m gpu`."""
 import gzip
-import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, seams_env
+from conftest import seams_env
 from amp_cases import codes, parse_table, table_from_oracle
-from test_gpu_truth import CIG, _oracle, _sam
+from gpu_child import run_child
+from gpu_readers import CIG, CLI, EOF_BLOCK, _oracle, _sam, _same, make_genome
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-EOF_BLOCK = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0])
-
 # one ctx, one allocated job: the table as text (plain, BGZF) and as arrays, then (sam) a yield with the truth SAM on.
 # variants: [{name, env}]: the plain file again under these seams (read at every call by the seams build)
 _CHILD = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
-import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, leg_env, open_job, yield_leg
+a = job_args()
+g = open_job(a)
 out = a["out"]
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 res = dict(plain=g.write_amplicons(out + ".tsv"), kt=g.amplicon_kernel_time(), bgzf=g.write_amplicons(out + ".tsv.gz", bgzf=True), fulls=g.stats()["full_amplicons"])
 np.savez(out + "_places.npz", **g.amplicon_places())
 for v in a.get("variants", []):
-    os.environ.update(v["env"])
-    res[v["name"]] = g.write_amplicons(out + "_" + v["name"] + ".tsv")
-    if v.get("bgzf"):
-        g.write_amplicons(out + "_" + v["name"] + ".tsv.gz", bgzf=True)
-    for k in v["env"]:
-        del os.environ[k]
+    with leg_env(v["env"]):
+        res[v["name"]] = g.write_amplicons(out + "_" + v["name"] + ".tsv")
+        if v.get("bgzf"):
+            g.write_amplicons(out + "_" + v["name"] + ".tsv.gz", bgzf=True)
 if a.get("sam"):
     g.set_truth_sam(out + ".sam")
-    f1, f2 = g.yield_reads()
-    open(out + "_1.fq", "wb").write(f1); open(out + "_2.fq", "wb").write(f2)
+    yield_leg(g, out, {})
     res["reads_written"] = g.stats()["reads_written"]
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(out, env=None, timeout=300, **a):
     a["out"] = str(out)
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ), capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return a["out"], json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 def _genome(fa):
@@ -89,11 +77,7 @@ def test_file_and_arrays_equal_the_oracles_tables(case, g1_job, oracle_bin, mode
     names, lens, G = _genome(fa)
     want, arr, most_full, most_semi = table_from_oracle(orc, names, lens, G)
     got = open(out + ".tsv").read()
-    if got != want:
-        gl, wl = got.split("\n"), want.split("\n")
-        bad = [i for i in range(min(len(gl), len(wl))) if gl[i] != wl[i]]
-        print("lines", len(gl), len(wl), "first differences", [(gl[i], wl[i]) for i in bad[:5]])
-    assert got == want
+    _same(got, want, case)
     assert res["plain"] == len(want) == os.path.getsize(out + ".tsv") and res["fulls"] == len(arr["rec"]) > 30000
     z = np.load(out + "_places.npz")
     assert z["rec"].dtype == np.uint32 and z["start"].dtype == np.uint64 and z["strand"].dtype == np.int8
@@ -160,8 +144,7 @@ def test_truth_sam_of_the_same_job_ber_001(models, golden_inputs, tmp_path):
 def test_chunk_and_lds_edges(models, tmp_path):
     """3: chunks of 257 amplicons (a workgroup and one lane), of 1, and larger than the job; an LDS run of 64 bytes, shorter than
     most lines and never a whole number of them: every setting writes the default's file, plain and (257, the LDS run) BGZF."""
-    fa = str(tmp_path / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "14000,11000", "--seed", "3", "--simu-out", fa])
+    fa = make_genome(str(tmp_path / "g.fa"), "14000,11000", 3)
     variants = [dict(name="c257", env=dict(SCS_TEST_AMP_CHUNK="257"), bgzf=True), dict(name="c1", env=dict(SCS_TEST_AMP_CHUNK="1")),
                 dict(name="cbig", env=dict(SCS_TEST_AMP_CHUNK="100000000")), dict(name="lds64", env=dict(SCS_TEST_AMP_LDS="64"), bgzf=True),
                 dict(name="c257lds48", env=dict(SCS_TEST_AMP_CHUNK="257", SCS_TEST_AMP_LDS="48"))]
@@ -190,8 +173,7 @@ def test_bgzf(g1_job):
 def test_cli(models, tmp_path):
     """5: `--amplicons out.tsv` and `--amplicons out.tsv.gz` beside a normal job write the same table; the job's FASTQ is the FASTQ
     of a run without the option."""
-    fa = str(tmp_path / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "14000,11000", "--seed", "3", "--simu-out", fa])
+    fa = make_genome(str(tmp_path / "g.fa"), "14000,11000", 3)
     base = [CLI, "genreads", "-i", fa, "-m", models["Illumina_HiSeq2500"], "-c", "2", "--seed", "5"]
     for name, extra in (("off", []), ("tsv", ["--amplicons", str(tmp_path / "a.tsv")]), ("gz", ["--amplicons", str(tmp_path / "a.tsv.gz")])):
         r = subprocess.run(base + ["-o", str(tmp_path / name)] + extra, capture_output=True, text=True, timeout=300)
@@ -208,22 +190,16 @@ def test_cli(models, tmp_path):
 
 
 _OWN = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
+import ctypes, os
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
-def fails(f, code, word):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and word in str(e), (code, word, e)
-        return
-    raise SystemExit("no error: " + word)
-out = %(out)r
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=%(prof)r, seed=5)
+from scssim_amd import SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
+from gpu_child import fails, job_args
+a = job_args()
+out = a["out"]
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
 fails(lambda: s.write_amplicons(out + "_s.tsv"), SCS_EINVAL, "sharded")
 fails(s.amplicon_places, SCS_EINVAL, "sharded")
-g = scssim_amd.GenReads(profile=%(prof)r, input_fasta=%(fa)r, coverage=3.0, seed=41)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=3.0, seed=41)
 fails(lambda: g.write_amplicons(out + "_early.tsv"), SCS_EINVAL, "scs_allocate_reads")
 fails(g.amplicon_places, SCS_EINVAL, "scs_allocate_reads")
 g.create_frags(); g.amplify()
@@ -243,7 +219,7 @@ after = scssim_amd.live_resources()
 assert after == before, (before, after)                    # the calls' buffers, streams, events and pinned blocks are gone: they were the calls' own
 f1, f2 = g.yield_reads()
 open(out + "_1.fq", "wb").write(f1); open(out + "_2.fq", "wb").write(f2)
-assert not __import__("os").path.exists(out + "_early.tsv") and not __import__("os").path.exists(out + "_s.tsv")
+assert not os.path.exists(out + "_early.tsv") and not os.path.exists(out + "_s.tsv")
 g.close(); s.close()
 assert scssim_amd.live_resources() == (0, 0, 0, 0), scssim_amd.live_resources()
 print("ok", size)
@@ -255,9 +231,7 @@ def test_refusals_and_ownership(g1_job, models, golden_inputs, tmp_path):
     the ctx writes the same table and yields the same FASTQ as the job that never failed (g1_job: equal to the oracle's in test
     1); SCS_EOVERFLOW for too small a cap; the call's buffers are gone when it returns, everything once the contexts are destroyed."""
     out = str(tmp_path / "own")
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"])],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_OWN, dict(out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"]), timeout=300, ok=True)
     ref, _ = g1_job
     assert open(out + ".tsv", "rb").read() == open(ref + ".tsv", "rb").read()
     for m in ("_1.fq", "_2.fq"):

@@ -4,38 +4,32 @@ byte; the same ctx's scs_amplicon_places agree; dense edits (ber = 0.01); slab, 
 and the ownership of the buffers.  Each job runs in a child process under its own time limit; the checks run here.
 Run with `-m gpu`."""
 import gzip
-import json
 import os
 import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, seams_env
+from conftest import seams_env
 from amp_cases import parse_table, table_from_oracle
+from gpu_child import run_child
+from gpu_readers import CLI, EOF_BLOCK, _oracle, _same, make_genome
 from site_cases import KEYS, fasta, figures, header, most_alts_at_a_coordinate, sites_from_table
-from test_gpu_truth import _oracle
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-EOF_BLOCK = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0])
-
 # one ctx, one allocated job: the table as VCF (min_reads 0 and 1, BGZF) and as arrays, the amplicon places (and table) of the same ctx.
 # variants: [{name, env, bgzf}]: the plain file again under these seams (read at every call by the seams build)
 _CHILD = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
 import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, leg_env, open_job
+a = job_args()
+g = open_job(a)
 out = a["out"]
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 live0 = scssim_amd.live_resources()
 res = dict(plain=g.write_artefacts(out + ".vcf"), kt=g.artefact_kernel_time(), live0=live0, live1=scssim_amd.live_resources())
 res["min1"] = g.write_artefacts(out + "_m1.vcf", min_reads=1)
@@ -49,21 +43,17 @@ np.savez(out + "_places.npz", **g.amplicon_places())
 if a.get("table"):
     g.write_amplicons(out + ".tsv")
 for v in a.get("variants", []):
-    os.environ.update(v["env"])
-    res[v["name"]] = g.write_artefacts(out + "_" + v["name"] + ".vcf")
-    if v.get("bgzf"):
-        g.write_artefacts(out + "_" + v["name"] + ".vcf.gz", bgzf=True)
-    for k in v["env"]:
-        del os.environ[k]
-print("RESULT " + json.dumps(res))
+    with leg_env(v["env"]):
+        res[v["name"]] = g.write_artefacts(out + "_" + v["name"] + ".vcf")
+        if v.get("bgzf"):
+            g.write_artefacts(out + "_" + v["name"] + ".vcf.gz", bgzf=True)
+emit(res)
 '''
 
 
 def _run(out, env=None, timeout=300, **a):
     a["out"] = str(out)
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ), capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return a["out"], json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 JOBS = {"g1_hiseq2500_pe": ("Illumina_HiSeq2500", "PE", 3.0, 41), "g3_hiseq2000_se": ("Illumina_HiSeq2000", "SE", 2.0, 23), "g2_xten_pe_nblock": ("Illumina_HiSeqXTen", "PE", 2.0, 41)}
@@ -103,14 +93,6 @@ def _reference(case, oracle_bin, models, golden_inputs, tmp_path):
     assert names == scssim_amd.fasta_probe(fa)[0]
     text, _, _, _ = table_from_oracle(orc, names, lens, G)
     return names, lens, G, parse_table(text)
-
-
-def _same(got, want, what):
-    if got != want:
-        gl, wl = got.split("\n"), want.split("\n")
-        bad = [i for i in range(min(len(gl), len(wl))) if gl[i] != wl[i]]
-        print(what, "lines", len(gl), len(wl), "first differences", [(gl[i], wl[i]) for i in bad[:5]])
-    assert got == want, what
 
 
 @pytest.mark.parametrize("case", list(JOBS))
@@ -222,8 +204,7 @@ def test_bgzf(g1_job):
 def test_cli(models, tmp_path):
     """6: `--artefacts x.vcf.gz --artefacts-min-reads 1` beside `--amplicons`: the table of the Python binding on the same job; neither
     option changes the FASTQ files."""
-    fa = str(tmp_path / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "14000,11000", "--seed", "3", "--simu-out", fa])
+    fa = make_genome(str(tmp_path / "g.fa"), "14000,11000", 3)
     base = [CLI, "genreads", "-i", fa, "-m", models["Illumina_HiSeq2500"], "-c", "2", "--seed", "5"]
     for name, extra in (("off", []), ("gz", ["--artefacts", str(tmp_path / "a.vcf.gz"), "--artefacts-min-reads", "1", "--amplicons", str(tmp_path / "a.tsv")]),
                         ("vcf", ["--artefacts", str(tmp_path / "a.vcf")])):
@@ -239,22 +220,16 @@ def test_cli(models, tmp_path):
 
 
 _OWN = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
+import ctypes, os
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
-def fails(f, code, word):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and word in str(e), (code, word, e)
-        return
-    raise SystemExit("no error: " + word)
-out = %(out)r
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=%(prof)r, seed=5)
+from scssim_amd import SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
+from gpu_child import fails, job_args
+a = job_args()
+out = a["out"]
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
 fails(lambda: s.write_artefacts(out + "_s.vcf"), SCS_EINVAL, "sharded")
 fails(s.artefact_sites, SCS_EINVAL, "sharded")
-g = scssim_amd.GenReads(profile=%(prof)r, input_fasta=%(fa)r, coverage=3.0, seed=41)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=3.0, seed=41)
 fails(lambda: g.write_artefacts(out + "_early.vcf"), SCS_EINVAL, "scs_allocate_reads")
 fails(g.artefact_sites, SCS_EINVAL, "scs_allocate_reads")
 g.create_frags(); g.amplify()
@@ -279,7 +254,6 @@ assert r["sites"] == total
 assert scssim_amd.live_resources() == before, (before, scssim_amd.live_resources())       # after calls: every buffer, stream and event of a call is gone
 f1, f2 = g.yield_reads()
 open(out + "_1.fq", "wb").write(f1); open(out + "_2.fq", "wb").write(f2)
-import os
 assert not os.path.exists(out + "_early.vcf") and not os.path.exists(out + "_s.vcf") and not os.path.exists(out + "_flag.vcf")
 g.close(); s.close()
 assert scssim_amd.live_resources() == (0, 0, 0, 0), scssim_amd.live_resources()
@@ -292,9 +266,7 @@ def test_refusals_and_ownership(g1_job, oracle_bin, models, golden_inputs, tmp_p
     opened, after which the ctx writes the table of the job that never failed and yields the oracle's FASTQ; SCS_EOVERFLOW for too
     small a cap, with the count; scs_live_resources unchanged after a call and after a failed call, zero once the contexts are gone."""
     out = str(tmp_path / "own")
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"])],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_OWN, dict(out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"]), timeout=300, ok=True)
     ref, _ = g1_job
     assert open(out + ".vcf", "rb").read() == open(ref + ".vcf", "rb").read() == open(out + "_null.vcf", "rb").read()
     orc = str(tmp_path / "orc")

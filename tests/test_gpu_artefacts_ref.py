@@ -1,51 +1,37 @@
 """GPU tests of the artefact table on the original reference (scs_write_artefacts_ref / scs_artefact_ref_sites / `scssim genreads
 --lift --artefacts-ref`).  The reference side of every check is the per-base restatement of
 tests/site_ref_cases.py over what the SAME ctx reports: amplicon_places(), download_read_numbers(), artefact_sites(0), the staged
-bases and lift_segments().  The golden simuvars genome; the dense layout of test_gpu_lift.py with het substitutions and a raised
+bases and lift_segments().  The golden simuvars genome; the dense layout of tests/lift_cases.py with het substitutions and a raised
 error rate, held to what it must reach; a plain genome; slab, chunk and LDS edges, BGZF and a second call; nothing else moves; the
 two-step CLI flow; refusals and ownership.  Each job runs in a child process under its own time limit; the checks run here.
 Run with `-m gpu`."""
 import gzip
-import json
 import os
 import subprocess
-import sys
-import zlib
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, seams_env
+from conftest import seams_env
+from gpu_child import run_child, sv_ref  # noqa: F401 (a fixture)
+from gpu_readers import CLI, SV, Segs, _inflate, _same, make_genome
+from lift_cases import write_dense_het_inputs
 from site_ref_cases import KEYS, conservation, header, pieces_of, restate
-from test_gpu_lift import Segs, write_dense_inputs
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-SV = os.path.join(GOLDEN, "simuvars")
-EOF_BLOCK = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0])
-
 # one ctx, one genome (built by simuvars, or a FASTA and its lift file), one allocated job: the table as VCF (min_reads 0 and 1, BGZF,
 # a second call) and as arrays, what the restatement reads from the same ctx, then the plain file again under each variant's seams
 # (read at every call by the seams build).  moves: the haplotype table, a yield with site support and its table, before and after.
 _CHILD = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
 import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, leg_env, open_job, yield_leg
+a = job_args()
+g = open_job(a, lift_file=True, segs=True)
 out = a["out"]
-if a.get("fasta"):
-    g.load_genome(a["fasta"]); g.load_lift(a["lift"])
-else:
-    g.simuvars(a["ref"], a.get("snp"), a.get("vars"))
-g.write_lift(out + ".lift")
-t = g.lift_segments()
-np.savez(out + "_segs.npz", hap_off=t.hap_off, len=t.len, ref_pos=t.ref_pos, ref_rec=t.ref_rec, kind=t.kind, ref_lens=t.ref_lens)
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 res = {}
 import time
 t0 = time.time(); res["times"] = []
@@ -57,8 +43,7 @@ def moves(tag):
     res["hap_" + tag] = g.write_artefacts(out + "_hap_" + tag + ".vcf")
     np.savez(out + "_hapsites_" + tag + ".npz", **g.artefact_sites())
     g.set_site_support(True, 0); g.set_seed(a["seed"])
-    f1, f2 = g.yield_reads()
-    open(out + "_" + tag + "_1.fq", "wb").write(f1); open(out + "_" + tag + "_2.fq", "wb").write(f2)
+    yield_leg(g, out + "_" + tag, {})
     g.write_site_support(out + "_sup_" + tag + ".vcf")
     g.set_site_support(False)
 if a.get("moves"):
@@ -74,8 +59,8 @@ res["again"] = g.write_artefacts_ref(out + "_again.vcf")
 res["kt_before_arrays"] = g.artefact_ref_kernel_time()         # (of a call that wrote every site)
 for m in (0, 1):
     s = g.artefact_ref_sites(m)
-    res["unlifted%%d" %% m] = s.pop("unlifted")
-    np.savez(out + "_sites%%d.npz" %% m, **s)
+    res["unlifted%d" % m] = s.pop("unlifted")
+    np.savez(out + "_sites%d.npz" % m, **s)
 res["kt_after_arrays"] = g.artefact_ref_kernel_time()
 res["live2"] = scssim_amd.live_resources()
 lap("the table in every form")
@@ -86,22 +71,18 @@ np.savez(out + "_hap.npz", **g.artefact_sites(0))
 np.save(out + "_rn.npy", g.download_read_numbers())
 np.save(out + "_codes.npy", g.download_genome()["codes"])
 for v in a.get("variants", []):
-    os.environ.update(v["env"])
-    res[v["name"]] = g.write_artefacts_ref(out + "_" + v["name"] + ".vcf")
-    if v.get("bgzf"):
-        g.write_artefacts_ref(out + "_" + v["name"] + ".vcf.gz", bgzf=True)
-    for k in v["env"]:
-        del os.environ[k]
+    with leg_env(v["env"]):
+        res[v["name"]] = g.write_artefacts_ref(out + "_" + v["name"] + ".vcf")
+        if v.get("bgzf"):
+            g.write_artefacts_ref(out + "_" + v["name"] + ".vcf.gz", bgzf=True)
     lap(v["name"])
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(out, env=None, timeout=300, **a):
     a["out"] = str(out)
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ), capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return a["out"], json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 class Inputs:
@@ -121,27 +102,6 @@ class Inputs:
 
     def restate(self, min_reads=0):
         return restate(self.starts, self.lens, self.reads, self.ed_g, self.hap["alt"], self.hap["na"], self.hap["nr"], self.G, self.seg, self.ref_lens, self.ref_names, min_reads)
-
-
-def _same(got, want, what):
-    if got != want:
-        gl, wl = got.split("\n"), want.split("\n")
-        bad = [i for i in range(min(len(gl), len(wl))) if gl[i] != wl[i]]
-        print(what, "lines", len(gl), len(wl), "first differences", [(gl[i], wl[i]) for i in bad[:5]])
-    assert got == want, what
-
-
-def _inflate(z):
-    """the members of a BGZF file, one by one; the last one is the end-of-file block"""
-    assert z.endswith(EOF_BLOCK)
-    text, at = b"", 0
-    while at < len(z):
-        assert z[at:at + 4] == b"\x1f\x8b\x08\x04" and z[at + 12:at + 14] == b"BC"
-        size = int.from_bytes(z[at + 16:at + 18], "little") + 1
-        text += zlib.decompress(z[at + 18:at + size - 8], -15)
-        at += size
-    assert at == len(z)
-    return text
 
 
 def check_job(out, res, what):
@@ -176,14 +136,6 @@ def check_job(out, res, what):
     return inp, arr, unl, extra
 
 
-@pytest.fixture(scope="module")
-def sv_ref(tmp_path_factory):
-    d = tmp_path_factory.mktemp("svref")
-    ref = str(d / "ref.fa")
-    open(ref, "wb").write(gzip.open(os.path.join(SV, "ref.fa.gz")).read())
-    return ref
-
-
 def test_golden_simuvars_genome(sv_ref, models, tmp_path):
     """1: the golden simuvars genome (1.5 Mb staged, CN 0 .. 8, het insertions / deletions / substitutions, three reference records),
     PE HiSeq2500 at 2x, the default error rate: file and arrays equal the restatement at min_reads 0 and 1; the contig lines are the
@@ -197,26 +149,6 @@ def test_golden_simuvars_genome(sv_ref, models, tmp_path):
 
 # ---- 2: the dense case
 DENSE_BER, DENSE_COV, DENSE_SEED = 0.01, 6.0, 19
-DENSE_LONG_INS = 2500                                      # one insertion that holds whole amplicons (they are 1 to 2 kb; the layout's own insertions are 130 bases)
-
-
-def write_dense_het_inputs(d):
-    """test_gpu_lift.write_dense_inputs' reference, and a copy of its variation file with a het substitution every 50 bases (REF as the
-    reference has it, ALT the next base), one het insertion of 2500 bases and a stretch of 600 bases at CN 4 (two copies in tandem on
-    either haplotype)."""
-    ref, var = write_dense_inputs(d)
-    seq = "".join(open(ref).read().split("\n")[1:])
-    nxt = dict(A="C", C="G", G="T", T="A")
-    lines = open(var).read().rstrip("\n").split("\n")
-    lines += ["s\tchr1\t%d\t%s\t%s\thet" % (p, seq[p - 1], nxt[seq[p - 1]]) for p in range(325, 59500, 50)]
-    rng = np.random.default_rng(3)
-    lines.append("i\tchr1\t31000\t%s\thet" % bytes(np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, DENSE_LONG_INS)]).decode())
-    lines.append("c\tchr1\t52001\t52600\t4\t2")             # a tandem unit shorter than an amplicon: two pieces of one amplicon overlap on the reference
-    var2 = str(d / "dense_het_vars.txt")
-    open(var2, "w").write("\n".join(lines) + "\n")
-    return ref, var2
-
-
 DENSE_VARIANTS = [dict(name="slab3", env=dict(SCS_TEST_SITE_SLAB="20000")),                       # 3 slabs
                   dict(name="slab1200", env=dict(SCS_TEST_SITE_SLAB="50")),                       # 1200 slabs: more than the counting pass sums in LDS; a copy junction jumps 80 slabs back
                   dict(name="chunk257", env=dict(SCS_TEST_AMP_CHUNK="257")), dict(name="lds16", env=dict(SCS_TEST_SITE_LDS="16")),
@@ -309,8 +241,7 @@ def test_two_step_flow_through_the_cli(dense_job, models, tmp_path):
 def test_plain_genome(models, tmp_path):
     """3: no variant files, two identical haplotypes: every line's NA / NR is the sum of the haplotype table's lines at that
     coordinate, TA / TR the sum of the two haplotypes' coverage; nothing is unlifted."""
-    ref = str(tmp_path / "ref.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40500", "--seed", "17", "--ref-out", ref])
+    ref = make_genome(str(tmp_path / "ref.fa"), "60000,40500", 17, ref=True)
     out, res = _run(tmp_path / "job", prof=models["Illumina_HiSeq2500"], ref=ref, cov=3.0, layout="PE", seed=3)
     inp, arr, unl, extra = check_job(out, res, "plain")
     assert unl == (0, 0) and len(inp.seg) == 4 and inp.ref_lens == [60000, 40500]
@@ -333,40 +264,33 @@ def test_plain_genome(models, tmp_path):
 
 
 _OWN = r'''
-import sys
-sys.path.insert(0, %(root)r)
+import ctypes
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL, SCS_EIO
-def fails(f, code, *words):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and all(w in str(e) for w in words), (code, words, e)
-        return
-    raise SystemExit("no error: " + " ".join(words))
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=%(prof)r, seed=5)
-fails(lambda: s.write_artefacts_ref(%(tmp)r + "/s.vcf"), SCS_EINVAL, "scs_write_artefacts_ref", "sharded")
+from scssim_amd import SCS_EINVAL, SCS_EIO
+from gpu_child import fails, job_args
+a = job_args()
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
+fails(lambda: s.write_artefacts_ref(a["tmp"] + "/s.vcf"), SCS_EINVAL, "scs_write_artefacts_ref", "sharded")
 fails(s.artefact_ref_sites, SCS_EINVAL, "scs_artefact_ref_sites", "sharded")
-g = scssim_amd.GenReads(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=2.0, seed=5)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 live = scssim_amd.live_resources()
-fails(lambda: g.write_artefacts_ref(%(tmp)r + "/a.vcf"), SCS_EINVAL, "no lift table", "scs_simuvars", "scs_load_lift")
+fails(lambda: g.write_artefacts_ref(a["tmp"] + "/a.vcf"), SCS_EINVAL, "no lift table", "scs_simuvars", "scs_load_lift")
 fails(g.artefact_ref_sites, SCS_EINVAL, "no lift table")
 assert scssim_amd.live_resources() == live
-g.simuvars(%(ref)r, None, None)                              # a genome with its table, nothing allocated yet
-fails(lambda: g.write_artefacts_ref(%(tmp)r + "/a.vcf"), SCS_EINVAL, "scs_allocate_reads")
+g.simuvars(a["ref"], None, None)                              # a genome with its table, nothing allocated yet
+fails(lambda: g.write_artefacts_ref(a["tmp"] + "/a.vcf"), SCS_EINVAL, "scs_allocate_reads")
 fails(g.artefact_ref_sites, SCS_EINVAL, "scs_allocate_reads")
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 live = scssim_amd.live_resources()
-fails(lambda: g.write_artefacts_ref(%(tmp)r + "/no/such/dir/a.vcf"), SCS_EIO, "scs_write_artefacts_ref", "can not open")
+fails(lambda: g.write_artefacts_ref(a["tmp"] + "/no/such/dir/a.vcf"), SCS_EIO, "scs_write_artefacts_ref", "can not open")
 fails(lambda: g.write_artefacts_ref(""), SCS_EINVAL, "no path")
 assert scssim_amd.live_resources() == live                   # a failed call leaves nothing
-r = g.write_artefacts_ref(%(tmp)r + "/a.vcf")
+r = g.write_artefacts_ref(a["tmp"] + "/a.vcf")
 assert r["sites"] > 0 and scssim_amd.live_resources() == live
-import ctypes
-assert g._L.scs_write_artefacts_ref(g._ctx, (%(tmp)r + "/b.vcf").encode(), 2, 0, None, None, None) == SCS_EINVAL      # an unknown flag
-assert g._L.scs_write_artefacts_ref(g._ctx, (%(tmp)r + "/b.vcf").encode(), 0, 0, None, None, None) == 0              # every output pointer may be NULL
-assert open(%(tmp)r + "/b.vcf").read() == open(%(tmp)r + "/a.vcf").read()
+assert g._L.scs_write_artefacts_ref(g._ctx, (a["tmp"] + "/b.vcf").encode(), 2, 0, None, None, None) == SCS_EINVAL      # an unknown flag
+assert g._L.scs_write_artefacts_ref(g._ctx, (a["tmp"] + "/b.vcf").encode(), 0, 0, None, None, None) == 0              # every output pointer may be NULL
+assert open(a["tmp"] + "/b.vcf").read() == open(a["tmp"] + "/a.vcf").read()
 n = ctypes.c_uint64()
 g._L.scs_artefact_ref_sites.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
 assert g._L.scs_artefact_ref_sites(g._ctx, 0, *([None] * 8), 0, ctypes.byref(n), None) == scssim_amd.SCS_EOVERFLOW and n.value == r["sites"]
@@ -381,6 +305,4 @@ print("ok")
 def test_refusals_and_ownership(sv_ref, models, golden_inputs, tmp_path):
     """6: a sharded ctx, a genome without a lift table, a call before allocate_reads and an unwritable path are refused by code and
     words; the live resources read the same around good and failed calls, and zero after scs_destroy."""
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=sv_ref, tmp=str(tmp_path))],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_OWN, dict(prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=sv_ref, tmp=str(tmp_path)), timeout=300, ok=True)

@@ -6,69 +6,61 @@ must also equal the host emulation's (scs_bgzf_probe), which pins sizes, offsets
 One child process per probe does all the GPU work and writes what it got to files; every check runs here."""
 import json
 import os
-import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 import bgzf_cases as bc
+from gpu_child import run_child
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
 _BGZF_CHILD = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import json, os
 import scssim_amd, bgzf_cases as bc
-out, guards = %(out)r, {}
+from gpu_child import job_args
+out, guards = job_args()["out"], {}
 for name in bc.CASES:
     for zbase in bc.ZBASES[name]:
         z, ok = scssim_amd.bgzf_device_probe(bc.data(name), zbase)
-        open(os.path.join(out, "%%s.z%%d.bin" %% (name, zbase)), "wb").write(z)
-        guards["%%s.z%%d" %% (name, zbase)] = ok
+        open(os.path.join(out, "%s.z%d.bin" % (name, zbase)), "wb").write(z)
+        guards["%s.z%d" % (name, zbase)] = ok
 json.dump(guards, open(os.path.join(out, "guards.json"), "w"))
 print("bgzf child ok")
 '''
 
 _SCAN_CHILD = r'''
-import os, sys
 import numpy as np
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import scssim_amd, bgzf_cases as t
+from gpu_child import job_args
 res = {}
 for kind in ("small", "full"):
     for n in t.SCAN_SIZES:
-        res["alone.%%s.%%d" %% (kind, n)] = scssim_amd.scan_probe(t.scan_input(n, kind))
+        res["alone.%s.%d" % (kind, n)] = scssim_amd.scan_probe(t.scan_input(n, kind))
         o0, o1 = scssim_amd.scan_probe(t.scan_input(t.scan_partner(n), kind, 1), t.scan_input(n, kind))
-        res["pair0.%%s.%%d" %% (kind, n)], res["pair1.%%s.%%d" %% (kind, n)] = o0, o1
+        res["pair0.%s.%d" % (kind, n)], res["pair1.%s.%d" % (kind, n)] = o0, o1
     for tag, n0, n1 in (("n1_zero", 1000, 0), ("n0_zero", 0, 1000), ("both_zero", 0, 0)):
         o0, o1 = scssim_amd.scan_probe(t.scan_input(n0, kind, 2), t.scan_input(n1, kind, 3))
-        res["%%s0.%%s" %% (tag, kind)], res["%%s1.%%s" %% (tag, kind)] = o0, o1
-np.savez(%(out)r, **res)
+        res["%s0.%s" % (tag, kind)], res["%s1.%s" % (tag, kind)] = o0, o1
+np.savez(job_args()["out"], **res)
 print("scan child ok")
 '''
-
-
-def _child(code, timeout):
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ), capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, "exit %d\n%s\n%s" % (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
 
 
 @pytest.fixture(scope="module")
 def device_bgzf(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("bgzf_dev"))
-    _child(_BGZF_CHILD % dict(root=ROOT, out=out), 900)
+    run_child(_BGZF_CHILD, dict(out=out), timeout=900, ok=True)
     return out, json.load(open(os.path.join(out, "guards.json")))
 
 
 @pytest.fixture(scope="module")
 def device_scan(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("scan_dev") / "scan.npz")
-    _child(_SCAN_CHILD % dict(root=ROOT, out=out), 600)
+    run_child(_SCAN_CHILD, dict(out=out), timeout=600, ok=True)
     return np.load(out)
 
 

@@ -3,72 +3,47 @@ job gives, read by read; they do not depend on batch cuts, the sink, its writers
 the GPU; the FASTQ does not change; the file, the CLI, the refusals and the ownership of the buffers.  Each job runs in a child
 process under its own time limit; the checks run here.  Run with `-m gpu`."""
 import gzip
-import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, seams_env
-from test_gpu_truth import CIG, _exact_profile, _sam
+from conftest import seams_env
+from gpu_child import run_child
+from gpu_readers import CIG, CLI, _exact_profile, _sam, make_genome
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-
 # one ctx, one amplified job, then a yield per leg: {name, w (0: depth off), sink (callback / null / files / device), sam, writers, ...}
 _CHILD = r'''
-import json, os, sys, ctypes
-sys.path.insert(0, %(root)r)
 import numpy as np
-import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], isize=a.get("isize", 260), ber=a.get("ber", 3.4e-4))
-out = a["out"]
-g.create_frags(); g.amplify(); g.allocate_reads(0)
+from gpu_child import emit, job_args, open_job, yield_leg
+a = job_args()
+g = open_job(a)
 res = {}
 for leg in a["legs"]:
-    pre = out + "_" + leg["name"]
+    pre = a["out"] + "_" + leg["name"]
     g.set_seed(a["seed"])
     g.set_depth(leg.get("w", 0))
     g.set_truth_sam(pre + ".sam" if leg.get("sam") else None)
-    kind = leg.get("sink", "callback")
-    if kind == "callback":
-        f1, f2 = g.yield_reads()
-        open(pre + "_1.fq", "wb").write(f1); open(pre + "_2.fq", "wb").write(f2)
-    elif kind == "null":
-        g.yield_reads(collect=False)
-    elif kind == "files":
-        g.yield_reads_files(pre, leg.get("writers", 1), leg.get("generations", 1), bgzf=leg.get("bgzf", False))
-    else:
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]; hip.hipFree.argtypes = [ctypes.c_void_p]
-        d1, d2, cap = ctypes.c_void_p(), ctypes.c_void_p(), 64 << 20
-        assert hip.hipMalloc(ctypes.byref(d1), cap) == 0 and hip.hipMalloc(ctypes.byref(d2), cap) == 0
-        g.yield_reads_device(d1, cap, d2, cap)
-        hip.hipFree(d1); hip.hipFree(d2)
+    yield_leg(g, pre, leg)
     res[leg["name"]] = dict(reads_written=g.stats()["reads_written"], k_depth=g.kernel_times()["k_depth"], k_reads=g.kernel_times()["k_reads"])
     if leg.get("w"):
         r, b, off = g.depth()
         np.savez(pre + "_depth.npz", reads=r, bases=b, off=off)
         if leg.get("write"):
             g.write_depth(pre + ".tsv")
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(tmp_path, legs, env=None, timeout=300, **a):
     a.setdefault("out", str(tmp_path / "job"))
     a["legs"] = legs
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ),
-                       capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    res = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
-    return a["out"], res
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 def _arrays(out, name):
@@ -132,8 +107,7 @@ def test_counters_equal_the_truth_sam_of_the_same_job(case, model, layout, cov, 
 def test_frequent_indels(variant, models, tmp_path):
     """2: the exact-placement model of test_gpu_truth.py with indel rates at which most reads carry events, at bins of 1 and 64
     bases against the SAM.  replay: every read with events has them drawn again (SCS_EV_REPLAY), the other branch of read_place."""
-    fa = str(tmp_path / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40000", "--seed", "17", "--simu-out", fa])
+    fa = make_genome(str(tmp_path / "g.fa"), "60000,40000", 17)
     prof = _exact_profile(models["Illumina_HiSeq2500"], str(tmp_path / "x.profile"), 0.01, 0.01)
     env = seams_env(SCS_EV_REPLAY="1") if variant == "replay" else None
     widths = (1, 64) if variant == "plain" else (64,)
@@ -226,24 +200,18 @@ def test_depth_file_and_cli(models, golden_inputs, tmp_path):
 
 
 _OWN = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
+import ctypes
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL, SCS_EOVERFLOW
-def fails(f, code, word):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and word in str(e), (code, word, e)
-        return
-    raise SystemExit("no error: " + word)
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=%(prof)r, seed=5)
+from scssim_amd import SCS_EINVAL, SCS_EOVERFLOW
+from gpu_child import fails, job_args
+a = job_args()
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
 s.set_depth(1000)
 fails(s.depth_bins, SCS_EINVAL, "no genome")
 fails(s.yield_reads, SCS_EINVAL, "scs_set_depth")
 s.set_depth(0)
 fails(s.yield_reads, SCS_EINVAL, "scs_allocate_reads")       # the refusal is gone: what is missing now is the job itself
-g = scssim_amd.GenReads(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=2.0, seed=5)
 fails(g.depth_bins, SCS_EINVAL, "off")
 g.set_depth(1000)
 n, w = g.depth_bins()
@@ -272,6 +240,4 @@ print("ok")
 def test_refusals_and_ownership(models, golden_inputs, tmp_path):
     """5: a sharded ctx is refused at the yield call by name and is rid of the refusal after set_depth(0); no download before a yield,
     none into too small a buffer; the timer counts launches only with depth on; nothing is left once the contexts are destroyed."""
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"])],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_OWN, dict(prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"]), timeout=300, ok=True)

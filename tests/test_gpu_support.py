@@ -1,128 +1,67 @@
 """GPU tests of the site support (scs_set_site_support / scssim genreads --support): the six counters per artefact position equal
-a pileup of the truth SAM of the same yield call, made here in numpy; they do not depend on the sink, its writers, batch cuts, the
+a pileup of the truth SAM of the same yield call, made in numpy (tests/support_cases.py); they do not depend on the sink, its writers, batch cuts, the
 LDS table's size, the slabs of the site table or whether the text leaves the GPU; nothing else moves; the file, the CLI, the
 refusals and the ownership of the buffers.  Each job runs in a child process under its own time limit; the checks run here.
 Run with `-m gpu`."""
 import gzip
-import json
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, seams_env
-from test_gpu_truth import CIG, _exact_profile, _sam
+from conftest import seams_env
+from gpu_child import run_child
+from gpu_readers import CLI, EOF_BLOCK, _exact_profile, _sam
+from support_cases import pileup_from_sam
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-EOF_BLOCK = bytes([0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0])
 KEYS = ("rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")
 SUFFIX_HEADER = [b'##INFO=<ID=DP,Number=1,Type=Integer,', b'##INFO=<ID=AD,Number=2,Type=Integer,', b'##INFO=<ID=DL,Number=1,Type=Integer,']
 
 # one ctx, one allocated job, then a yield per leg: {name, sup (min_reads; absent: off), w (depth bin width, 0: off), sam, sink
 # (callback / null / files / device), writers, generations, bgzf, env (seams set for the leg), write (the files of the table)}
 _CHILD = r'''
-import json, os, sys, ctypes
-sys.path.insert(0, %(root)r)
 import numpy as np
 import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], isize=a.get("isize", 260), ber=a.get("ber", 3.4e-4))
-out = a["out"]
-g.create_frags(); g.amplify(); g.allocate_reads(0)
+from gpu_child import emit, job_args, leg_env, open_job, yield_leg
+a = job_args()
+g = open_job(a)
 res = {}
 for leg in a["legs"]:
-    pre = out + "_" + leg["name"]
-    os.environ.update(leg.get("env", {}))
-    g.set_seed(a["seed"])
-    on = "sup" in leg
-    g.set_site_support(on, leg.get("sup", 0))
-    g.set_depth(leg.get("w", 0))
-    g.set_truth_sam(pre + ".sam" if leg.get("sam") else None)
-    kind = leg.get("sink", "callback")
-    if kind == "callback":
-        f1, f2 = g.yield_reads()
-        open(pre + "_1.fq", "wb").write(f1); open(pre + "_2.fq", "wb").write(f2)
-    elif kind == "null":
-        g.yield_reads(collect=False)
-    elif kind == "files":
-        g.yield_reads_files(pre, leg.get("writers", 1), leg.get("generations", 1), bgzf=leg.get("bgzf", False))
-    else:
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]; hip.hipFree.argtypes = [ctypes.c_void_p]
-        d1, d2, cap = ctypes.c_void_p(), ctypes.c_void_p(), 64 << 20
-        assert hip.hipMalloc(ctypes.byref(d1), cap) == 0 and hip.hipMalloc(ctypes.byref(d2), cap) == 0
-        g.yield_reads_device(d1, cap, d2, cap)
-        hip.hipFree(d1); hip.hipFree(d2)
-    r = dict(reads_written=g.stats()["reads_written"], k_support=g.site_support_kernel_time(), k_reads=g.kernel_times()["k_reads"])
-    if leg.get("w"):
-        dr, db, off = g.depth()
-        np.savez(pre + "_depth.npz", reads=dr, bases=db, off=off)
-    if on:
-        np.savez(pre + "_support.npz", **g.site_support())
-        np.savez(pre + "_sites.npz", **g.artefact_sites(leg["sup"]))
-        if leg.get("write"):
-            r["plain"] = g.write_site_support(pre + ".vcf")
-            r["bgzf"] = g.write_site_support(pre + ".vcf.gz", bgzf=True)
-            r["art"] = g.write_artefacts(pre + "_art.vcf", min_reads=leg["sup"])
-        g.set_site_support(False)
-    for k in leg.get("env", {}):
-        del os.environ[k]
+    pre = a["out"] + "_" + leg["name"]
+    with leg_env(leg.get("env", {})):
+        g.set_seed(a["seed"])
+        on = "sup" in leg
+        g.set_site_support(on, leg.get("sup", 0))
+        g.set_depth(leg.get("w", 0))
+        g.set_truth_sam(pre + ".sam" if leg.get("sam") else None)
+        yield_leg(g, pre, leg)
+        r = dict(reads_written=g.stats()["reads_written"], k_support=g.site_support_kernel_time(), k_reads=g.kernel_times()["k_reads"])
+        if leg.get("w"):
+            dr, db, off = g.depth()
+            np.savez(pre + "_depth.npz", reads=dr, bases=db, off=off)
+        if on:
+            np.savez(pre + "_support.npz", **g.site_support())
+            np.savez(pre + "_sites.npz", **g.artefact_sites(leg["sup"]))
+            if leg.get("write"):
+                r["plain"] = g.write_site_support(pre + ".vcf")
+                r["bgzf"] = g.write_site_support(pre + ".vcf.gz", bgzf=True)
+                r["art"] = g.write_artefacts(pre + "_art.vcf", min_reads=leg["sup"])
+            g.set_site_support(False)
     res[leg["name"]] = r
 g.close()
 res["live_end"] = scssim_amd.live_resources()
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(tmp_path, legs, env=None, timeout=300, **a):
     a.setdefault("out", str(tmp_path / "job"))
     a["legs"] = legs
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ),
-                       capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    res = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
-    return a["out"], res
-
-
-CLS = {"A": 0, "C": 1, "G": 2, "T": 3}
-
-
-def pileup_from_sam(path, rec, pos):
-    """The contract from the SAM alone: (counts [positions, 6], positions' index per site, figures) at the distinct coordinates of
-    the sites (rec, pos).  POS, CIGAR and SEQ; inserted bases are skipped, D gives class 5."""
-    hdr, recs = _sam(path)
-    sq = [(h.split("\t")[1][3:], int(h.split("\t")[2][3:])) for h in hdr if h.startswith("@SQ")]
-    off = np.concatenate([[0], np.cumsum([ln for _, ln in sq])]).astype(np.int64)
-    first = {name: off[i] for i, (name, _) in enumerate(sq)}
-    x = off[rec.astype(np.int64)] + pos.astype(np.int64)
-    assert (np.diff(x) >= 0).all()
-    P, site_pos = np.unique(x, return_inverse=True)
-    cnt = np.zeros((len(P), 6), np.int64)
-    fig = dict(records=len(recs), reverse=0, ins_left=0, contributions=0)
-    for r in recs:
-        g, qi, seq, rev, ins, hit_after_ins = first[r[2]] + int(r[3]) - 1, 0, r[9], int(r[1]) & 16, False, False
-        for n, k in CIG.findall(r[5]):
-            n = int(n)
-            if k == "I":
-                qi += n; ins = True
-                continue
-            lo, hi = np.searchsorted(P, [g, g + n])
-            for j in range(lo, hi):
-                cnt[j, 5 if k == "D" else CLS.get(seq[qi + P[j] - g], 4)] += 1
-                fig["contributions"] += 1
-                fig["reverse"] += 1 if rev else 0
-                hit_after_ins |= ins
-            g += n
-            if k == "M":
-                qi += n
-        fig["ins_left"] += 1 if hit_after_ins else 0
-    return cnt, site_pos, fig
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 def check_against_sam(out, name):
@@ -307,25 +246,18 @@ def test_cli_writes_the_bytes_of_the_api(g1_reference, models, golden_inputs, tm
 
 
 _OWN = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
-import numpy as np
+import ctypes, os
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
-def fails(f, code, word):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and word in str(e), (code, word, e)
-        return
-    raise SystemExit("no error: " + word)
-out = %(out)r
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=%(prof)r, seed=5)
+from scssim_amd import SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
+from gpu_child import fails, job_args
+a = job_args()
+out = a["out"]
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
 s.set_site_support(True)
 fails(s.yield_reads, SCS_EINVAL, "scs_set_site_support")
 s.set_site_support(False)
 fails(s.yield_reads, SCS_EINVAL, "scs_allocate_reads")       # the refusal is gone: what is missing now is the job itself
-g = scssim_amd.GenReads(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=2.0, seed=5)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 for seed in (5, 6):                                         # the yields' own buffers exist before the census is taken
     g.set_seed(seed); g.yield_reads(collect=False)
@@ -359,7 +291,6 @@ assert scssim_amd.live_resources() == before, (before, scssim_amd.live_resources
 g.set_seed(5); g.yield_reads(collect=False)
 assert g.site_support_kernel_time()["launches"] == 0
 fails(g.site_support, SCS_EINVAL, "scs_set_site_support")
-import os
 assert not os.path.exists(out + "_early.vcf") and not os.path.exists(out + "_flag.vcf")
 g.close(); s.close()
 assert scssim_amd.live_resources() == (0, 0, 0, 0), scssim_amd.live_resources()
@@ -372,22 +303,20 @@ def test_refusals_and_ownership(g1_reference, models, golden_inputs, tmp_path):
     read-out or file before a yield; cap = 0 returns the count; an unknown flag bit; an unwritable path is SCS_EIO and the ctx goes
     on; a second yield after scs_set_seed holds its own counters; scs_live_resources is back after set_site_support(0), and zero
     once the contexts are gone."""
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, out=str(tmp_path / "own"), prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"])],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_OWN, dict(out=str(tmp_path / "own"), prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"]), timeout=300, ok=True)
     _, res = g1_reference
     assert res["live_end"] == [0, 0, 0, 0]
 
 
 # the four per-batch side outputs of one ctx: leg "all" has them on together, then each alone after set_seed
 _SIDE = r'''
-import json, sys
-sys.path.insert(0, %(root)r)
 import numpy as np
 import scssim_amd
-out = %(out)r
-g = scssim_amd.GenReads(profile=%(prof)r, coverage=3.0, layout="PE", seed=41)
-g.simuvars(%(fa)r)                                          # no variant files: the identity lift table
+from gpu_child import emit, job_args
+a = job_args()
+out = a["out"]
+g = scssim_amd.GenReads(profile=a["prof"], coverage=3.0, layout="PE", seed=41)
+g.simuvars(a["fa"])                                          # no variant files: the identity lift table
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 res = {}
 for name in ("all", "sam", "depth", "depth_ref", "support"):
@@ -397,19 +326,19 @@ for name in ("all", "sam", "depth", "depth_ref", "support"):
     g.set_depth(100 if on("depth") else 0); g.set_depth_ref(100 if on("depth_ref") else 0); g.set_site_support(on("support"), 0)
     f1, f2 = g.yield_reads()
     open(out + "_" + name + "_1.fq", "wb").write(f1); open(out + "_" + name + "_2.fq", "wb").write(f2)
-    a = {}
+    z = {}
     if on("depth"):
-        a["hreads"], a["hbases"], _ = g.depth()
+        z["hreads"], z["hbases"], _ = g.depth()
     if on("depth_ref"):
-        a["reads"], a["bases"], a["copies"], _ = g.depth_ref()
+        z["reads"], z["bases"], z["copies"], _ = g.depth_ref()
     if on("support"):
-        a["counts"] = g.site_support()["counts"]
-    np.savez(out + "_" + name + ".npz", **a)
+        z["counts"] = g.site_support()["counts"]
+    np.savez(out + "_" + name + ".npz", **z)
     res[name] = dict(reads_written=g.stats()["reads_written"], batches=g.kernel_times()["k_reads"]["launches"], k_depth=g.kernel_times()["k_depth"]["launches"],
                      k_truth=g.kernel_times()["k_truth"]["launches"], k_depth_lift=g.depth_ref_kernel_time()["launches"], k_support=g.site_support_kernel_time()["launches"])
 g.close()
 res["live_end"] = scssim_amd.live_resources()
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
@@ -419,10 +348,7 @@ def test_all_side_outputs_in_one_yield_equal_each_alone(models, golden_inputs, t
     one with each alone.  The SAM's bytes, both haplotype depth arrays, the three reference arrays and the support counters of
     the combined call equal the single calls'; the FASTQ text is the same five times; nothing is left after close()."""
     out = str(tmp_path / "side")
-    r = subprocess.run([sys.executable, "-c", _SIDE % dict(root=ROOT, out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"])],
-                       env=seams_env(SCS_TEST_BATCH_SHIFT="8"), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    res = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    res = run_child(_SIDE, dict(out=out, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"]), env=seams_env(SCS_TEST_BATCH_SHIFT="8"), timeout=300)
     print(res)
     every, singles = np.load(out + "_all.npz"), {"depth": ("hreads", "hbases"), "depth_ref": ("reads", "bases", "copies"), "support": ("counts",)}
     n = res["all"]["batches"]

@@ -1,32 +1,28 @@
 """GPU tests of the site support table on the original reference (scs_set_site_support_ref / `scssim genreads --lift --support-ref`;
 DESIGN.md section 19).  The sites are scs_artefact_ref_sites' own; the six counters of every reference position equal the truth SAM
-of the same yield call piled up (pileup_from_sam of tests/test_gpu_support.py) at the staged positions the per-base restatement of
-tests/support_ref_cases.py names, summed by X(g).  The golden simuvars genome; the dense het layout of test_gpu_artefacts_ref.py,
+of the same yield call piled up (pileup_from_sam of tests/support_cases.py) at the staged positions the per-base restatement of
+tests/support_ref_cases.py names, summed by X(g).  The golden simuvars genome; the dense het layout of tests/lift_cases.py,
 held to what it must reach; invariance over fill chunks, slabs, LDS table sizes, batch cuts, sinks and a second call; a plain
 genome against --support of the two haplotypes; the file, the CLI, nothing else moving; refusals and ownership.  Each job runs in
 a child process under its own time limit; the checks run here.  Run with `-m gpu`."""
-import gzip
-import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, seams_env
+from conftest import seams_env
+from gpu_child import run_child, sv_ref  # noqa: F401 (a fixture)
+from gpu_readers import CLI, SV, Segs, _inflate, make_genome
+from lift_cases import write_dense_het_inputs
 from site_ref_cases import header
+from support_cases import pileup_from_sam
 from support_ref_cases import INFO3, fields, restate, strip_support
-from test_gpu_artefacts_ref import _inflate, write_dense_het_inputs
-from test_gpu_lift import Segs
-from test_gpu_support import pileup_from_sam
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-SV = os.path.join(GOLDEN, "simuvars")
 KEYS = ("ref_rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")
 
 # one ctx, one genome (built by simuvars, or a FASTA and its lift file), one allocated job, then a yield per leg: {name, ref
@@ -35,86 +31,59 @@ KEYS = ("ref_rec", "pos", "ref", "alt", "na", "ta", "nr", "tr")
 # leg), write (the table's files and the artefact table's of the same min_reads), art (min_reads of an artefact table on the
 # reference written with the feature off)}
 _CHILD = r'''
-import json, os, sys, ctypes
-sys.path.insert(0, %(root)r)
 import numpy as np
 import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], coverage=a["cov"], layout="PE", seed=a["seed"], ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, leg_env, open_job, yield_leg
+a = job_args()
+g = open_job(a, lift_file=True, segs=True)
 out = a["out"]
-if a.get("fasta"):
-    g.load_genome(a["fasta"]); g.load_lift(a["lift"])
-else:
-    g.simuvars(a["ref"], a.get("snp"), a.get("vars"))
-t = g.lift_segments()
-np.savez(out + "_segs.npz", hap_off=t.hap_off, len=t.len, ref_pos=t.ref_pos, ref_rec=t.ref_rec, kind=t.kind, ref_lens=t.ref_lens)
-g.write_lift(out + ".lift")
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 np.savez(out + "_hap.npz", **g.artefact_sites(0))
 res = {}
 for leg in a["legs"]:
     pre = out + "_" + leg["name"]
-    os.environ.update(leg.get("env", {}))
-    g.set_seed(a["seed"])
-    g.set_site_support(False); g.set_site_support_ref(False)
-    if "ref" in leg:
-        g.set_site_support_ref(True, leg["ref"])
-    if "sup" in leg:
-        g.set_site_support(True, leg["sup"])
-    g.set_depth(leg.get("w", 0)); g.set_depth_ref(leg.get("wr", 0))
-    g.set_truth_sam(pre + ".sam" if leg.get("sam") else None)
-    kind = leg.get("sink", "callback")
-    if kind == "callback":
-        f1, f2 = g.yield_reads()
-        open(pre + "_1.fq", "wb").write(f1); open(pre + "_2.fq", "wb").write(f2)
-    elif kind == "null":
-        g.yield_reads(collect=False)
-    elif kind == "files":
-        g.yield_reads_files(pre, leg.get("writers", 1), leg.get("generations", 1), bgzf=leg.get("bgzf", False))
-    else:
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]; hip.hipFree.argtypes = [ctypes.c_void_p]
-        d1, d2, cap = ctypes.c_void_p(), ctypes.c_void_p(), 64 << 20
-        assert hip.hipMalloc(ctypes.byref(d1), cap) == 0 and hip.hipMalloc(ctypes.byref(d2), cap) == 0
-        g.yield_reads_device(d1, cap, d2, cap)
-        hip.hipFree(d1); hip.hipFree(d2)
-    r = dict(reads_written=g.stats()["reads_written"], k_support=g.site_support_kernel_time(), k_reads=g.kernel_times()["k_reads"])
-    if leg.get("w"):
-        dr, db, off = g.depth()
-        np.savez(pre + "_depth.npz", reads=dr, bases=db)
-    if leg.get("wr"):
-        dr, db, dc, off = g.depth_ref()
-        np.savez(pre + "_depth_ref.npz", reads=dr, bases=db, copies=dc)
-    if "sup" in leg:
-        np.savez(pre + "_hsupport.npz", **g.site_support())
-        g.write_site_support(pre + "_hsup.vcf")
-    if "ref" in leg:
-        r["k_support_ref"], r["k_open"], r["k_gather"] = g.site_support_ref_kernel_time(), g.site_support_ref_kernel_time(0), g.site_support_ref_kernel_time(1)
-        s = g.site_support_ref(); r["unlifted"] = s.pop("unlifted")
-        np.savez(pre + "_support.npz", **s)
-        s = g.artefact_ref_sites(leg["ref"]); r["art_unlifted"] = s.pop("unlifted")
-        np.savez(pre + "_sites.npz", **s)
-        if leg.get("write"):
-            r["plain"] = g.write_site_support_ref(pre + ".vcf")
-            r["bgzf"] = g.write_site_support_ref(pre + ".vcf.gz", bgzf=True)
-            r["art"] = g.write_artefacts_ref(pre + "_art.vcf", min_reads=leg["ref"])
-    if "art" in leg:
-        r["art"] = g.write_artefacts_ref(pre + "_art.vcf", min_reads=leg["art"])
-    for k in leg.get("env", {}):
-        del os.environ[k]
+    with leg_env(leg.get("env", {})):
+        g.set_seed(a["seed"])
+        g.set_site_support(False); g.set_site_support_ref(False)
+        if "ref" in leg:
+            g.set_site_support_ref(True, leg["ref"])
+        if "sup" in leg:
+            g.set_site_support(True, leg["sup"])
+        g.set_depth(leg.get("w", 0)); g.set_depth_ref(leg.get("wr", 0))
+        g.set_truth_sam(pre + ".sam" if leg.get("sam") else None)
+        yield_leg(g, pre, leg)
+        r = dict(reads_written=g.stats()["reads_written"], k_support=g.site_support_kernel_time(), k_reads=g.kernel_times()["k_reads"])
+        if leg.get("w"):
+            dr, db, off = g.depth()
+            np.savez(pre + "_depth.npz", reads=dr, bases=db)
+        if leg.get("wr"):
+            dr, db, dc, off = g.depth_ref()
+            np.savez(pre + "_depth_ref.npz", reads=dr, bases=db, copies=dc)
+        if "sup" in leg:
+            np.savez(pre + "_hsupport.npz", **g.site_support())
+            g.write_site_support(pre + "_hsup.vcf")
+        if "ref" in leg:
+            r["k_support_ref"], r["k_open"], r["k_gather"] = g.site_support_ref_kernel_time(), g.site_support_ref_kernel_time(0), g.site_support_ref_kernel_time(1)
+            s = g.site_support_ref(); r["unlifted"] = s.pop("unlifted")
+            np.savez(pre + "_support.npz", **s)
+            s = g.artefact_ref_sites(leg["ref"]); r["art_unlifted"] = s.pop("unlifted")
+            np.savez(pre + "_sites.npz", **s)
+            if leg.get("write"):
+                r["plain"] = g.write_site_support_ref(pre + ".vcf")
+                r["bgzf"] = g.write_site_support_ref(pre + ".vcf.gz", bgzf=True)
+                r["art"] = g.write_artefacts_ref(pre + "_art.vcf", min_reads=leg["ref"])
+        if "art" in leg:
+            r["art"] = g.write_artefacts_ref(pre + "_art.vcf", min_reads=leg["art"])
     res[leg["name"]] = r
 g.set_site_support(False); g.set_site_support_ref(False); g.set_depth(0); g.set_depth_ref(0); g.set_truth_sam(None)
 g.close()
 res["live_closed"] = scssim_amd.live_resources()
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(out, legs, env=None, timeout=300, **a):
     a["out"], a["legs"] = str(out), legs
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ), capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return a["out"], json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 class Job:
@@ -153,14 +122,6 @@ def check_against_sam(out, name, job):
     assert (want[np.arange(len(x)), np.minimum(z["ref"], 4).astype(np.int64)] * (z["ref"] != z["alt"]) + want[np.arange(len(x)), z["alt"].astype(np.int64)] <= dp).all()
     fig.update(sites=len(x), positions=len(xs), staged=len(pos))
     return z, x, pos, pos_x, cnt, fig
-
-
-@pytest.fixture(scope="module")
-def sv_ref(tmp_path_factory):
-    d = tmp_path_factory.mktemp("svref")
-    ref = str(d / "ref.fa")
-    open(ref, "wb").write(gzip.open(os.path.join(SV, "ref.fa.gz")).read())
-    return ref
 
 
 def test_golden_simuvars_genome(sv_ref, models, tmp_path):
@@ -279,7 +240,7 @@ def plain_job(models, tmp_path_factory):
     everything off, --support after; both depth tracks beside them."""
     d = tmp_path_factory.mktemp("plain_sup_ref")
     ref, simu, lift = str(d / "ref.fa"), str(d / "simu.fa"), str(d / "simu.lift")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40500", "--seed", "17", "--ref-out", ref])
+    make_genome(ref, "60000,40500", 17, ref=True)
     r = subprocess.run([CLI, "simuvars", "-r", ref, "-o", simu, "--lift", lift], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     return _run(d / "job", PLAIN_LEGS, prof=models["Illumina_HiSeq2500"], fasta=simu, lift=lift, **PLAIN) + (simu, lift)
@@ -381,25 +342,18 @@ def test_nothing_else_moves(plain_job):
 
 
 _OWN = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
-import numpy as np
+import ctypes, os
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
-def fails(f, code, *words):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and all(w in str(e) for w in words), (code, words, e)
-        return
-    raise SystemExit("no error: " + " ".join(words))
-out = %(out)r
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=%(prof)r, seed=5)
+from scssim_amd import SCS_EINVAL, SCS_EIO, SCS_EOVERFLOW
+from gpu_child import fails, job_args
+a = job_args()
+out = a["out"]
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
 s.set_site_support_ref(True)
 fails(s.yield_reads, SCS_EINVAL, "scs_set_site_support_ref", "sharded")
 s.set_site_support_ref(False)
 fails(s.yield_reads, SCS_EINVAL, "scs_allocate_reads")      # the refusal is gone: what is missing now is the job itself
-g = scssim_amd.GenReads(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=2.0, seed=5)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 census = scssim_amd.live_resources()
 g.set_site_support_ref(True)
@@ -407,7 +361,7 @@ fails(lambda: g.yield_reads(collect=False), SCS_EINVAL, "scs_set_site_support_re
 assert scssim_amd.live_resources() == census                # a refused yield call leaves nothing
 g.set_site_support_ref(False)
 assert scssim_amd.live_resources() == census
-g.simuvars(%(ref)r, None, None)
+g.simuvars(a["ref"], None, None)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 for seed in (5, 6):                                         # the yields' own buffers exist before the census is taken
     g.set_seed(seed); g.yield_reads(collect=False)
@@ -450,7 +404,6 @@ assert scssim_amd.live_resources() == before, (before, scssim_amd.live_resources
 fails(lambda: g.write_site_support_ref(out + "_off.vcf"), SCS_EINVAL, "scs_set_site_support_ref")
 g.set_seed(5); g.yield_reads(collect=False)
 assert g.site_support_ref_kernel_time()["launches"] == 0 and g.site_support_ref_kernel_time(1)["launches"] == 0
-import os
 assert not os.path.exists(out + "_early.vcf") and not os.path.exists(out + "_flag.vcf") and not os.path.exists(out + "_off.vcf")
 g.close(); s.close()
 assert scssim_amd.live_resources() == (0, 0, 0, 0), scssim_amd.live_resources()
@@ -463,6 +416,4 @@ def test_refusals_and_ownership(sv_ref, models, golden_inputs, tmp_path):
     while the other table is on, naming both; no read-out or file before a yield; cap = 0 returns the count; an unknown flag bit;
     an unwritable path is SCS_EIO and the ctx goes on; a second yield holds its own counters; the timer's units are pairs;
     scs_live_resources is back after scs_set_site_support_ref(ctx, 0, ..) and zero once the contexts are gone."""
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, out=str(tmp_path / "own"), prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=sv_ref)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_OWN, dict(out=str(tmp_path / "own"), prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=sv_ref), timeout=300, ok=True)

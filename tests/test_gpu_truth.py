@@ -1,8 +1,6 @@
 """GPU tests of the truth SAM (scs_set_truth_sam / scssim genreads --truth): the FASTQ does not change, the SAM is complete and
 well-formed, and every read lies where its lineage says, base for base.  Each job runs in a child process under its own time
 limit; the checks run here.  Run with `-m gpu`."""
-import gzip
-import json
 import math
 import os
 import re
@@ -13,72 +11,37 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, seams_env
+from gpu_child import run_child
+from gpu_readers import CIG, CUT_JOB, CUT_LDS, _exact_profile, _fasta, _fastq, _oracle, _sam, cut_job_inputs, make_genome, pair_floor
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
+# one ctx, one amplified job: (lineage) the tables a read's place is checked against, (plain) a yield without the SAM, then the yield with it
 _CHILD = r'''
-import json, os, sys, ctypes
-sys.path.insert(0, %(root)r)
-import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], isize=a.get("isize", 260), ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, open_job, yield_leg
+a = job_args()
+g = open_job(a)
 out = a["out"]
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 if a.get("lineage"):
     import numpy as np
     f = g.download_frags(); s = g.download_amplicons(0); u = g.download_amplicons(1)
     np.savez(out + "_lineage.npz", fgoff=f["goff"], flen=f["len"], fstrand=f["strand"], spar=s["parent"], sspos=s["spos"], slen=s["len"],
              upar=u["parent"], uspos=u["spos"], ulen=u["len"])
 if a.get("plain"):
-    f1, f2 = g.yield_reads()
-    open(out + "_plain_1.fq", "wb").write(f1); open(out + "_plain_2.fq", "wb").write(f2)
+    yield_leg(g, out + "_plain", {})
 g.set_truth_sam(out + ".sam")
-if a["sink"] == "files":
-    g.yield_reads_files(out, 1, bgzf=a.get("bgzf", False))
-else:
-    f1, f2 = g.yield_reads()
-    open(out + "_1.fq", "wb").write(f1); open(out + "_2.fq", "wb").write(f2)
-print("truth_bytes", g.truth_bytes(), "pairs", g.stats()["pairs_written"], json.dumps(g.kernel_times()["k_truth"]))
+yield_leg(g, out, a)
+emit(dict(truth_bytes=g.truth_bytes(), pairs=g.stats()["pairs_written"], k_truth=g.kernel_times()["k_truth"]))
 '''
 
 
 def _run(tmp_path, env=None, timeout=900, **a):
     a.setdefault("out", str(tmp_path / "job"))
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ),
-                       capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return a["out"], r.stdout
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
-def _fastq(path):
-    op = gzip.open if path.endswith(".gz") else open
-    lines = op(path, "rb").read().split(b"\n")
-    return [(lines[i][1:].decode(), lines[i + 1].decode(), lines[i + 3].decode()) for i in range(0, len(lines) - 1, 4)]
-
-
-def _fasta(path):
-    recs, name, parts = {}, None, []
-    for ln in open(path, "rb").read().split(b"\n"):
-        if ln.startswith(b">"):
-            if name is not None:
-                recs[name] = b"".join(parts).upper()
-            name, parts = ln[1:].split()[0].decode(), []
-        else:
-            parts.append(ln.strip())
-    recs[name] = b"".join(parts).upper()
-    return {k: re.sub(rb"[^ACGT]", b"N", v) for k, v in recs.items()}
-
-
-def _sam(path):
-    hdr, recs = [], []
-    for ln in open(path).read().split("\n")[:-1]:
-        (hdr if ln.startswith("@") else recs).append(ln if ln.startswith("@") else ln.split("\t"))
-    return hdr, recs
-
-
-CIG = re.compile(r"(\d+)([MID])")
 COMP = bytes.maketrans(b"ACGTN", b"TGCAN")
 
 
@@ -193,10 +156,6 @@ def check_lineage(recs, pos, span, rev, rec_off, lz, paired):
         assert (rev == ~fwd_amp).all()
 
 
-def _oracle(oracle_bin, fa, prof, prefix, args, seed):
-    subprocess.check_call([oracle_bin, "genreads", "-i", fa, "-m", prof, "-o", prefix, "--rng", "counter", "--seed", str(seed), "-t", "16", "-q"] + args)
-
-
 @pytest.mark.parametrize("case,model,layout,cov", [("g1_hiseq2500_pe", "Illumina_HiSeq2500", "PE", 3.0), ("g3_hiseq2000_se", "Illumina_HiSeq2000", "SE", 2.0)])
 def test_fastq_unchanged_and_sam_complete(case, model, layout, cov, oracle_bin, models, golden_inputs, tmp_path):
     """1 + 2 + 4: with truth on the FASTQ is byte-identical to truth off and to the oracle; the SAM has a record per FASTQ record,
@@ -211,34 +170,7 @@ def test_fastq_unchanged_and_sam_complete(case, model, layout, cov, oracle_bin, 
         want = open(orc + (m + ".fq" if paired else ".fq"), "rb").read()
         assert open(out + m + ".fq", "rb").read() == want == open(out + "_plain" + m + ".fq", "rb").read()
     check_sam(out + ".sam", [out + m + ".fq" for m in mates], fa, paired, isize=260 if paired else None, lineage=out + "_lineage.npz")
-    assert int(so.split()[1]) == os.path.getsize(out + ".sam")
-
-
-def _exact_profile(src, dst, ins, dele):
-    """Substitution rows with all their mass on the row's own base (kmer XYZ -> Z), and the given indel rates."""
-    lines = open(src).read().split("\n")
-    out, i, L = [], 0, None
-    while i < len(lines):
-        ln = lines[i]
-        if ln.startswith("readLength:"):
-            L = int(ln.split(":")[1])
-        if ln in ("[Insert Rate]", "[Deletion Rate]"):
-            out += [ln, "%g" % (ins if ln == "[Insert Rate]" else dele)]
-            i += 2
-            continue
-        m = re.match(r"kmer: ([ACGTNX]{3})$", ln)
-        if m:
-            b = m.group(1)[2]
-            out.append(ln)
-            row = "\t".join("1" if c == b else "0" for c in "ACGT")
-            for r in lines[i + 1:i + 1 + 2 * L]:
-                out.append(row if b in "ACGT" else r)
-            i += 1 + 2 * L
-            continue
-        out.append(ln)
-        i += 1
-    open(dst, "w").write("\n".join(out))
-    return dst
+    assert so["truth_bytes"] == os.path.getsize(out + ".sam")
 
 
 @pytest.mark.parametrize("variant", ["plain", "replay", "rollback51"])
@@ -247,8 +179,7 @@ def test_exact_placement(variant, models, tmp_path):
     every read is the genome under its CIGAR (inserted bases aside) and NM is its indel bases.  An off-by-one anywhere shows as
     ~75 % mismatches.  replay: every read with events takes the replay path (SCS_EV_REPLAY).  rollback51: 51-base reads with
     many deletions, so that n + delta < 50 rolls reads back to no events at all."""
-    fa = str(tmp_path / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "400000,300000", "--seed", "17", "--simu-out", fa])
+    fa = make_genome(str(tmp_path / "g.fa"), "400000,300000", 17)
     src = models["Illumina_HiSeq2500"]
     if variant == "rollback51":
         src51 = str(tmp_path / "m51.profile")
@@ -273,36 +204,14 @@ def test_exact_placement(variant, models, tmp_path):
 @pytest.mark.parametrize("sink", ["files", "callback"])
 def test_many_batches_and_ns(sink, models, tmp_path):
     """5: the 12 Mb two-record genome with an N block, many small batches; the file sink with BGZF FASTQ and a callback sink."""
-    fa = str(tmp_path / "simu.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "7000000,5000000", "--seed", "31", "--n-block", "20000", "--simu-out", fa])
+    fa = make_genome(str(tmp_path / "simu.fa"), "7000000,5000000", 31, n_block=20000)
     out, _ = _run(tmp_path, env=seams_env(SCS_TEST_BATCH_SHIFT="12"), prof=models["Illumina_HiSeqXTen"], fa=fa, cov=1.0, layout="PE", seed=8,
                   sink=sink, bgzf=True, lineage=True)
     fqs = [out + m + (".fq.gz" if sink == "files" else ".fq") for m in ("_1", "_2")]
     check_sam(out + ".sam", fqs, fa, True, isize=260, lineage=out + "_lineage.npz")
 
 
-# ---- the emit pass under a cut LDS (SCS_TEST_TRUTH_LDS).  The job: test_gpu_truth_bam.py::test_frequent_indels' genome and
-# profile (insertion and deletion rates 0.01, no substitution anywhere), PE, at a coverage of 0.2: 350 kb / (2 x 125) x 0.2 = 280 pairs
-CUT_JOB = dict(cov=0.2, layout="PE", seed=7, sink="callback", ber=0.0)
-CUT_LDS = 256                                             # bytes: below any pair of the job (pair_floor)
-
-
-def cut_job_inputs(d, models):
-    fa = str(d / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "200000,150000", "--seed", "17", "--simu-out", fa])
-    return fa, _exact_profile(models["Illumina_HiSeq2500"], str(d / "x.profile"), 0.01, 0.01)
-
-
-def pair_floor(probe, rname, **kw):
-    """Bytes of the smallest pair of records a job can hold, on the CPU, through the formatter the kernels run (`probe`: one of the
-    record probes of scssim_amd).  The shortest read the profile admits has n + delta = 50 bases (fewer: the events are rolled
-    back); its smallest record has every field at its narrowest: amplicon 0, count 1, a one-digit POS and PNEXT, FLAG 99, TLEN 50,
-    the 75 deleted bases at the window's end (dropped from the CIGAR: "50M"), no mismatch.  A pair is two records, read 2's FLAG
-    (147) a digit wider."""
-    ev = [(50, 1, 75)]
-    rec = probe(seq="A" * 50, qual="I" * 50, pos0=0, n=125, events=ev, reverse=False, rname=rname, amp=0, cnt=1, paired=True, is_read2=False, mate=(49, True, ev), **kw)
-    return 2 * len(rec)
-
+# ---- the emit pass under a cut LDS (SCS_TEST_TRUTH_LDS): the job, its inputs and pair_floor are in tests/gpu_readers.py
 
 @pytest.fixture(scope="module")
 def cut_reference(models, tmp_path_factory):
@@ -310,7 +219,7 @@ def cut_reference(models, tmp_path_factory):
     d = tmp_path_factory.mktemp("cut")
     fa, prof = cut_job_inputs(d, models)
     out, so = _run(d, prof=prof, fa=fa, plain=True, **CUT_JOB)
-    pairs = int(so.split()[3])
+    pairs = so["pairs"]
     print("pairs: %d" % pairs)
     assert 200 <= pairs <= 400
     for m in ("_1.fq", "_2.fq"):
@@ -339,34 +248,22 @@ def test_sam_under_a_cut_lds(knobs, cut_reference, tmp_path):
 
 
 _ERR = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL
-kw = dict(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=kw["profile"], seed=5)
-s.set_truth_sam(%(out)r + "_s.sam")
-try:
-    s.yield_reads(); raise SystemExit("sharded: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "sharded" in str(e), e
-g = scssim_amd.GenReads(**kw)
+from scssim_amd import SCS_EINVAL
+from gpu_child import device_buffers, fails, job_args
+a = job_args()
+out = a["out"]
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
+s.set_truth_sam(out + "_s.sam")
+fails(s.yield_reads, SCS_EINVAL, "sharded")
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=2.0, seed=5)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
-g.set_truth_sam(%(out)r + ".sam")
-try:
-    g.yield_reads_files(%(out)r + "_w", 3); raise SystemExit("writers: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "writers" in str(e), e
-hip = ctypes.CDLL("libamdhip64.so")
-hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-d1, d2 = ctypes.c_void_p(), ctypes.c_void_p()
-assert hip.hipMalloc(ctypes.byref(d1), 1 << 24) == 0 and hip.hipMalloc(ctypes.byref(d2), 1 << 24) == 0
-try:
-    g.yield_reads_device(d1, 1 << 24, d2, 1 << 24); raise SystemExit("device: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "scs_yield_reads_device" in str(e), e
+g.set_truth_sam(out + ".sam")
+fails(lambda: g.yield_reads_files(out + "_w", 3), SCS_EINVAL, "writers")
+with device_buffers(1 << 24) as (d1, d2):
+    fails(lambda: g.yield_reads_device(d1, 1 << 24, d2, 1 << 24), SCS_EINVAL, "scs_yield_reads_device")
 f1, f2 = g.yield_reads()
-open(%(out)r + "_1.fq", "wb").write(f1); open(%(out)r + "_2.fq", "wb").write(f2)
+open(out + "_1.fq", "wb").write(f1); open(out + "_2.fq", "wb").write(f2)
 print("ok")
 '''
 
@@ -376,8 +273,6 @@ def test_refusals_leave_the_ctx_usable(models, golden_inputs, tmp_path):
     reads and their SAM."""
     out = str(tmp_path / "e")
     fa = golden_inputs["g1_hiseq2500_pe"]
-    r = subprocess.run([sys.executable, "-c", _ERR % dict(root=ROOT, prof=models["Illumina_HiSeq2500"], fa=fa, out=out)],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    run_child(_ERR, dict(prof=models["Illumina_HiSeq2500"], fa=fa, out=out), timeout=600, ok=True)
     assert not os.path.exists(out + "_w_1.fq") and not os.path.exists(out + "_w.p00_1.fq")
     check_sam(out + ".sam", [out + "_1.fq", out + "_2.fq"], fa, True)

@@ -2,53 +2,40 @@
 project's own truth SAM of the same job (tests/test_gpu_truth.py pins that one to the genome and the lineage): a child process
 runs the job twice on one ctx with the same seed, once with set_truth_sam and once with set_truth_bam, and the checks here decode
 the BAM with tests/bam_cases.py and compare it with the SAM record for record, column for column.  Run with `-m gpu`."""
-import json
 import os
-import re
-import subprocess
-import sys
 
 import pytest
 
-from conftest import ROOT, seams_env
-
+from conftest import seams_env
 from bam_cases import read_bam, reg2bin
-from test_gpu_truth import CUT_JOB, CUT_LDS, cut_job_inputs, pair_floor
+from gpu_child import run_child
+from gpu_readers import CUT_JOB, CUT_LDS, _exact_profile, cut_job_inputs, make_genome, pair_floor
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
 _CHILD = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
 import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, open_job, yield_leg
+a = job_args()
+g = open_job(a)
 out = a["out"]
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 res = {}
 for kind in ("sam", "bam"):
     g.set_truth_sam(out + ".sam" if kind == "sam" else None)
     g.set_truth_bam(out + ".bam" if kind == "bam" else None)
-    if a["sink"] == "files":
-        g.yield_reads_files(out + "_" + kind, 1, bgzf=True)
-    else:
-        f1, f2 = g.yield_reads()
-        open(out + "_" + kind + "_1.fq", "wb").write(f1); open(out + "_" + kind + "_2.fq", "wb").write(f2)
+    yield_leg(g, out + "_" + kind, dict(sink=a["sink"], bgzf=True))
     res[kind] = dict(truth_bytes=g.truth_bytes(), pairs=g.stats()["pairs_written"], k_truth=g.kernel_times()["k_truth"])
 g.close()
 res["live"] = list(scssim_amd.live_resources())
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(tmp_path, env=None, timeout=300, **a):
     a.setdefault("out", str(tmp_path / "job"))
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ),
-                       capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return a["out"], json.loads(r.stdout.split("RESULT ")[1])
+    return a["out"], run_child(_CHILD, a, env=env, timeout=timeout)
 
 
 def check_bam_equals_sam(bam_path, sam_path, paired, truth_bytes=None):
@@ -99,37 +86,8 @@ def test_golden_bam_equals_sam(case, model, layout, cov, models, golden_inputs, 
     assert res["live"] == [0, 0, 0, 0]
 
 
-def _exact_profile(src, dst, ins, dele):
-    """Substitution rows with all their mass on the row's own base (kmer XYZ -> Z), and the given indel rates."""
-    lines = open(src).read().split("\n")
-    out, i, L = [], 0, None
-    while i < len(lines):
-        ln = lines[i]
-        if ln.startswith("readLength:"):
-            L = int(ln.split(":")[1])
-        if ln in ("[Insert Rate]", "[Deletion Rate]"):
-            out += [ln, "%g" % (ins if ln == "[Insert Rate]" else dele)]
-            i += 2
-            continue
-        m = re.match(r"kmer: ([ACGTNX]{3})$", ln)
-        if m:
-            b = m.group(1)[2]
-            out.append(ln)
-            row = "\t".join("1" if c == b else "0" for c in "ACGT")
-            out += [row if b in "ACGT" else r for r in lines[i + 1:i + 1 + 2 * L]]
-            i += 1 + 2 * L
-            continue
-        out.append(ln)
-        i += 1
-    open(dst, "w").write("\n".join(out))
-    return dst
-
-
 def _genome(tmp_path, lengths, seed, n_block=None):
-    fa = str(tmp_path / "g.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", lengths, "--seed", str(seed), "--simu-out", fa]
-                          + (["--n-block", str(n_block)] if n_block else []))
-    return fa
+    return make_genome(str(tmp_path / "g.fa"), lengths, seed, n_block)
 
 
 @pytest.mark.parametrize("variant", ["plain", "replay", "cut_runs"])
@@ -168,21 +126,15 @@ def test_a_batch_smaller_than_one_block(models, tmp_path):
 
 # the job with the truth BAM or the truth SAM on the reference set: the yield must fail with SCS_EOVERFLOW and name the truth output
 _REFUSED = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r)
-import numpy as np
 import scssim_amd
 from scssim_amd import ScsError, SCS_EOVERFLOW
-a = json.loads(%(args)r)
+from gpu_child import emit, job_args, open_job
+a = job_args()
 out = a["out"]
+g = open_job(a, segs=a["kind"] == "ref", allocate=False)
 if a["kind"] == "bam":
-    g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a["ber"])
     g.set_truth_bam(out + ".bam")
 else:
-    g = scssim_amd.GenReads(profile=a["prof"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], ber=a["ber"])
-    g.simuvars(a["ref"], None, None, None)
-    t = g.lift_segments()
-    np.savez(out + "_segs.npz", hap_off=t.hap_off, len=t.len, ref_pos=t.ref_pos, ref_rec=t.ref_rec, kind=t.kind, ref_lens=t.ref_lens)
     g.set_truth_ref_sam(out + ".sam")
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 res = dict(reads_requested=g.stats()["reads_requested"])
@@ -192,7 +144,7 @@ except ScsError as e:
     res["code"], res["message"], res["overflow"] = e.code, str(e), SCS_EOVERFLOW
 g.close()
 res["live"] = list(scssim_amd.live_resources())
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
@@ -207,15 +159,11 @@ def test_a_pair_larger_than_the_lds_is_refused(kind, models, tmp_path):
         fa, prof = cut_job_inputs(tmp_path, models)
         a = dict(CUT_JOB, kind=kind, fa=fa, prof=prof)
     else:
-        ref = str(tmp_path / "ref.fa")
-        subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40500", "--seed", "17", "--ref-out", ref])
+        ref = make_genome(str(tmp_path / "ref.fa"), "60000,40500", 17, ref=True)
         prof = _exact_profile(models["Illumina_HiSeq2500"], str(tmp_path / "x.profile"), 0.01, 0.01)
         a = dict(CUT_JOB, kind=kind, ref=ref, prof=prof, cov=0.7)
     a["out"] = str(tmp_path / "job")
-    r = subprocess.run([sys.executable, "-c", _REFUSED % dict(root=ROOT, args=json.dumps(a))], env=seams_env(SCS_TEST_TRUTH_LDS=str(CUT_LDS)),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    res = json.loads(r.stdout.split("RESULT ")[1])
+    res = run_child(_REFUSED, a, env=seams_env(SCS_TEST_TRUTH_LDS=str(CUT_LDS)), timeout=300)
     print(res)
     assert 200 <= res["reads_requested"] // 2 <= 400
     assert res["code"] == res["overflow"] and "truth SAM / BAM" in res["message"], res
@@ -234,48 +182,30 @@ def test_a_pair_larger_than_the_lds_is_refused(kind, models, tmp_path):
 
 
 _ERR = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL
-kw = dict(profile=%(prof)r, input_fasta=%(fa)r, coverage=2.0, seed=5)
-s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=kw["profile"], seed=5)
-s.set_truth_bam(%(out)r + "_s.bam")
-try:
-    s.yield_reads(); raise SystemExit("sharded: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "sharded" in str(e) and "BAM" in str(e), e
-g = scssim_amd.GenReads(**kw)
+from scssim_amd import SCS_EINVAL
+from gpu_child import device_buffers, fails, job_args
+a = job_args()
+out = a["out"]
+s = scssim_amd.GenReads(shard_count=2, shard_rank=0, profile=a["prof"], seed=5)
+s.set_truth_bam(out + "_s.bam")
+fails(s.yield_reads, SCS_EINVAL, "sharded", "BAM")
+g = scssim_amd.GenReads(profile=a["prof"], input_fasta=a["fa"], coverage=2.0, seed=5)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
-g.set_truth_sam(%(out)r + ".sam")
-try:
-    g.set_truth_bam(%(out)r + ".bam"); raise SystemExit("BAM over SAM: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "scs_set_truth_sam" in str(e) and "scs_set_truth_bam" in str(e), e
+g.set_truth_sam(out + ".sam")
+fails(lambda: g.set_truth_bam(out + ".bam"), SCS_EINVAL, "scs_set_truth_sam", "scs_set_truth_bam")       # BAM over SAM
 g.set_truth_bam(None)                                    # clears only its own: the SAM stays on
 f1, f2 = g.yield_reads()
-open(%(out)r + "_sam_1.fq", "wb").write(f1); open(%(out)r + "_sam_2.fq", "wb").write(f2)
+open(out + "_sam_1.fq", "wb").write(f1); open(out + "_sam_2.fq", "wb").write(f2)
 g.set_truth_sam(None)
-g.set_truth_bam(%(out)r + ".bam")
-try:
-    g.set_truth_sam(%(out)r + "_2.sam"); raise SystemExit("SAM over BAM: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "scs_set_truth_sam" in str(e) and "scs_set_truth_bam" in str(e), e
+g.set_truth_bam(out + ".bam")
+fails(lambda: g.set_truth_sam(out + "_2.sam"), SCS_EINVAL, "scs_set_truth_sam", "scs_set_truth_bam")     # SAM over BAM
 g.set_truth_sam(None)                                    # ... and the BAM stays on
-try:
-    g.yield_reads_files(%(out)r + "_w", 3); raise SystemExit("writers: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "writers" in str(e) and "BAM" in str(e), e
-hip = ctypes.CDLL("libamdhip64.so")
-hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-d1, d2 = ctypes.c_void_p(), ctypes.c_void_p()
-assert hip.hipMalloc(ctypes.byref(d1), 1 << 24) == 0 and hip.hipMalloc(ctypes.byref(d2), 1 << 24) == 0
-try:
-    g.yield_reads_device(d1, 1 << 24, d2, 1 << 24); raise SystemExit("device: no error")
-except ScsError as e:
-    assert e.code == SCS_EINVAL and "scs_yield_reads_device" in str(e) and "BAM" in str(e), e
+fails(lambda: g.yield_reads_files(out + "_w", 3), SCS_EINVAL, "writers", "BAM")
+with device_buffers(1 << 24) as (d1, d2):
+    fails(lambda: g.yield_reads_device(d1, 1 << 24, d2, 1 << 24), SCS_EINVAL, "scs_yield_reads_device", "BAM")
 f1, f2 = g.yield_reads()
-open(%(out)r + "_bam_1.fq", "wb").write(f1); open(%(out)r + "_bam_2.fq", "wb").write(f2)
+open(out + "_bam_1.fq", "wb").write(f1); open(out + "_bam_2.fq", "wb").write(f2)
 print("ok", g.truth_bytes())
 '''
 
@@ -284,10 +214,8 @@ def test_refusals_leave_the_ctx_usable(models, golden_inputs, tmp_path):
     """5: a sharded ctx, writers = 3 and scs_yield_reads_device with the BAM set fail with SCS_EINVAL and say BAM; one truth output
     per ctx, either way round; the same ctx then writes a BAM that equals its SAM."""
     out = str(tmp_path / "e")
-    r = subprocess.run([sys.executable, "-c", _ERR % dict(root=ROOT, prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], out=out)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    so = run_child(_ERR, dict(prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], out=out), timeout=300, ok=True)
     assert not os.path.exists(out + "_w_1.fq") and not os.path.exists(out + "_2.sam") and not os.path.exists(out + "_s.bam")
-    check_bam_equals_sam(out + ".bam", out + ".sam", True, int(r.stdout.split()[-1]))
+    check_bam_equals_sam(out + ".bam", out + ".sam", True, int(so.split()[-1]))
     _same_fastq(out, "callback")
 

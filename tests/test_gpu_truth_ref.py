@@ -5,42 +5,31 @@ column check of every record through scs_lift_positions; the dense layout, where
 the file does not depend on sinks, batch cuts or the emit pass' LDS run, and the FASTQ does not know of it; the two-step flow
 through the CLI; refusals and ownership.  Each job runs in a child process under its own time limit.  Run with `-m gpu`."""
 import gzip
-import json
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT, seams_env
-from test_gpu_truth import CIG, _exact_profile, _sam
-from test_gpu_lift import DENSE_COV, Segs, expected_reach, lift_from_sam, write_dense_inputs
+from conftest import seams_env
+from gpu_child import run_child, sv_ref  # noqa: F401 (a fixture)
+from gpu_readers import CIG, CLI, SV, Segs, _exact_profile, _sam, make_genome
+from lift_cases import DENSE_COV, expected_reach, lift_from_sam, write_dense_inputs
 from truth_ref_cases import lift_sam_records, table_from_lift_file
 
 import scssim_amd
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "scssim_amd", "bin", "scssim")
-SV = os.path.join(GOLDEN, "simuvars")
-
 # one ctx, one genome built by simuvars, one amplified job, then a yield per leg with the same seed:
 # {name, truth ("sam" / "ref" / none), sink (callback / null / files), bgzf, wr (depth by reference bin), support}; then the column check
 _CHILD = r'''
-import json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests"))
-import numpy as np
 import scssim_amd
-a = json.loads(%(args)r)
-g = scssim_amd.GenReads(profile=a["prof"], coverage=a["cov"], layout=a["layout"], seed=a["seed"], isize=a.get("isize", 260), ber=a.get("ber", 3.4e-4))
+from gpu_child import emit, job_args, open_job, yield_leg
+a = job_args()
+g = open_job(a, lift_file=True, segs=True)
 out = a["out"]
-g.simuvars(a["ref"], a.get("snp"), a.get("vars"), None)
-g.write_lift(out + ".lift")
-t = g.lift_segments()
-np.savez(out + "_segs.npz", hap_off=t.hap_off, len=t.len, ref_pos=t.ref_pos, ref_rec=t.ref_rec, kind=t.kind, ref_lens=t.ref_lens)
-g.create_frags(); g.amplify(); g.allocate_reads(0)
 res = {}
 for leg in a["legs"]:
     pre = out + "_" + leg["name"]
@@ -51,33 +40,23 @@ for leg in a["legs"]:
         g.set_truth_sam(pre + ".sam")
     if leg.get("truth") == "ref":
         g.set_truth_ref_sam(pre + ".sam")
-    kind = leg.get("sink", "callback")
-    if kind == "callback":
-        f1, f2 = g.yield_reads()
-        open(pre + "_1.fq", "wb").write(f1); open(pre + "_2.fq", "wb").write(f2)
-    elif kind == "null":
-        g.yield_reads(collect=False)
-    else:
-        g.yield_reads_files(pre, 1, 1, bgzf=leg.get("bgzf", False))
+    yield_leg(g, pre, leg)
     res[leg["name"]] = dict(reads_written=g.stats()["reads_written"], truth_bytes=g.truth_bytes(), k_truth=g.kernel_times()["k_truth"], k_reads=g.kernel_times()["k_reads"])
 if a.get("column_check"):
     from truth_ref_cases import column_check, table_from_lift_file
-    from test_gpu_truth import _sam
+    from gpu_readers import _sam
     hap, ref = a["column_check"]
     res["columns"] = column_check(table_from_lift_file(out + ".lift"), _sam(out + "_" + hap + ".sam")[1], _sam(out + "_" + ref + ".sam")[1], g.lift_positions)
 g.close()
 res["live_end"] = scssim_amd.live_resources()
-print("RESULT " + json.dumps(res))
+emit(res)
 '''
 
 
 def _run(tmp_path, legs, env=None, timeout=300, **a):
     a.setdefault("out", str(tmp_path / "job"))
     a["legs"] = legs
-    r = subprocess.run([sys.executable, "-c", _CHILD % dict(root=ROOT, args=json.dumps(a))], env=env or dict(os.environ),
-                       capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    res = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+    res = run_child(_CHILD, a, env=env, timeout=timeout)
     assert res["live_end"] == [0, 0, 0, 0]
     return a["out"], res
 
@@ -108,14 +87,6 @@ def check_lifted(out, res, paired, hap="hap", ref="ref"):
     for m in ("_1.fq", "_2.fq"):
         assert open(out + "_" + hap + m, "rb").read() == open(out + "_" + ref + m, "rb").read()
     return recs
-
-
-@pytest.fixture(scope="module")
-def sv_ref(tmp_path_factory):
-    d = tmp_path_factory.mktemp("svref")
-    ref = str(d / "ref.fa")
-    open(ref, "wb").write(gzip.open(os.path.join(SV, "ref.fa.gz")).read())
-    return ref
 
 
 def test_golden_simuvars_genome(sv_ref, models, tmp_path):
@@ -183,8 +154,7 @@ def test_dense_layout(model, layout, L, dense, models, tmp_path):
 def test_plain_genome(models, tmp_path):
     """4: simuvars without variants, one R segment per staged record: every record is the haplotype SAM's line with RNAME mapped to
     the reference's name, NM / MD replaced by YH / YP / YB:i:1 and an I at either end turned into S."""
-    ref = str(tmp_path / "ref.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40500", "--seed", "17", "--ref-out", ref])
+    ref = make_genome(str(tmp_path / "ref.fa"), "60000,40500", 17, ref=True)
     out, res = _run(tmp_path, PAIR, prof=models["Illumina_HiSeq2500"], ref=ref, cov=3.0, layout="PE", seed=3)
     t = table_from_lift_file(out + ".lift")
     assert len(t) == 4 and t.ref_lens == [60000, 40500]
@@ -258,31 +228,25 @@ def test_two_step_flow_through_the_cli(sv_ref, models, tmp_path):
 
 
 _OWN = r'''
-import sys, ctypes
-sys.path.insert(0, %(root)r)
+import os
 import scssim_amd
-from scssim_amd import ScsError, SCS_EINVAL
-out = %(out)r
-def fails(f, code, *words):
-    try:
-        f()
-    except ScsError as e:
-        assert e.code == code and all(w in str(e) for w in words), (str(e), words)
-    else:
-        raise SystemExit("no error: " + repr(words))
-kw = dict(profile=%(prof)r, coverage=2.0, seed=5)
+from scssim_amd import SCS_EINVAL
+from gpu_child import device_buffers, fails, job_args
+a = job_args()
+out = a["out"]
+kw = dict(profile=a["prof"], coverage=2.0, seed=5)
 s = scssim_amd.GenReads(shard_count=2, shard_rank=0, **kw)
 s.set_truth_ref_sam(out + "_s.sam")
 fails(s.yield_reads, SCS_EINVAL, "sharded", "scs_set_truth_ref_sam")
 # a genome without a lift table
 g = scssim_amd.GenReads(**kw)
-g.load_genome(%(fa)r)
+g.load_genome(a["fa"])
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 g.set_truth_ref_sam(out + "_nolift.sam")
 fails(g.yield_reads, SCS_EINVAL, "scs_set_truth_ref_sam", "scs_load_lift", "scs_simuvars")
 g.set_truth_ref_sam(None)
 # a genome with its table
-g.simuvars(%(ref)r, None, None)
+g.simuvars(a["ref"], None, None)
 g.create_frags(); g.amplify(); g.allocate_reads(0)
 for seed in (5, 6):                                         # the yields' own buffers exist before the census is taken
     g.set_seed(seed); g.yield_reads()
@@ -301,12 +265,8 @@ fails(lambda: g.set_truth_sam(out + "_h.sam"), SCS_EINVAL, "scs_set_truth_ref_sa
 fails(lambda: g.set_truth_bam(out + "_b.bam"), SCS_EINVAL, "scs_set_truth_ref_sam", "scs_set_truth_bam")
 g.set_truth_sam(None); g.set_truth_bam(None)                # ... and the reference SAM stays on
 fails(lambda: g.yield_reads_files(out + "_w", 3), SCS_EINVAL, "writers", "scs_set_truth_ref_sam")
-hip = ctypes.CDLL("libamdhip64.so")
-hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]; hip.hipFree.argtypes = [ctypes.c_void_p]
-d1, d2 = ctypes.c_void_p(), ctypes.c_void_p()
-assert hip.hipMalloc(ctypes.byref(d1), 1 << 24) == 0 and hip.hipMalloc(ctypes.byref(d2), 1 << 24) == 0
-fails(lambda: g.yield_reads_device(d1, 1 << 24, d2, 1 << 24), SCS_EINVAL, "scs_yield_reads_device", "scs_set_truth_ref_sam")
-hip.hipFree(d1); hip.hipFree(d2)
+with device_buffers(1 << 24) as (d1, d2):
+    fails(lambda: g.yield_reads_device(d1, 1 << 24, d2, 1 << 24), SCS_EINVAL, "scs_yield_reads_device", "scs_set_truth_ref_sam")
 g.yield_reads()
 during = scssim_amd.live_resources()
 n = g.truth_bytes()
@@ -316,7 +276,6 @@ after = scssim_amd.live_resources()
 assert during[0] > before[0] and after == before, (before, during, after)
 g.set_seed(5); g.yield_reads()
 assert g.kernel_times()["k_truth"]["launches"] == 0
-import os
 assert not any(os.path.exists(out + x) for x in ("_s.sam", "_nolift.sam", "_h.sam", "_b.bam", "_w_1.fq"))
 g.close(); s.close()
 assert scssim_amd.live_resources() == (0, 0, 0, 0), scssim_amd.live_resources()
@@ -328,8 +287,5 @@ def test_refusals_and_ownership(models, golden_inputs, tmp_path):
     """7: a sharded ctx, a ctx without a lift table, writers = 3 and scs_yield_reads_device fail the yield call with SCS_EINVAL by the
     setter's name; one truth output per ctx, every way round, NULL clearing only its own; scs_live_resources is back after the
     output is switched off, and zero once the contexts are gone."""
-    ref = str(tmp_path / "ref.fa")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", "60000,40500", "--seed", "17", "--ref-out", ref])
-    r = subprocess.run([sys.executable, "-c", _OWN % dict(root=ROOT, out=str(tmp_path / "own"), prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=ref)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    ref = make_genome(str(tmp_path / "ref.fa"), "60000,40500", 17, ref=True)
+    run_child(_OWN, dict(out=str(tmp_path / "own"), prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=ref), timeout=300, ok=True)

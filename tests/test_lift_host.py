@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from lift_cases import copies_from_table, ref_layout
 from test_depth_host import EVENTS, pos_cigar
 
 import scssim_amd
@@ -97,24 +98,6 @@ def test_no_structural_variants_give_one_segment_per_record(case, sv):
     assert len(t) == 6 and (t.kind == 0).all() and (t.ref_pos == 0).all()
     assert t.ref_rec.tolist() == [0, 0, 1, 1, 2, 2] and t.len.tolist() == [400000, 400000, 150000, 150000, 60000, 60000] == t.hap_lens.tolist()
     assert (len(subst) > 0) == (case == "snp_only")
-
-
-def ref_layout(ref_lens, w):
-    """(bin_off, n_bins) of the reference records' bins."""
-    off = np.concatenate([[0], np.cumsum([-(-int(ln) // w) for ln in ref_lens])]).astype(np.int64)
-    return off, int(off[-1])
-
-
-def copies_from_table(t, ref_lens, w):
-    """copies[b] of the contract in numpy, base by base: n_bins + 1 entries, the last one the inserted bases."""
-    off, nb = ref_layout(ref_lens, w)
-    r = np.asarray(t.kind) == 0
-    ln, rp, rr = np.asarray(t.len, np.int64)[r], np.asarray(t.ref_pos, np.int64)[r], np.asarray(t.ref_rec, np.int64)[r]
-    within = np.arange(ln.sum()) - np.repeat(np.cumsum(ln) - ln, ln)
-    copies = np.bincount(np.repeat(off[rr], ln) + (np.repeat(rp, ln) + within) // w, minlength=nb + 1).astype(np.uint64)
-    assert copies[nb] == 0
-    copies[nb] = np.asarray(t.len, np.uint64)[~r].sum()
-    return copies
 
 
 @pytest.mark.parametrize("w", [1000, 37])

@@ -5,33 +5,22 @@ seconds of the yield call and the library's HIP-event times of k_reads and k_dep
 depth legs in a child process whose kernel has no LDS table (SCS_TEST_DEPTH_SLOTS=0 in the seams build: every add is a global
 atomic) -- the A/B of the aggregation; `--slots 512` is the product's table through the same build."""
 import argparse
-import json
 import os
-import subprocess
 import sys
-import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cost_job as cj  # noqa: E402
 
 
 def job(a, td):
-    import gzip
-    import scssim_amd
-    fa, prof = os.path.join(td, "chr20.fa"), os.path.join(td, "m.profile")
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_genome.py"), "--lengths", str(a.bases), "--seed", "20", "--n-block", "60000", "--simu-out", fa])
-    src = os.path.join(td, "x.profile")
-    open(src, "wb").write(gzip.open(os.path.join(ROOT, "tests", "golden", "models", "Illumina_HiSeqXTen.profile.gz")).read())
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_profile.py"), src, prof, "--read-length", "150"])
-    g = scssim_amd.GenReads(profile=prof, input_fasta=fa, coverage=a.coverage, seed=220)
-    g.create_frags(); g.amplify(); g.allocate_reads(0)
-    g.yield_reads_files(os.path.join(td, "reads_warm"), a.writers)      # warm-up: the buffers, the pinned slots, the page cache
-    for leg in [l for _ in range(a.repeats) for l in a.legs.split(",")]:
-        out = os.path.join(td, "reads_" + leg)
+    g = cj.open_ctx(a, td)
+    cj.allocate(g)
+    cj.warm_up(g, td, a.writers)
+    for leg in cj.legs(a, td):
         g.set_depth(a.bin if leg == "on" else 0)
         t = time.time()
-        g.yield_reads_files(out, a.writers)
+        g.yield_reads_files(os.path.join(td, "reads_" + leg), a.writers)
         wall = time.time() - t
         st, kt = g.stats(), g.kernel_times()
         rec = dict(leg=leg, slots=a.slots, bin=a.bin if leg == "on" else 0, writers=a.writers, wall_s=round(wall, 3), pairs=st["pairs_written"],
@@ -40,28 +29,15 @@ def job(a, td):
             r, b, _ = g.depth()
             rec.update(bins=int(r.size), reads_sum=int(r.sum()), bases_sum=int(b.sum()), reads_max=int(r.max()))
             assert rec["reads_sum"] == st["reads_written"]
-        print(json.dumps(rec), flush=True)
-        for f in os.listdir(td):
-            if f.startswith("reads_"):
-                os.unlink(os.path.join(td, f))
+        cj.emit(rec)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="off,on", help="comma list of off, on")
-    ap.add_argument("--repeats", type=int, default=2, help="runs of every leg after one unrecorded warm-up yield")
-    ap.add_argument("--slots", type=int, default=None, help="entries of the kernel's LDS table (the seams build; 0: none).  Default: the product build")
     ap.add_argument("--bin", type=int, default=1000)
-    ap.add_argument("--writers", type=int, default=1)
-    ap.add_argument("--out-dir", default="/dev/shm" if os.path.isdir("/dev/shm") else None)
-    ap.add_argument("--bases", type=int, default=63025520)
-    ap.add_argument("--coverage", type=float, default=30.0)
-    a = ap.parse_args()
-    if a.slots is not None and os.environ.get("SCS_TEST_DEPTH_SLOTS") != str(a.slots):   # the seam is read once per process: a fresh child with it set
-        env = dict(os.environ, SCS_TEST_DEPTH_SLOTS=str(a.slots), SCSSIM_HIP_LIB=os.path.join(ROOT, "scssim_amd", "libscssim_hip_seams.so"))
-        sys.exit(subprocess.call([sys.executable] + sys.argv, env=env))
-    with tempfile.TemporaryDirectory(dir=a.out_dir) as td:
-        job(a, td)
+    cj.add_common(ap, repeats=2, slots="the kernel", writers=True)
+    cj.run(ap.parse_args(), job, seam="SCS_TEST_DEPTH_SLOTS")
 
 
 if __name__ == "__main__":
