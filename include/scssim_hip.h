@@ -303,6 +303,58 @@ int         scs_write_depth(scs_ctx* ctx, const char* path);
 int         scs_depth_layout_probe(const uint64_t* rec_lens, int n_records, uint32_t bin_width, uint64_t* bin_off, uint64_t* n_bins);
 int         scs_depth_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, uint32_t bin_width,
                                  uint64_t* reads_bin, uint64_t* bins, uint32_t* bases, int cap, int* n_out);
+/* ---- coverage profile: per-base depth of the job, its histogram per record and a Lorenz summary, made on the GPU ---------
+ * scs_set_coverage(ctx, max_depth): the following yield calls also keep depth[g] for every base g of the staged genome: the
+ * (read, base) pairs an M operation of the truth CIGAR aligns to g (0: off, the default -- no buffer exists, no coverage code
+ * runs; max_depth D in 1 .. 65535).  The rules are those of the depth track's `bases`: D and I count nothing, leading and trailing
+ * deletions are dropped, reads without a FASTQ record count nothing, both mates of a pair count.  So the depths of a bin of
+ * scs_set_depth add up to its `bases`, those of the genome to the sum of the M lengths.  Per staged record r, hist[r][k], k = 0 ..
+ * D, counts its non-N bases of depth k, the last bucket those of depth >= D; N bases are in no bucket.  n_bases[r] = its N bases,
+ * sum[r] / sum_n[r] = the exact sum of the depths over its non-N / its N bases (so the top bucket's mass is
+ * sum - sum_{k < D} k hist[k]).  One more row, the genome, is the sum of the records' rows.  Sums of integers: nothing depends on
+ * batch cuts, the sink, its writers or whether the text leaves the GPU.  The arrays are zeroed on the ctx stream at the start of
+ * every yield call and valid once it has returned; scs_set_coverage(ctx, 0) (or another max_depth) releases them.  Device memory:
+ * 4 bytes per staged base, rounded up to 16 KB; where it cannot be had the yield call fails as any allocation does, its message
+ * stating the bytes.  Applies to every yield entry point and sink, beside either truth output, both depth tracks and the site
+ * support.  A sharded ctx (shard_count > 1) fails the yield call with SCS_EINVAL naming this setter, before any GPU work.  A
+ * read outside its record, a read with more than 32 indel events, a negative running depth or one that is not 0 behind the
+ * last base fail the call (SCS_EOVERFLOW), never give a wrong count.
+ * scs_coverage_shape: the staged records and max_depth (SCS_EINVAL: off, or no genome staged).
+ * scs_download_coverage: records + 1 rows, the genome's last; hist row-major, max_depth + 1 values per row; any pointer may be
+ * NULL; SCS_EINVAL before a yield call with coverage on has finished, SCS_EOVERFLOW when cap_rows < records + 1; synchronises the
+ * ctx stream itself.
+ * scs_coverage_range: the depths of [start, end) of staged record `record`, copied from the device array (SCS_EINVAL: not inside
+ * the record, or no finished call).
+ * scs_write_coverage: text written by the host.  "#coverage\tmax_depth=D\t..." states that the last bucket counts depth >= D;
+ * "#summary\trecord\tbases\tn_bases\taligned\tmean\tbreadth1\tbreadth5\tbreadth10\tbreadth20\tgini" heads one "#s\t..." line per
+ * record and one for `genome`: bases = all its bases, aligned = sum + sum_n, mean and the breadths (fractions at depth >= 1, 5,
+ * 10, 20; a threshold above D counts the top bucket) over the non-N bases; then "#record\tdepth\tcount\tsize\tfraction" and
+ * `bedtools genomecov`'s five columns for every bucket with count > 0 (size = the record's non-N bases), the genome's rows last.
+ * gini is computed from the histogram with the top bucket at its mean depth: exact when no base reaches D, a lower bound
+ * otherwise; 0 when all depths are 0 or the record has no non-N base.
+ * scs_coverage_kernel_time: which = 0 the per-batch pass (one event pair per batch, units = pairs), 1 the end-of-job pass (one
+ * pair, units = staged bases) of the last yield call; not part of scs_kernel_time's table. */
+int         scs_set_coverage(scs_ctx* ctx, uint32_t max_depth);
+int         scs_coverage_shape(const scs_ctx* ctx, uint32_t* records, uint32_t* max_depth);
+int         scs_download_coverage(scs_ctx* ctx, uint64_t* hist, uint64_t* n_bases, uint64_t* sum, uint64_t* sum_n, uint64_t cap_rows);
+int         scs_coverage_range(scs_ctx* ctx, uint32_t record, uint64_t start, uint64_t end, uint32_t* out);
+int         scs_write_coverage(scs_ctx* ctx, const char* path);
+int         scs_coverage_kernel_time(const scs_ctx* ctx, int which, uint64_t* launches, double* ms, uint64_t* units);
+/* Test seams of the coverage profile.  scs_coverage_read_probe (host only): one read through the function the per-batch kernel
+ * runs; arguments as scs_depth_read_probe; [starts[i], ends[i]), i < *n_out: the intervals of record coordinates it marks,
+ * ascending (SCS_EINVAL: not a valid alignment inside the record, or more than 32 events; SCS_EOVERFLOW: cap is too small, *n_out
+ * is set).  scs_coverage_stats_probe (host only): one histogram row of max_depth + 1 buckets and its sum through the function
+ * scs_write_coverage runs; out = mean, the four breadths, gini.  scs_coverage_tile: the end-of-job pass' tile and the chunk of
+ * its tile-offset scan.  scs_coverage_finish_probe (needs the GPU): the end-of-job kernels alone over diff[n_bases + 1],
+ * codes[n_bases] (0 .. 3, 4 = N) and records of rec_lens (adding up to n_bases); lds_buckets: buckets of a workgroup's LDS
+ * histogram (< 0: the product's; 0: none); depth[n_bases], hist[n_records][max_depth + 1], n_n / sum / sum_n[n_records], any of
+ * them NULL.  Differences that are not those of intervals give the flag's error (SCS_EOVERFLOW), and the ctx stays usable. */
+int         scs_coverage_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len,
+                                    uint64_t* starts, uint64_t* ends, int cap, int* n_out);
+int         scs_coverage_stats_probe(const uint64_t* hist, uint32_t max_depth, uint64_t sum, double out[6]);
+void        scs_coverage_tile(uint32_t* tile, uint32_t* chunk);
+int         scs_coverage_finish_probe(scs_ctx* ctx, const int32_t* diff, const uint8_t* codes, uint64_t n_bases, const uint64_t* rec_lens, uint32_t n_records,
+                                      uint32_t max_depth, int lds_buckets, uint32_t* depth, uint64_t* hist, uint64_t* n_n, uint64_t* sum, uint64_t* sum_n);
 /* ---- lift table and depth by reference bin: the job in the coordinates of the original reference ---------------------------
  * Every other truth product lives in the coordinates of the staged haplotype records.  The lift table maps them to the reference
  * `simuvars` built them from: segments that ascend and tile the staged genome, none straddling two staged records, each `len`

@@ -404,6 +404,66 @@ def depth_read_probe(pos0, n, events=(), reverse=False, rec_len=1 << 40, bin_wid
     return first.value, [(bins[i], bases[i]) for i in range(k.value)]
 
 
+def coverage_read_probe(pos0, n, events=(), reverse=False, rec_len=1 << 40):
+    """Host-only: the intervals [(start, end), ...] of record coordinates one read marks in the coverage profile, ascending, through
+    the function the per-batch kernel runs.  Arguments as for depth_read_probe."""
+    L = load_library()
+    L.scs_coverage_read_probe.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    ev = (C.c_int32 * max(1, 3 * len(events)))(*[int(v) for e in events for v in e])
+    k = C.c_int()
+    args = (int(n), int(pos0), int(bool(reverse)), ev, len(events), int(rec_len))
+    rc = L.scs_coverage_read_probe(*args, None, None, 0, C.byref(k))
+    if rc not in (SCS_OK, SCS_EOVERFLOW):
+        raise ScsError(rc, "scs_coverage_read_probe: not a valid alignment inside the record")
+    a, b = (C.c_uint64 * max(1, k.value))(), (C.c_uint64 * max(1, k.value))()
+    rc = L.scs_coverage_read_probe(*args, a, b, k.value, C.byref(k))
+    if rc:
+        raise ScsError(rc, "scs_coverage_read_probe")
+    return [(a[i], b[i]) for i in range(k.value)]
+
+
+def coverage_stats_probe(hist, total):
+    """Host-only: dict(mean=, breadth=(at 1, 5, 10, 20), gini=) of one histogram row (max_depth + 1 buckets, the last one depth >=
+    max_depth) whose depths add up to `total`, through the function write_coverage runs."""
+    import numpy as np
+    L = load_library()
+    L.scs_coverage_stats_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    h = np.ascontiguousarray(hist, np.uint64)
+    out = np.zeros(6, np.float64)
+    rc = L.scs_coverage_stats_probe(h.ctypes.data, h.size - 1, int(total), out.ctypes.data)
+    if rc:
+        raise ScsError(rc, "scs_coverage_stats_probe: a row has 2 .. 65536 buckets")
+    return dict(mean=float(out[0]), breadth=tuple(float(v) for v in out[1:5]), gini=float(out[5]))
+
+
+def coverage_tile():
+    """(tile, chunk): entries of the difference array per workgroup of the coverage profile's end-of-job pass, and tile sums per
+    step of its tile-offset scan."""
+    L = load_library()
+    L.scs_coverage_tile.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.scs_coverage_tile.restype = None
+    t, c = C.c_uint32(), C.c_uint32()
+    L.scs_coverage_tile(C.byref(t), C.byref(c))
+    return t.value, c.value
+
+
+def coverage_finish_probe(ctx, diff, codes, rec_lens, max_depth, lds_buckets=-1):
+    """Needs the GPU: the end-of-job kernels of the coverage profile alone, on the GenReads `ctx`.  diff: int32[G + 1], codes:
+    uint8[G] (0 .. 3, 4 = N), rec_lens adding up to G; lds_buckets: buckets of a workgroup's LDS histogram (-1: the product's).
+    Returns dict(depth=uint32[G], hist=uint64[records][max_depth + 1], n_bases=, sum=, sum_n=); inconsistent differences raise
+    ScsError (SCS_EOVERFLOW) and leave the ctx usable."""
+    import numpy as np
+    d, cd, ln = np.ascontiguousarray(diff, np.int32), np.ascontiguousarray(codes, np.uint8), np.ascontiguousarray(rec_lens, np.uint64)
+    G, nr, D = cd.size, ln.size, int(max_depth)
+    if d.size != G + 1:
+        raise ValueError("diff has G + 1 entries")
+    out = dict(depth=np.zeros(G, np.uint32), hist=np.zeros((nr, D + 1), np.uint64), n_bases=np.zeros(nr, np.uint64), sum=np.zeros(nr, np.uint64), sum_n=np.zeros(nr, np.uint64))
+    fn = ctx._L.scs_coverage_finish_probe
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int] + [C.c_void_p] * 5
+    ctx._ck(fn(ctx._ctx, d.ctypes.data, cd.ctypes.data, G, ln.ctypes.data, nr, D, int(lds_buckets), *[out[k].ctypes.data for k in ("depth", "hist", "n_bases", "sum", "sum_n")]))
+    return out
+
+
 class LiftTable:
     """A lift table as numpy arrays: per segment hap_off (global staged index), len, ref_pos, ref_rec, kind (0: R, 1: I); the
     reference records' and the staged records' names and lengths."""
@@ -1021,6 +1081,53 @@ class GenReads:
         """The depth track of the last yield call as tab-separated text: #record, start, end (BED coordinates), reads, bases."""
         self._L.scs_write_depth.argtypes = [C.c_void_p, C.c_char_p]
         self._ck(self._L.scs_write_depth(self._ctx, os.fsencode(path)))
+
+    def set_coverage(self, max_depth):
+        """Coverage profile: the following yield calls also keep the per-base depth of the staged genome (the M operations of the
+        truth CIGAR, as the depth track's `bases`), its histogram per record with buckets 0 .. max_depth (the last one depth >=
+        max_depth; N bases in none) and the exact sums.  max_depth in 1 .. 65535; 0 turns it off and releases the arrays."""
+        self._L.scs_set_coverage.argtypes = [C.c_void_p, C.c_uint32]
+        self._ck(self._L.scs_set_coverage(self._ctx, int(max_depth)))
+
+    def coverage_shape(self):
+        """(staged records, max_depth) of the coverage profile."""
+        self._L.scs_coverage_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        n, d = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.scs_coverage_shape(self._ctx, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    def coverage(self):
+        """The tables of the last yield call as numpy uint64 arrays: dict(hist=[records + 1][max_depth + 1], n_bases=, sum=, sum_n=
+        [records + 1]); the last row is the genome."""
+        np = self._np
+        nr, D = self.coverage_shape()
+        a = dict(hist=np.zeros((nr + 1, D + 1), np.uint64), n_bases=np.zeros(nr + 1, np.uint64), sum=np.zeros(nr + 1, np.uint64), sum_n=np.zeros(nr + 1, np.uint64))
+        self._L.scs_download_coverage.argtypes = [C.c_void_p] * 5 + [C.c_uint64]
+        self._ck(self._L.scs_download_coverage(self._ctx, *[a[k].ctypes.data for k in ("hist", "n_bases", "sum", "sum_n")], nr + 1))
+        return a
+
+    def coverage_range(self, record, start, end):
+        """The per-base depth of [start, end) of staged record `record` after the last yield call, as numpy uint32."""
+        np = self._np
+        out = np.zeros(max(0, int(end) - int(start)), np.uint32)
+        self._L.scs_coverage_range.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+        self._ck(self._L.scs_coverage_range(self._ctx, int(record), int(start), int(end), out.ctypes.data))
+        return out
+
+    def write_coverage(self, path):
+        """The coverage profile of the last yield call as text: summary lines per record and for the genome (bases, N bases, aligned
+        bases, mean depth, breadth at 1 / 5 / 10 / 20, Gini), then `bedtools genomecov`'s five columns."""
+        self._L.scs_write_coverage.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_write_coverage(self._ctx, os.fsencode(path)))
+
+    def coverage_kernel_time(self, which=0):
+        """Event pairs, milliseconds and units of the last yield call's coverage passes: which=0 the per-batch marks (units: pairs),
+        1 the end-of-job pass (units: staged bases)."""
+        fn = self._L.scs_coverage_kernel_time
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(fn(self._ctx, int(which), C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def amplicon_places(self):
         """The amplified pool after allocate_reads, one entry per full amplicon in list order (the index the read names print): dict

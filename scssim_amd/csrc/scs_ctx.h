@@ -12,6 +12,7 @@
 #include "scs_bgzf.h"
 #include "scs_truth.h"
 #include "scs_depth.h"
+#include "scs_coverage.h"
 #include "scs_lift.h"
 #include "scs_outfile.h"
 
@@ -200,6 +201,11 @@ struct KernelTimer {         // HIP events on the ctx stream around the launches
 // counters of the last yield call (planes of `bins` entries, zeroed on the ctx stream at the start of every call; valid: a call with
 // the track on has finished) and the kernel's tables
 struct DepthTrack { uint32_t width = 0; uint64_t bins = 0; bool valid = false; DevBuf cnt, tab; };
+// The coverage profile of a ctx (scs_set_coverage; scs_coverage.cpp): max_depth (0: off -- no buffer of it exists, no code of it
+// runs); the difference array of the running yield call, the per-base depths once it has finished (bases + 1 int32, padded to
+// whole tiles, zeroed on the ctx stream at the start of every call; valid: a call with it on has finished); the tables of the
+// last call -- hist[n_rec][max_depth + 1], n_bases, sum, sum_n [n_rec], all uint64 --, the kernels' record starts and tile sums
+struct CovTrack { uint32_t max_depth = 0, n_rec = 0; uint64_t bases = 0; bool valid = false; DevBuf diff, tab, rec, tiles; };
 enum { TM_ERRSCAN,TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
 struct SinkPipe;             // scs_sink.h
@@ -267,6 +273,9 @@ struct scs_ctx {
     bool truth_ref = false; DevBuf t_refs;
     // depth track (scs_set_depth; scs_depth.cpp): counters reads[bins] then bases[bins]; tables rec_off[nr + 1] then bin_off[nr + 1]
     DepthTrack depth;
+    // coverage profile (scs_set_coverage; scs_coverage.cpp)
+    CovTrack cov;
+    KernelTimer tm_cov_mark{"k_cov_mark"}, tm_cov_finish{"k_cov_finish"};   // the last yield call's per-batch marks and its end-of-job pass (scs_coverage_kernel_time; not of tm[])
     // lift table (scs_lift.cpp): the staged records as stretches of the original reference -- kept by scs_simuvars
     // or read by scs_load_lift, on the host and (d_lift: the segments) on the device; tied to the staged genome: staging another drops it.
     // Depth by reference bin (scs_set_depth_ref; scs_depth.cpp): the bins of the reference records; counters reads, bases, copies of
@@ -344,7 +353,7 @@ struct scs_ctx {
     scs_stats st{};
     KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}, {"k_depth"}};
     // the timers a yield call runs: reset at its start, collected at its end.  A new side output's timer is one more entry here
-    std::array<KernelTimer*, 8> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref, &tm_support_ref_open, &tm_support_ref_gather}; }
+    std::array<KernelTimer*, 10> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref, &tm_support_ref_open, &tm_support_ref_gather, &tm_cov_mark, &tm_cov_finish}; }
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
@@ -407,6 +416,12 @@ void truth_ref_release(scs_ctx* c);
 void depth_check(scs_ctx* c);
 void depth_yield_check(scs_ctx* c);
 void depth_open(scs_ctx* c, bool on_ref);
+// the coverage profile (scs_coverage.cpp): coverage_check refuses (SCS_EINVAL) a sharded or sliced ctx at the yield call's entry;
+// coverage_open: the call's zeroed difference array and tables and the kernels' record starts; coverage_finish: the end-of-job
+// pass on the ctx stream (lds: buckets of its LDS histogram)
+void coverage_check(scs_ctx* c);
+void coverage_open(scs_ctx* c);
+void coverage_finish(scs_ctx* c, uint32_t lds);
 // lift table (scs_lift.cpp): lift_install makes T the ctx's table (host and device), lift_drop forgets it (every call that stages a
 // genome); need_lift refuses (SCS_EINVAL) in fn's name where there is none
 void lift_install(scs_ctx* c, LiftTable&& T);

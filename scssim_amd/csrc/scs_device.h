@@ -99,8 +99,8 @@ struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned
 
 // error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right,
 // 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table, 9 for the site support counters, 10 for the
-// depth track by reference bin
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512, FLAG_LIFT = 1024 };
+// depth track by reference bin, 11 for the coverage profile
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512, FLAG_LIFT = 1024, FLAG_COVERAGE = 2048 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))
@@ -280,6 +280,25 @@ struct DepthArgs : PlaceArgs {
     unsigned long long* reads; unsigned long long* bases;  // the counters, one per bin each
 };
 void launch_depth(hipStream_t s, const DepthArgs& a);
+
+// ---- coverage profile (scs_k_coverage.hip; scs_set_coverage): per-base depth as a difference array of
+// n_bases + 1 int32 entries, padded with zeros to cov_tiles(n_bases) tiles of COV_TILE.  launch_cov_mark, per batch: +1 / -1 at the
+// ends of every read's aligned runs.  launch_cov_finish, once: the array becomes the depths (in place), counted per record into
+// hist (n_rec rows of max_depth + 1), n_n / sum / sum_n (n_rec each); lds: buckets of a workgroup's LDS histogram (at most
+// COV_LDS_BUCKETS; 0: every count goes to memory); tile_sums / tile_offs: cov_tiles(n_bases) entries each.  FLAG_COVERAGE: a read
+// outside its record, more than TRUTH_EVCAP events, a negative depth, or a depth that is not 0 behind the last base
+struct CovArgs : PlaceArgs {
+    const uint64_t* rec_off; uint32_t n_rec;               // record starts (n_rec + 1)
+    int32_t* diff;
+};
+struct CovFinish {
+    int32_t* diff; const uint8_t* codes; uint64_t n_bases; const uint64_t* rec_off; uint32_t n_rec, max_depth, lds;
+    int32_t* tile_sums; int32_t* tile_offs;
+    unsigned long long* hist; unsigned long long* n_n; unsigned long long* sum; unsigned long long* sum_n; uint32_t* flags;
+};
+uint64_t cov_tiles(uint64_t n_bases);
+void launch_cov_mark(hipStream_t s, const CovArgs& a);
+void launch_cov_finish(hipStream_t s, const CovFinish& f);
 
 // ---- lift table (scs_k_lift.hip; scs_lift.h): the staged records as stretches of the original reference.
 // k_depth_lift: the depth track of a batch by REFERENCE bin -- k_depth's placement and LDS table, the bins found through the

@@ -51,6 +51,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_SITE) m += " artefact table (an amplicon that cannot be placed, a slab whose entries differ from their count, site counts that contradict each other, or a line the two passes size differently)";
         if (f & FLAG_LIFT) m += " depth by reference bin / truth SAM on the reference (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand; artefact table on the reference: an amplicon whose walk leaves the lift table or its record's segments, or a segment that lifts outside its reference record)";
         if (f & FLAG_SUPPORT) m += " site support (a read placed outside its record, pair flags that are not a strand, a read with more than 32 indel events, a FASTQ record that is not where the offsets say, or sites that are not in order" + std::string(c->support_ref ? "; on the reference: staged positions that do not ascend, or a reference counter past 2^32 - 1" : "") + ")";
+        if (f & FLAG_COVERAGE) m += " coverage profile (a read placed outside its record, a read with more than 32 indel events, pair flags that are not a strand, a negative running depth, or a depth that is not 0 behind the genome's last base)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }
@@ -90,7 +91,7 @@ int scs_create(const scs_config* cfg, scs_ctx** out) {
         if (cfg->stream) c->stream.adopt((hipStream_t)cfg->stream); else c->stream.ensure(hipStreamNonBlocking);
         c->key = RngKey{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32)};
         for (KernelTimer& t : c->tm) t.gate = &c->timing_gate;
-        c->tm_support.gate = &c->timing_gate; c->tm_depth_ref.gate = &c->timing_gate; c->tm_support_ref_open.gate = &c->timing_gate; c->tm_support_ref_gather.gate = &c->timing_gate;
+        c->tm_support.gate = &c->timing_gate; c->tm_depth_ref.gate = &c->timing_gate; c->tm_support_ref_open.gate = &c->timing_gate; c->tm_support_ref_gather.gate = &c->timing_gate; c->tm_cov_mark.gate = &c->timing_gate; c->tm_cov_finish.gate = &c->timing_gate;
         c->flags.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->flags.p, 0, 256, c->stream));
         c->dsums.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->dsums.p, 0, 256, c->stream));
         c->d_tot.reserve(256, c->stream);
@@ -202,7 +203,7 @@ int scs_allocate_reads(scs_ctx* c, uint64_t reads) { return guarded(c, [&] { do_
 static int discard_sink(void*, const char*, size_t, const char*, size_t) { return 0; }
 int scs_yield_reads(scs_ctx* c, scs_sink_fn sink, void* user) {
     return guarded(c, [&] {
-        truth_check(c, false, 1); depth_check(c); support_check(c);
+        truth_check(c, false, 1); depth_check(c); support_check(c); coverage_check(c);
         // with truth on, a NULL sink still takes the sink path: the SAM needs its writer; the FASTQ text stays on the device
         double t = now_s(); CallbackSink cb(sink ? sink : discard_sink, user);
         OutTarget tg{false, nullptr, nullptr, 0, 0, (sink || !c->truth_path.empty()) ? &cb : nullptr}; tg.discard = !sink;
@@ -212,7 +213,7 @@ int scs_yield_reads(scs_ctx* c, scs_sink_fn sink, void* user) {
 int scs_yield_reads_device(scs_ctx* c, void* d1, size_t cap1, void* d2, size_t cap2, uint64_t* n1, uint64_t* n2, uint64_t* pairs) {
     return guarded(c, [&] {
         if (!d1 || (c->cfg.paired && !d2)) throw ScsError(SCS_EINVAL, "scs_yield_reads_device: null output buffer");
-        truth_check(c, true, 1); depth_check(c); support_check(c);
+        truth_check(c, true, 1); depth_check(c); support_check(c); coverage_check(c);
         double t = now_s(); OutTarget tg{true, (char*)d1, (char*)d2, cap1, cap2, nullptr}; do_yield(c, tg, n1, n2, pairs); c->st.t_stage[5] = now_s() - t;
     });
 }
@@ -225,7 +226,7 @@ int scs_yield_reads_files_ex(scs_ctx* c, const char* prefix, int writers, int ge
         if (flags & ~(SCS_SINK_BGZF | SCS_SINK_IN_PLACE)) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: unknown sink flag");
         if (!prefix || !*prefix) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: no output prefix");
         if (writers > 64 || generations > 64 || (int64_t)std::max(1, writers) * std::max(1, generations) > 99) throw ScsError(SCS_EINVAL, "scs_yield_reads_files: at most 64 writers and 99 parts");
-        truth_check(c, false, writers); depth_check(c); support_check(c);
+        truth_check(c, false, writers); depth_check(c); support_check(c); coverage_check(c);
         const bool pe = c->cfg.paired != 0, shard = c->cfg.shard_count > 1; const std::string pre = prefix;
         const std::string base = shard ? shard_base(pre, c->cfg.shard_rank) : pre;
         FastqParts files; std::string err;

@@ -149,12 +149,12 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth.width != 0, depth_ref = c->depth_ref.width != 0, support = c->support_on; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth.width != 0, depth_ref = c->depth_ref.width != 0, support = c->support_on, coverage = c->cov.max_depth != 0; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, bi = 0;                           // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
     OutFile truth_fd;                                                              // (closed after the pipe's writers have ended: declared first); its total: the header, every batch's bytes, the end-of-file block
-    PipeGuard guard{nullptr}; RecTable rt; TruthArgs ta{}; DepthArgs da{}; LiftArgs la{}; SupportArgs sa{};
+    PipeGuard guard{nullptr}; RecTable rt; TruthArgs ta{}; DepthArgs da{}; LiftArgs la{}; SupportArgs sa{}; CovArgs ca{};
     // shard index: the pair index at which each list segment starts (pair_off at the segment's first amplicon); the byte offset of
     // that record = the bytes of the batches before its batch (known once every batch is made) + its offset inside the batch
     std::vector<uint64_t> bpair, bb[2]; std::vector<SegAt> seg_at;
@@ -222,6 +222,12 @@ struct Yield {               // the state of one do_yield call
         sa.counts = c->sp_cnt.as<uint32_t>(); sa.slots = slots;
         place_job(sa);
     }
+    void coverage_open() {
+        // this call's difference array and tables, zeroed on the ctx stream, and the kernels' record starts (scs_coverage.cpp)
+        scs::coverage_open(c);
+        ca.rec_off = c->cov.rec.as<uint64_t>(); ca.n_rec = c->cov.n_rec; ca.diff = c->cov.diff.as<int32_t>();
+        place_job(ca);
+    }
     void setup() {           // the batches' bounds; the truth file; the pipe's writers; the BGZF totals' pinned words and events, the BGZF kernels' CRC tables; the batches' two buffer sets; the pre-pass' stream; the shard index
         // The pairs are planned (k_plan_pairs: insert sizes, positions, the amplicon resolved to an index map) batch by batch, at the
         // head of each batch's pre-pass: bounds[b] = the amplicon that holds the batch's first pair.
@@ -235,6 +241,7 @@ struct Yield {               // the state of one do_yield call
         if (depth) depth_open();
         if (depth_ref) depth_ref_open();
         if (support) support_open();
+        if (coverage) coverage_open();
         if (to_sink) {
             if (!c->pipe) c->pipe.reset(new SinkPipe);
             c->copy_stream.ensure(hipStreamNonBlocking); for (int k = 0; k < 2; ++k) { c->ev_made[k].ensure(hipEventDisableTiming); c->ev_d2h[k].ensure(hipEventDisableTiming); }
@@ -399,6 +406,17 @@ struct Yield {               // the state of one do_yield call
         launch_support(s, sa);
         c->tm_support.end(s); c->tm_support.add_units(b.np);
     }
+    void coverage_batch(const Batch& b) {
+        // the batch's reads into the difference array, from what depth_batch reads.  Before ev_free, as truth_batch
+        place_batch(ca, b);
+        c->tm_cov_mark.begin(s);
+        launch_cov_mark(s, ca);
+        c->tm_cov_mark.end(s); c->tm_cov_mark.add_units(b.np);
+    }
+    void coverage_finish() {
+        // after the last batch: the differences become depths, counted per record (three kernels on the ctx stream, scs_k_coverage.hip)
+        scs::coverage_finish(c, seam_u32("SCS_TEST_COV_LDS", COV_LDS_BUCKETS));   // (read at every call: the legs of one test job differ in it)
+    }
     void ship(Ship sh) {                                                           // D2H on the copy stream into a free pinned slot, then to the region's writer
         if (bgzf || (bam && sh.p[2])) HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl]));   // the blocks' totals have arrived
         if (bgzf) { sh.n[0] = c->h_z[sh.dsl * 3]; sh.n[1] = c->h_z[sh.dsl * 3 + 1]; }
@@ -445,7 +463,7 @@ struct Yield {               // the state of one do_yield call
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];
         for (KernelTimer* t : c->yield_timers()) t->collect();
-        c->depth.valid = depth; c->support_valid = support; c->depth_ref.valid = depth_ref;
+        c->depth.valid = depth; c->support_valid = support; c->depth_ref.valid = depth_ref; c->cov.valid = coverage;
         c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
         for (int m = 0; m < 2; ++m) { c->st.fastq_bytes[m] = tot[m]; c->st.sink_bytes[m] = to_sink ? sunk[m] : 0; }
         // 1526 B per created amplicon + per pair (insert size + FASTQ bytes of both records)
@@ -464,7 +482,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
     for (KernelTimer* t : c->yield_timers()) t->reset();
-    c->depth.valid = false; c->support_valid = false; c->depth_ref.valid = false;
+    c->depth.valid = false; c->support_valid = false; c->depth_ref.valid = false; c->cov.valid = false;
     depth_yield_check(c);                                  // more than 2^27 bins, no lift table: refused before any GPU work
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
@@ -497,6 +515,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         if (y.depth) y.depth_batch(b);
         if (y.depth_ref) y.depth_ref_batch(b);
         if (y.support) y.support_batch(b);
+        if (y.coverage) y.coverage_batch(b);
         if (y.ps != s) { HIP_OK(hipEventRecord(c->ev_free[b.k], s)); y.free_rec[b.k] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
         if (y.to_sink) y.sink_batch(b);                                            // BGZF where asked; then to the region's writer (with BGZF: the batch before)
@@ -504,6 +523,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     }
     if (y.have_pending) y.ship(y.pending);
     if (y.support) support_close(c);                                               // (the table on the reference: the staged counters summed by reference position)
+    if (y.coverage) y.coverage_finish();                                           // (the per-base depths and their histogram, before the call's last synchronise)
     y.finish(n1_out, n2_out, pairs_out);
 }
 
