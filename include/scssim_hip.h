@@ -355,6 +355,62 @@ int         scs_coverage_stats_probe(const uint64_t* hist, uint32_t max_depth, u
 void        scs_coverage_tile(uint32_t* tile, uint32_t* chunk);
 int         scs_coverage_finish_probe(scs_ctx* ctx, const int32_t* diff, const uint8_t* codes, uint64_t n_bases, const uint64_t* rec_lens, uint32_t n_records,
                                       uint32_t max_depth, int lds_buckets, uint32_t* depth, uint64_t* hist, uint64_t* n_n, uint64_t* sum, uint64_t* sum_n);
+/* ---- coverage profile on the reference: the per-base depth an aligner's pile-up is compared with --------------------------
+ * scs_set_coverage_ref(ctx, max_depth): the following yield calls also keep, for every base p of the reference records the lift
+ * table names (scs_simuvars, scs_load_lift), ref_depth[p] (uint32) = the sum of the staged depths (scs_set_coverage's depth[g]) of
+ * every staged base in an R segment that lifts to p: every haplotype and every tandem copy counts, and a read over two copies of
+ * p counts twice, as its pieces do in scs_set_depth_ref's `bases`.  0: off, the default -- no buffer exists, no code of it runs;
+ * max_depth D in 1 .. 65535, independent of scs_set_coverage's.  The depths are lifted ONCE, at the end of the job: the batches
+ * mark the staged difference array, the staged end-of-job pass makes the staged depths, two more kernels carry them through the
+ * table and count them.  So this switch brings the staged array and its pass whether or not scs_set_coverage is on (one array,
+ * one marking pass per batch with both on); scs_download_coverage, scs_coverage_range and scs_write_coverage still need
+ * scs_set_coverage (and while this switch is on, scs_set_coverage with another max_depth releases the staged tables only: the
+ * array stays).  Staged bases of I segments have no reference coordinate: their depths are summed into `unlifted`, so
+ * sum ref_depth + unlifted = sum of the staged depths = sum of the truth CIGARs' M lengths.  The host checks this equality
+ * (uint64 on both sides) when the call ends and fails the call with the coverage profile's flag error (SCS_EOVERFLOW) where it
+ * does not hold: that check is also the net under a uint32 wrap of one reference base's depth.
+ * Per reference base, made once per (genome, lift table): copies[p] = the staged bases that lift to p (the per-base true copy
+ * number), n_copies[p] = those of them that are N; 16 bits each in one uint32.  A table that could put more than 65535 staged
+ * bases on one reference base fails the call (SCS_EOVERFLOW) before any kernel runs.  Classes: N -- copies > 0 and every copy
+ * is N, in no bucket; absent -- copies = 0 (copy number 0 on every haplotype), counted in bucket 0 because no read can cover it
+ * and `genomecov` on aligned reads shows it so, and reported as `absent`, so hist[0] - absent is the uncovered present sequence;
+ * counted -- everything else (mixed N and non-N copies count as sequence).  The reference's own bases are never staged: an N gap
+ * under a CN-0 stretch cannot be told from sequence.
+ * Tables per reference record and a last `genome` row: hist[r][0 .. D] (the last bucket depth >= D), n_bases, absent, sum, sum_n
+ * (exact), and depth by copy number: cn_bases[r][c], cn_sum[r][c], c = 0 .. 16 (the last one copies >= 16) over the non-N bases,
+ * cn_sum / cn_bases the mean depth at true copy number c; cn_bases[r][0] = absent[r].
+ * Device memory: 8 bytes per reference base beside scs_set_coverage's 4 per staged base; an allocation that fails states the
+ * bytes.  Every yield entry point and sink; one GPU.  A sharded ctx, or a ctx without a lift table, fails the yield call with
+ * SCS_EINVAL naming this setter (and scs_load_lift / scs_simuvars) before any GPU work.  A segment that lifts outside its
+ * reference record adds nothing and fails the call (the lift flag's error).  Staging another genome or installing another table
+ * invalidates the arrays and has the copies remade; scs_set_coverage_ref(ctx, 0) (or another max_depth) releases them.
+ * scs_coverage_ref_shape: the reference records and max_depth (SCS_EINVAL: off, or no lift table).
+ * scs_download_coverage_ref: ref_records + 1 rows, the genome's last; hist max_depth + 1 values per row, cn_bases / cn_sum 17;
+ * any pointer may be NULL; errors as scs_download_coverage.
+ * scs_coverage_ref_range: ref_depth and copies of [start, end) of reference record ref_record, from the device arrays; either
+ * output may be NULL.
+ * scs_write_coverage_ref: scs_write_coverage's text with the reference's record names: the "#coverage" line;
+ * "#summary\trecord\tbases\tn_bases\tabsent\taligned\tmean\tbreadth1\tbreadth5\tbreadth10\tbreadth20\tgini" and a "#s" line per
+ * record and for `genome`; "#cn\trecord\tcopies\tbases\taligned\tmean" and a "#c" line for every (record, c) with bases;
+ * "#unlifted\t<aligned bases>\t<inserted bases>"; then genomecov's five columns.
+ * scs_coverage_ref_kernel_time: which = 0 the once-per-layout copies kernel (no launch when the layout stands), 1 the end-of-job
+ * lift and count, units = staged bases; not part of scs_kernel_time's table.
+ * scs_coverage_ref_finish_probe (test seam, needs the GPU): the three kernels alone, as the product launches them, over staged
+ * depths and codes of n_staged bases, a table in scs_lift_segments' layout that tiles staged records of hap_lens, and reference
+ * records of ref_lens; lds_buckets as scs_coverage_finish_probe.  ref_depth / packed (copies | n_copies << 16) per reference
+ * base, the tables with n_ref rows, *unlifted; any output may be NULL.  The sum identity is checked as in a yield call. */
+int         scs_set_coverage_ref(scs_ctx* ctx, uint32_t max_depth);
+int         scs_coverage_ref_shape(const scs_ctx* ctx, uint32_t* ref_records, uint32_t* max_depth);
+int         scs_download_coverage_ref(scs_ctx* ctx, uint64_t* hist, uint64_t* n_bases, uint64_t* absent, uint64_t* sum, uint64_t* sum_n,
+                                      uint64_t* cn_bases, uint64_t* cn_sum, uint64_t* unlifted, uint64_t cap_rows);
+int         scs_coverage_ref_range(scs_ctx* ctx, uint32_t ref_record, uint64_t start, uint64_t end, uint32_t* depth_out, uint32_t* copies_out);
+int         scs_write_coverage_ref(scs_ctx* ctx, const char* path);
+int         scs_coverage_ref_kernel_time(const scs_ctx* ctx, int which, uint64_t* launches, double* ms, uint64_t* units);
+int         scs_coverage_ref_finish_probe(scs_ctx* ctx, const uint32_t* depth, const uint8_t* codes, uint64_t n_staged,
+                                          const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                                          const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, uint32_t max_depth, int lds_buckets,
+                                          uint32_t* ref_depth, uint32_t* packed, uint64_t* hist, uint64_t* n_n, uint64_t* absent, uint64_t* sum, uint64_t* sum_n,
+                                          uint64_t* cn_bases, uint64_t* cn_sum, uint64_t* unlifted);
 /* ---- lift table and depth by reference bin: the job in the coordinates of the original reference ---------------------------
  * Every other truth product lives in the coordinates of the staged haplotype records.  The lift table maps them to the reference
  * `simuvars` built them from: segments that ascend and tile the staged genome, none straddling two staged records, each `len`

@@ -464,6 +464,32 @@ def coverage_finish_probe(ctx, diff, codes, rec_lens, max_depth, lds_buckets=-1)
     return out
 
 
+def coverage_ref_finish_probe(ctx, depth, codes, segs, hap_lens, ref_lens, max_depth, lds_buckets=-1):
+    """Needs the GPU: the kernels of the coverage profile on the reference alone, as the product launches them, on the GenReads
+    `ctx`.  depth: uint32[G] staged depths, codes: uint8[G] (0 .. 3, 4 = N), segs: (hap_off, len, ref_pos, ref_rec, kind) arrays in
+    lift_segments' layout that tile staged records of hap_lens (adding up to G), ref_lens: the reference records; lds_buckets: buckets
+    of the count kernel's LDS histogram (-1: the product's).  Returns dict(ref_depth=uint32[R], packed=uint32[R] (copies |
+    n_copies << 16), hist=uint64[ref records][max_depth + 1], n_bases=, absent=, sum=, sum_n=, cn_bases=, cn_sum= [ref records][17],
+    unlifted=int).  A segment that lifts outside its reference record raises ScsError (SCS_EOVERFLOW) and leaves the ctx usable."""
+    import numpy as np
+    d, cd = np.ascontiguousarray(depth, np.uint32), np.ascontiguousarray(codes, np.uint8)
+    ho, ln, rp = (np.ascontiguousarray(v, np.uint64) for v in segs[:3])
+    rr, kd = (np.ascontiguousarray(v, np.uint32) for v in segs[3:5])
+    hl, rl = np.ascontiguousarray(hap_lens, np.uint64), np.ascontiguousarray(ref_lens, np.uint64)
+    G, nf, D, R = cd.size, rl.size, int(max_depth), int(rl.sum())
+    if d.size != G or not (ho.size == ln.size == rp.size == rr.size == kd.size):
+        raise ValueError("depth and codes have G entries, the segment arrays one length")
+    out = dict(ref_depth=np.zeros(R, np.uint32), packed=np.zeros(R, np.uint32), hist=np.zeros((nf, D + 1), np.uint64), n_bases=np.zeros(nf, np.uint64), absent=np.zeros(nf, np.uint64),
+               sum=np.zeros(nf, np.uint64), sum_n=np.zeros(nf, np.uint64), cn_bases=np.zeros((nf, 17), np.uint64), cn_sum=np.zeros((nf, 17), np.uint64))
+    unl = C.c_uint64()
+    fn = ctx._L.scs_coverage_ref_finish_probe
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int] + [C.c_void_p] * 9 + [C.POINTER(C.c_uint64)]
+    ctx._ck(fn(ctx._ctx, d.ctypes.data, cd.ctypes.data, G, ho.ctypes.data, ln.ctypes.data, rp.ctypes.data, rr.ctypes.data, kd.ctypes.data, ho.size, hl.ctypes.data, hl.size, rl.ctypes.data, nf, D, int(lds_buckets),
+               *[out[k].ctypes.data for k in ("ref_depth", "packed", "hist", "n_bases", "absent", "sum", "sum_n", "cn_bases", "cn_sum")], C.byref(unl)))
+    out["unlifted"] = unl.value
+    return out
+
+
 class LiftTable:
     """A lift table as numpy arrays: per segment hap_off (global staged index), len, ref_pos, ref_rec, kind (0: R, 1: I); the
     reference records' and the staged records' names and lengths."""
@@ -1124,6 +1150,59 @@ class GenReads:
         """Event pairs, milliseconds and units of the last yield call's coverage passes: which=0 the per-batch marks (units: pairs),
         1 the end-of-job pass (units: staged bases)."""
         fn = self._L.scs_coverage_kernel_time
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(fn(self._ctx, int(which), C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def set_coverage_ref(self, max_depth):
+        """Coverage profile on the reference: the following yield calls also keep, per base of the reference records of the lift
+        table, the summed per-base depth of every staged base that lifts to it (every haplotype and tandem copy), its histogram
+        per reference record and the depth by true copy number.  max_depth in 1 .. 65535, its own; 0 turns it off and releases the
+        arrays.  It brings the staged array of set_coverage with it; what set_coverage exposes still needs set_coverage."""
+        self._L.scs_set_coverage_ref.argtypes = [C.c_void_p, C.c_uint32]
+        self._ck(self._L.scs_set_coverage_ref(self._ctx, int(max_depth)))
+
+    def coverage_ref_shape(self):
+        """(reference records, max_depth) of the coverage profile on the reference."""
+        self._L.scs_coverage_ref_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        n, d = C.c_uint32(), C.c_uint32()
+        self._ck(self._L.scs_coverage_ref_shape(self._ctx, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    def download_coverage_ref(self):
+        """The tables of the last yield call on the reference as numpy uint64 arrays: dict(hist=[ref records + 1][max_depth + 1],
+        n_bases=, absent=, sum=, sum_n= [ref records + 1], cn_bases=, cn_sum= [ref records + 1][17], unlifted=int); the last row is the genome."""
+        np = self._np
+        nf, D = self.coverage_ref_shape()
+        a = dict(hist=np.zeros((nf + 1, D + 1), np.uint64), n_bases=np.zeros(nf + 1, np.uint64), absent=np.zeros(nf + 1, np.uint64), sum=np.zeros(nf + 1, np.uint64), sum_n=np.zeros(nf + 1, np.uint64),
+                 cn_bases=np.zeros((nf + 1, 17), np.uint64), cn_sum=np.zeros((nf + 1, 17), np.uint64))
+        unl = C.c_uint64()
+        self._L.scs_download_coverage_ref.argtypes = [C.c_void_p] * 8 + [C.POINTER(C.c_uint64), C.c_uint64]
+        self._ck(self._L.scs_download_coverage_ref(self._ctx, *[a[k].ctypes.data for k in ("hist", "n_bases", "absent", "sum", "sum_n", "cn_bases", "cn_sum")], C.byref(unl), nf + 1))
+        a["unlifted"] = unl.value
+        return a
+
+    def coverage_ref_range(self, ref_record, start, end):
+        """(depth, copies) of [start, end) of reference record `ref_record` after the last yield call, as numpy uint32: the summed
+        per-base depth and the staged bases that lift to each base (its true copy number)."""
+        np = self._np
+        n = max(0, int(end) - int(start))
+        d, cp = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._L.scs_coverage_ref_range.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        self._ck(self._L.scs_coverage_ref_range(self._ctx, int(ref_record), int(start), int(end), d.ctypes.data, cp.ctypes.data))
+        return d, cp
+
+    def write_coverage_ref(self, path):
+        """The coverage profile on the reference of the last yield call as text: write_coverage's lines per reference record (with
+        `absent`), the mean depth by true copy number (#c lines), what lies in inserted sequence (#unlifted), genomecov's columns."""
+        self._L.scs_write_coverage_ref.argtypes = [C.c_void_p, C.c_char_p]
+        self._ck(self._L.scs_write_coverage_ref(self._ctx, os.fsencode(path)))
+
+    def coverage_ref_kernel_time(self, which=0):
+        """Event pairs, milliseconds and units (staged bases) of the last yield call's passes on the reference: which=0 the
+        once-per-layout copies kernel (no launch while the layout stands), 1 the end-of-job lift and count."""
+        fn = self._L.scs_coverage_ref_kernel_time
         fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
         self._ck(fn(self._ctx, int(which), C.byref(n), C.byref(ms), C.byref(u)))

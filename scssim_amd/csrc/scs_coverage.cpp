@@ -1,7 +1,9 @@
 // scs_coverage.cpp -- the coverage profile (include/scssim_hip.h: scs_set_coverage ...): the state of a ctx's
 // profile (CovTrack, scs_ctx.h), its refusals, the buffers of a yield call, the end-of-job pass, read-out and file.  What a read
 // marks and the file's summary are scs_coverage.h's; the kernels are scs_k_coverage.hip's, the per-batch one launched from
-// scs_reads.cpp.
+// scs_reads.cpp.  Below it the profile on the original reference (scs_set_coverage_ref ...; CovRefTrack): the
+// staged depths carried through the lift table at the end of the job (scs_k_coverage_ref.hip), with the same read-out and file.
+// Either switch brings the staged array and its end-of-job pass; what a switch EXPOSES is its own.
 #include "scs_textout.h"
 #include <cerrno>
 
@@ -30,17 +32,96 @@ CovTables tables(scs_ctx* c) {
     return t;
 }
 
+// ---- on the reference
+const char* const kRefLabel = "coverage profile on the reference (scs_set_coverage_ref)";
+
+void ref_ready(const scs_ctx* c, const std::string& fn) {
+    if (!c->cov_ref.max_depth || !c->cov_ref.valid) throw ScsError(SCS_EINVAL, fn + ": no yield call with the coverage profile on the reference on (scs_set_coverage_ref) has finished");
+}
+// where the tables lie in CovRefTrack::tab, in uint64 words: hist[nf][D + 1], n_n, absent, sum, sum_n [nf], cn_bases, cn_sum [nf][17], unlifted
+struct RefTab {
+    size_t nf, row, nc, nn, ab, sum, sumn, cnb, cns, unl, words;
+    RefTab(uint32_t n_ref, uint32_t D) : nf(n_ref), row((size_t)D + 1), nc(COV_REF_CN + 1u), nn(nf * row), ab(nn + nf), sum(ab + nf), sumn(sum + nf), cnb(sumn + nf), cns(cnb + nf * nc), unl(cns + nf * nc), words(unl + 1) {}
+};
+// a table that could put more than COV_REF_MAX_COPIES staged bases on one reference base is refused: the packed word's 16 bits
+// never wrap silently.  A sweep over the R segments' ends per reference record
+void ref_copies_fit(const LiftSeg* segs, size_t n) {
+    std::vector<std::pair<std::pair<uint32_t, uint64_t>, int>> ev; ev.reserve(2 * n);
+    for (size_t i = 0; i < n; ++i) if (segs[i].kind == 0u && segs[i].len) { ev.push_back({{segs[i].ref_rec, segs[i].ref_pos}, 1}); ev.push_back({{segs[i].ref_rec, segs[i].ref_pos + segs[i].len}, -1}); }
+    std::sort(ev.begin(), ev.end());                                               // (an end sorts before a start at the same coordinate)
+    int64_t run = 0;
+    for (const auto& e : ev) { run += e.second; if (run > (int64_t)COV_REF_MAX_COPIES) throw ScsError(SCS_EOVERFLOW, std::string(kRefLabel) + ": more than 65535 staged bases lift to one reference base (record " + std::to_string(e.first.first) + ", position " + std::to_string(e.first.second) + "); the per-base copies are 16 bits wide"); }
+}
+// R's arrays for reference records of these lengths and max_depth D, beside a staged array of `staged` bases: reserved (an
+// allocation failure states the bytes), the record starts uploaded; nothing is zeroed here
+void ref_reserve(CovRefTrack& R, const std::vector<uint64_t>& ref_lens, uint32_t D, uint64_t staged, hipStream_t s) {
+    const uint32_t nf = (uint32_t)ref_lens.size();
+    if (!nf) throw ScsError(SCS_EINVAL, std::string(kRefLabel) + ": the lift table names no reference record");
+    std::vector<uint64_t> roff(nf + 1, 0);
+    for (uint32_t r = 0; r < nf; ++r) roff[r + 1] = roff[r] + ref_lens[r];
+    const uint64_t nt = cov_ref_tiles(roff[nf]);
+    if (nt > 0x7FFFFFFFull) throw ScsError(SCS_EINVAL, std::string(kRefLabel) + ": the reference has more tiles than a grid holds");
+    const size_t arr = std::max<size_t>((size_t)nt * COV_TILE * 4, 16);
+    try { R.depth.reserve(arr, s); R.packed.reserve(arr, s); }
+    catch (const ScsError& e) {
+        throw ScsError(e.code, std::string(kRefLabel) + ": the two per-base arrays of " + std::to_string(roff[nf]) + " reference bases need " + std::to_string(2 * arr) + " bytes of device memory (8 per reference base), beside " +
+                       std::to_string((size_t)cov_tiles(staged) * COV_TILE * 4) + " bytes of the staged array (4 per staged base): " + e.what());
+    }
+    R.tab.reserve(RefTab(nf, D).words * 8, s);
+    upload(R.rec, roff, s);
+    R.n_ref = nf; R.bases = roff[nf];
+    HIP_OK(hipStreamSynchronize(s));                                               // (the host table goes)
+}
+CovRefArgs ref_args(const CovRefTrack& R, uint32_t D, const LiftSeg* segs, uint32_t n_seg, const uint32_t* depth, const uint8_t* codes, uint64_t staged, uint32_t lds, uint32_t* flags) {
+    const RefTab t(R.n_ref, D); unsigned long long* tab = R.tab.as<unsigned long long>();
+    return CovRefArgs{segs, n_seg, R.rec.as<uint64_t>(), R.n_ref, staged, R.bases, depth, codes, R.depth.as<uint32_t>(), R.packed.as<uint32_t>(), D, lds,
+                      tab, tab + t.nn, tab + t.ab, tab + t.sum, tab + t.sumn, tab + t.cnb, tab + t.cns, tab + t.unl, flags};
+}
+void ref_zero(const CovRefTrack& R, uint32_t D, bool packed_too, hipStream_t s) {
+    const size_t arr = std::max<size_t>((size_t)cov_ref_tiles(R.bases) * COV_TILE * 4, 16);
+    HIP_OK(hipMemsetAsync(R.depth.p, 0, arr, s)); HIP_OK(hipMemsetAsync(R.tab.p, 0, RefTab(R.n_ref, D).words * 8, s));
+    if (packed_too) HIP_OK(hipMemsetAsync(R.packed.p, 0, arr, s));
+}
+// the last call's tables on the host, nf + 1 rows each (the genome's last)
+struct RefTables { uint32_t nf, D; std::vector<uint64_t> hist, n_n, absent, sum, sum_n, cn_bases, cn_sum; uint64_t unlifted; };
+RefTables ref_tables(const CovRefTrack& R, uint32_t D, hipStream_t s) {
+    const RefTab t(R.n_ref, D); const size_t nf = t.nf;
+    std::vector<uint64_t> all(t.words);
+    HIP_OK(hipMemcpyAsync(all.data(), R.tab.p, all.size() * 8, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s));
+    RefTables o{R.n_ref, D, std::vector<uint64_t>((nf + 1) * t.row, 0), std::vector<uint64_t>(nf + 1, 0), std::vector<uint64_t>(nf + 1, 0), std::vector<uint64_t>(nf + 1, 0), std::vector<uint64_t>(nf + 1, 0),
+                std::vector<uint64_t>((nf + 1) * t.nc, 0), std::vector<uint64_t>((nf + 1) * t.nc, 0), all[t.unl]};
+    std::copy(all.begin(), all.begin() + t.nn, o.hist.begin());
+    std::copy(all.begin() + t.cnb, all.begin() + t.cns, o.cn_bases.begin()); std::copy(all.begin() + t.cns, all.begin() + t.unl, o.cn_sum.begin());
+    for (size_t r = 0; r < nf; ++r) {
+        for (size_t k = 0; k < t.row; ++k) o.hist[nf * t.row + k] += o.hist[r * t.row + k];
+        for (size_t k = 0; k < t.nc; ++k) { o.cn_bases[nf * t.nc + k] += o.cn_bases[r * t.nc + k]; o.cn_sum[nf * t.nc + k] += o.cn_sum[r * t.nc + k]; }
+        o.n_n[r] = all[t.nn + r]; o.absent[r] = all[t.ab + r]; o.sum[r] = all[t.sum + r]; o.sum_n[r] = all[t.sumn + r];
+        o.n_n[nf] += o.n_n[r]; o.absent[nf] += o.absent[r]; o.sum[nf] += o.sum[r]; o.sum_n[nf] += o.sum_n[r];
+    }
+    return o;
+}
+// sum ref_depth + unlifted = sum staged depth, uint64 on both sides: the reads' aligned bases all arrived somewhere.  It is also
+// the net under a uint32 wrap of one reference base's depth (many copies of a deep base): FLAG_COVERAGE's error
+void ref_identity(const RefTables& t, uint64_t staged_sum) {
+    const uint64_t got = t.sum[t.nf] + t.sum_n[t.nf] + t.unlifted;
+    if (got != staged_sum) throw ScsError(SCS_EOVERFLOW, "device work buffer overflow: coverage profile (on the reference: the depths of the reference bases and of inserted sequence add up to " + std::to_string(got) +
+                                          ", the staged depths to " + std::to_string(staged_sum) + " -- a reference base's depth passed 2^32 - 1, or the lift table does not cover the staged genome)");
+}
+
 }  // namespace
 
 void coverage_check(scs_ctx* c) {
-    if (!c->cov.max_depth) return;
-    if (c->cfg.shard_count > 1 || c->sliced) throw ScsError(SCS_EINVAL, std::string(kLabel) + ": not available for a sharded job (shard_count > 1); turn it off with scs_set_coverage(ctx, 0)");
+    const bool sharded = c->cfg.shard_count > 1 || c->sliced;
+    if (c->cov.max_depth && sharded) throw ScsError(SCS_EINVAL, std::string(kLabel) + ": not available for a sharded job (shard_count > 1); turn it off with scs_set_coverage(ctx, 0)");
+    if (!c->cov_ref.max_depth) return;
+    if (sharded) throw ScsError(SCS_EINVAL, std::string(kRefLabel) + ": not available for a sharded job (shard_count > 1); turn it off with scs_set_coverage_ref(ctx, 0)");
+    if (!c->have_lift) throw ScsError(SCS_EINVAL, std::string(kRefLabel) + ": the staged genome has no lift table; stage it with scs_simuvars, or read its table with scs_load_lift after staging");
 }
 
 // This call's difference array and tables, zeroed on the ctx stream, and the kernels' record starts (nr + 1) and tile sums
 void coverage_open(scs_ctx* c) {
     CovTrack& T = c->cov; const hipStream_t s = c->stream;
-    const std::vector<uint64_t> roff = record_starts(c); const uint32_t nr = (uint32_t)c->recs.size(), D = T.max_depth;
+    const std::vector<uint64_t> roff = record_starts(c); const uint32_t nr = (uint32_t)c->recs.size(), D = T.run_depth = T.max_depth ? T.max_depth : 1u;   // (only the profile on the reference is on: any valid max_depth, the tables stay private)
     if (!nr) throw ScsError(SCS_EINVAL, std::string(kLabel) + ": no genome is staged");
     const uint64_t G = roff[nr], nt = cov_tiles(G);
     if (nt > 0x7FFFFFFFull) throw ScsError(SCS_EINVAL, std::string(kLabel) + ": the staged genome has more tiles than a grid holds");
@@ -56,13 +137,50 @@ void coverage_open(scs_ctx* c) {
 
 // After the last batch: the differences become the depths, counted into the tables; the kernels' errors reach the call through the flags word
 void coverage_finish(scs_ctx* c, uint32_t lds) {
-    CovTrack& T = c->cov; const hipStream_t s = c->stream; const uint32_t nr = T.n_rec, D = T.max_depth; const uint64_t nt = cov_tiles(T.bases);
+    CovTrack& T = c->cov; const hipStream_t s = c->stream; const uint32_t nr = T.n_rec, D = T.run_depth; const uint64_t nt = cov_tiles(T.bases);
     unsigned long long* tab = T.tab.as<unsigned long long>(); const size_t nh = (size_t)nr * ((size_t)D + 1);
     const CovFinish f{T.diff.as<int32_t>(), c->genome.as<uint8_t>(), T.bases, T.rec.as<uint64_t>(), nr, D, lds, T.tiles.as<int32_t>(), T.tiles.as<int32_t>() + nt,
                       tab, tab + nh, tab + nh + nr, tab + nh + 2 * (size_t)nr, c->flags.as<uint32_t>()};
     c->tm_cov_finish.begin(s);
     launch_cov_finish(s, f);
     c->tm_cov_finish.end(s); c->tm_cov_finish.add_units(T.bases);
+}
+
+
+// The call's reference array and tables, zeroed on the ctx stream; the packed copies where the genome or the table is new (the
+// staged array is open: coverage_open has run)
+void coverage_ref_open(scs_ctx* c) {
+    CovRefTrack& R = c->cov_ref; const hipStream_t s = c->stream;
+    need_lift(c, "scs_set_coverage_ref");
+    if (c->lift.total() != c->cov.bases) throw ScsError(SCS_EINVAL, std::string(kRefLabel) + ": the lift table covers " + std::to_string(c->lift.total()) + " staged bases, " + std::to_string(c->cov.bases) + " are staged");
+    if (!R.copies) ref_copies_fit(c->lift.segs.data(), c->lift.segs.size());
+    ref_reserve(R, c->lift.ref_lens, R.max_depth, c->cov.bases, s);
+    ref_zero(R, R.max_depth, !R.copies, s);
+    if (!R.copies) {
+        c->tm_cov_ref_copies.begin(s);
+        launch_cov_ref_copies(s, ref_args(R, R.max_depth, c->d_lift.as<LiftSeg>(), (uint32_t)c->lift.segs.size(), nullptr, c->genome.as<uint8_t>(), c->cov.bases, 0, c->flags.as<uint32_t>()));
+        c->tm_cov_ref_copies.end(s); c->tm_cov_ref_copies.add_units(c->cov.bases);
+    }
+    HIP_OK(hipStreamSynchronize(s));                                               // (the host table goes)
+    if (!R.copies) { check_flags(c); R.copies = true; }
+}
+
+// After coverage_finish: the staged depths lie where their differences lay
+void coverage_ref_finish(scs_ctx* c, uint32_t lds) {
+    CovRefTrack& R = c->cov_ref; const hipStream_t s = c->stream;
+    c->tm_cov_ref_finish.begin(s);
+    launch_cov_ref_finish(s, ref_args(R, R.max_depth, c->d_lift.as<LiftSeg>(), (uint32_t)c->lift.segs.size(), c->cov.diff.as<uint32_t>(), c->genome.as<uint8_t>(), c->cov.bases, lds, c->flags.as<uint32_t>()));
+    c->tm_cov_ref_finish.end(s); c->tm_cov_ref_finish.add_units(c->cov.bases);
+}
+
+void coverage_ref_close(scs_ctx* c) {
+    const CovTrack& T = c->cov; const size_t nr = T.n_rec, nh = nr * ((size_t)T.run_depth + 1);
+    std::vector<uint64_t> st(2 * nr);
+    if (nr) HIP_OK(hipMemcpyAsync(st.data(), T.tab.as<uint64_t>() + nh + nr, st.size() * 8, hipMemcpyDeviceToHost, c->stream));   // the staged pass' sum and sum_n
+    const RefTables t = ref_tables(c->cov_ref, c->cov_ref.max_depth, c->stream);   // (synchronises)
+    uint64_t staged = 0; for (uint64_t v : st) staged += v;
+    ref_identity(t, staged);
+    c->cov_ref.unlifted = t.unlifted;
 }
 
 }  // namespace scs
@@ -75,8 +193,9 @@ int scs_set_coverage(scs_ctx* c, uint32_t max_depth) {
         CovTrack& T = c->cov;
         if (max_depth == T.max_depth) return;
         HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's arrays go: nothing may still read them
-        T.diff.release(); T.tab.release(); T.rec.release(); T.tiles.release(); T.valid = false; T.bases = 0; T.n_rec = 0; T.max_depth = max_depth;
-        if (!max_depth) for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish}) { t->ev.clear(); t->used = 0; t->reset(); }
+        T.tab.release(); T.valid = false; T.max_depth = max_depth;
+        if (!c->cov_ref.max_depth) { T.diff.release(); T.rec.release(); T.tiles.release(); T.bases = 0; T.n_rec = 0; }   // (the array does not depend on max_depth: it stays while the profile on the reference, which reads it, is on)
+        if (!max_depth && !c->cov_ref.max_depth) for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish}) { t->ev.clear(); t->used = 0; t->reset(); }
     });
 }
 
@@ -142,6 +261,155 @@ int scs_write_coverage(scs_ctx* c, const char* path) {
 int scs_coverage_kernel_time(const scs_ctx* c, int which, uint64_t* launches, double* ms, uint64_t* units) {
     if (which != 0 && which != 1) return SCS_EINVAL;
     return kernel_time_of(c, which ? &scs_ctx::tm_cov_finish : &scs_ctx::tm_cov_mark, launches, ms, units);
+}
+
+// ---- on the reference
+int scs_set_coverage_ref(scs_ctx* c, uint32_t max_depth) {
+    return guarded(c, [&] {
+        if (max_depth > COV_MAX_DEPTH) throw ScsError(SCS_EINVAL, "scs_set_coverage_ref: max_depth is at most 65535 (0: off)");
+        CovRefTrack& R = c->cov_ref;
+        if (max_depth == R.max_depth) return;
+        HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's arrays go: nothing may still read them
+        R.depth.release(); R.packed.release(); R.tab.release(); R.rec.release(); R.valid = false; R.copies = false; R.bases = 0; R.n_ref = 0; R.unlifted = 0; R.max_depth = max_depth;
+        if (!max_depth) {
+            for (KernelTimer* t : {&c->tm_cov_ref_copies, &c->tm_cov_ref_finish}) { t->ev.clear(); t->used = 0; t->reset(); }
+            if (!c->cov.max_depth) {                                               // the staged array was this switch's alone
+                CovTrack& T = c->cov;
+                T.diff.release(); T.tab.release(); T.rec.release(); T.tiles.release(); T.bases = 0; T.n_rec = 0;
+                for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish}) { t->ev.clear(); t->used = 0; t->reset(); }
+            }
+        }
+    });
+}
+
+int scs_coverage_ref_shape(const scs_ctx* c, uint32_t* ref_records, uint32_t* max_depth) {
+    if (!c) return SCS_EINVAL;
+    if (!c->cov_ref.max_depth || !c->have_lift) { const_cast<scs_ctx*>(c)->err = "scs_coverage_ref_shape: the coverage profile on the reference is off (scs_set_coverage_ref), or the staged genome has no lift table (scs_simuvars, scs_load_lift)"; return SCS_EINVAL; }
+    if (ref_records) *ref_records = (uint32_t)c->lift.ref_lens.size();
+    if (max_depth) *max_depth = c->cov_ref.max_depth;
+    return SCS_OK;
+}
+
+int scs_download_coverage_ref(scs_ctx* c, uint64_t* hist, uint64_t* n_bases, uint64_t* absent, uint64_t* sum, uint64_t* sum_n, uint64_t* cn_bases, uint64_t* cn_sum, uint64_t* unlifted, uint64_t cap_rows) {
+    return guarded(c, [&] {
+        ref_ready(c, "scs_download_coverage_ref");
+        const uint64_t rows = (uint64_t)c->cov_ref.n_ref + 1;
+        if (cap_rows < rows) throw ScsError(SCS_EOVERFLOW, "scs_download_coverage_ref: " + std::to_string(rows) + " rows (the reference records and the genome), room for " + std::to_string(cap_rows));
+        const RefTables t = ref_tables(c->cov_ref, c->cov_ref.max_depth, c->stream);
+        if (hist) std::copy(t.hist.begin(), t.hist.end(), hist);
+        if (n_bases) std::copy(t.n_n.begin(), t.n_n.end(), n_bases);
+        if (absent) std::copy(t.absent.begin(), t.absent.end(), absent);
+        if (sum) std::copy(t.sum.begin(), t.sum.end(), sum);
+        if (sum_n) std::copy(t.sum_n.begin(), t.sum_n.end(), sum_n);
+        if (cn_bases) std::copy(t.cn_bases.begin(), t.cn_bases.end(), cn_bases);
+        if (cn_sum) std::copy(t.cn_sum.begin(), t.cn_sum.end(), cn_sum);
+        if (unlifted) *unlifted = t.unlifted;
+    });
+}
+
+int scs_coverage_ref_range(scs_ctx* c, uint32_t ref_record, uint64_t start, uint64_t end, uint32_t* depth_out, uint32_t* copies_out) {
+    return guarded(c, [&] {
+        ref_ready(c, "scs_coverage_ref_range"); need_lift(c, "scs_coverage_ref_range");
+        const std::vector<uint64_t>& lens = c->lift.ref_lens;
+        if (ref_record >= c->cov_ref.n_ref || ref_record >= lens.size() || start > end || end > lens[ref_record])
+            throw ScsError(SCS_EINVAL, "scs_coverage_ref_range: [" + std::to_string(start) + ", " + std::to_string(end) + ") of reference record " + std::to_string(ref_record) + " is not inside a reference record");
+        uint64_t off = start; for (uint32_t r = 0; r < ref_record; ++r) off += lens[r];
+        const size_t n = (size_t)(end - start);
+        if (n && depth_out) HIP_OK(hipMemcpyAsync(depth_out, c->cov_ref.depth.as<uint32_t>() + off, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (n && copies_out) HIP_OK(hipMemcpyAsync(copies_out, c->cov_ref.packed.as<uint32_t>() + off, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (copies_out) for (size_t i = 0; i < n; ++i) copies_out[i] &= 0xFFFFu;      // (the packed word's other half counts the N copies)
+    });
+}
+
+int scs_write_coverage_ref(scs_ctx* c, const char* path) {
+    return guarded(c, [&] {
+        const std::string fn = "scs_write_coverage_ref";
+        if (!path || !*path) throw ScsError(SCS_EINVAL, fn + ": no path");
+        ref_ready(c, fn); need_lift(c, fn.c_str());
+        const RefTables t = ref_tables(c->cov_ref, c->cov_ref.max_depth, c->stream); const uint32_t nf = t.nf, D = t.D; const size_t row = (size_t)D + 1, nc = COV_REF_CN + 1u;
+        uint64_t inserted = 0; for (const LiftSeg& sg : c->lift.segs) if (sg.kind != 0u) inserted += sg.len;
+        FILE* o = fopen(path, "w");
+        if (!o) throw ScsError(SCS_EIO, fn + ": can not open " + path + ": " + strerror(errno));
+        auto name = [&](uint32_t r) { return r < nf ? c->lift.ref_names[r].c_str() : "genome"; };
+        auto size = [&](uint32_t r) { uint64_t n = 0; for (size_t k = 0; k < row; ++k) n += t.hist[r * row + k]; return n; };   // the non-N bases, the absent ones among them
+        bool okw = fprintf(o, "#coverage\tmax_depth=%u\tthe last bucket (depth %u) counts depth >= %u; gini takes it at its mean depth: exact when it is empty, a lower bound otherwise\n", D, D, D) > 0 &&
+                   fputs("#summary\trecord\tbases\tn_bases\tabsent\taligned\tmean\tbreadth1\tbreadth5\tbreadth10\tbreadth20\tgini\n", o) != EOF;
+        for (uint32_t r = 0; r <= nf && okw; ++r) {
+            const CovStats s = cov_stats(t.hist.data() + r * row, D, t.sum[r]);
+            okw = fprintf(o, "#s\t%s\t%llu\t%llu\t%llu\t%llu\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\t%.10g\n", name(r), (unsigned long long)(size(r) + t.n_n[r]), (unsigned long long)t.n_n[r], (unsigned long long)t.absent[r],
+                          (unsigned long long)(t.sum[r] + t.sum_n[r]), s.mean, s.breadth[0], s.breadth[1], s.breadth[2], s.breadth[3], s.gini) > 0;
+        }
+        if (okw) okw = fputs("#cn\trecord\tcopies\tbases\taligned\tmean\n", o) != EOF;
+        for (uint32_t r = 0; r <= nf && okw; ++r)
+            for (size_t k = 0; k < nc && okw; ++k) {
+                const uint64_t b = t.cn_bases[r * nc + k], a = t.cn_sum[r * nc + k];
+                if (b) okw = fprintf(o, "#c\t%s\t%llu\t%llu\t%llu\t%.10g\n", name(r), (unsigned long long)k, (unsigned long long)b, (unsigned long long)a, (double)a / (double)b) > 0;
+            }
+        if (okw) okw = fprintf(o, "#unlifted\t%llu\t%llu\n", (unsigned long long)t.unlifted, (unsigned long long)inserted) > 0;
+        if (okw) okw = fputs("#record\tdepth\tcount\tsize\tfraction\n", o) != EOF;
+        for (uint32_t r = 0; r <= nf && okw; ++r) {
+            const uint64_t n = size(r);
+            for (size_t k = 0; k < row && okw; ++k)
+                if (t.hist[r * row + k]) okw = fprintf(o, "%s\t%llu\t%llu\t%llu\t%.10g\n", name(r), (unsigned long long)k, (unsigned long long)t.hist[r * row + k], (unsigned long long)n, (double)t.hist[r * row + k] / (double)n) > 0;
+        }
+        if (fclose(o) != 0 || !okw) throw ScsError(SCS_EIO, fn + ": writing " + path + " failed");
+    });
+}
+
+int scs_coverage_ref_kernel_time(const scs_ctx* c, int which, uint64_t* launches, double* ms, uint64_t* units) {
+    if (which != 0 && which != 1) return SCS_EINVAL;
+    return kernel_time_of(c, which ? &scs_ctx::tm_cov_ref_finish : &scs_ctx::tm_cov_ref_copies, launches, ms, units);
+}
+
+// device test seam: the kernels of the profile on the reference alone (launch_cov_ref_copies, launch_cov_ref_finish: what the
+// product launches) over a caller's staged depths, codes and table, on the ctx's stream and flags word.  Rows are the reference
+// records' (no genome row); any output may be NULL
+int scs_coverage_ref_finish_probe(scs_ctx* c, const uint32_t* depth, const uint8_t* codes, uint64_t n_staged,
+                                  const uint64_t* seg_hap_off, const uint64_t* seg_len, const uint64_t* seg_ref_pos, const uint32_t* seg_ref_rec, const uint32_t* seg_kind, uint32_t n_seg,
+                                  const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, uint32_t max_depth, int lds_buckets,
+                                  uint32_t* ref_depth, uint32_t* packed, uint64_t* hist, uint64_t* n_n, uint64_t* absent, uint64_t* sum, uint64_t* sum_n, uint64_t* cn_bases, uint64_t* cn_sum, uint64_t* unlifted) {
+    return guarded(c, [&] {
+        const std::string fn = "scs_coverage_ref_finish_probe";
+        if (!depth || !codes || !n_staged || !n_seg || !seg_hap_off || !seg_len || !seg_ref_pos || !seg_ref_rec || !seg_kind || !hap_lens || !n_hap || !ref_lens || !n_ref || max_depth < 1u || max_depth > COV_MAX_DEPTH)
+            throw ScsError(SCS_EINVAL, fn + ": bad argument");
+        // the table as lift_parse leaves it: segments that ascend, tile the staged genome and straddle no staged record.  Where a
+        // segment lifts to is the kernels' to check
+        std::vector<LiftSeg> segs(n_seg); uint64_t at = 0, rec_end = 0; uint32_t rec = 0;
+        for (uint32_t i = 0; i < n_seg; ++i) {
+            segs[i] = LiftSeg{seg_hap_off[i], seg_len[i], seg_ref_pos[i], seg_ref_rec[i], seg_kind[i]};
+            while (rec < n_hap && at == rec_end) rec_end += hap_lens[rec++];
+            if (seg_hap_off[i] != at || !seg_len[i] || seg_len[i] > rec_end - at || seg_kind[i] > 1u) throw ScsError(SCS_EINVAL, fn + ": the segments do not tile the staged records");
+            at += seg_len[i];
+        }
+        while (rec < n_hap && at == rec_end) rec_end += hap_lens[rec++];
+        if (at != n_staged || rec != n_hap || rec_end != n_staged) throw ScsError(SCS_EINVAL, fn + ": the segments do not tile the staged records");
+        ref_copies_fit(segs.data(), segs.size());
+        const hipStream_t s = c->stream; CovRefTrack R; DevBuf d_depth, d_codes, d_segs;
+        ref_reserve(R, std::vector<uint64_t>(ref_lens, ref_lens + n_ref), max_depth, n_staged, s);
+        d_depth.reserve((size_t)n_staged * 4, s); d_codes.reserve(std::max<size_t>(n_staged, 16), s); upload(d_segs, segs, s);
+        HIP_OK(hipMemcpyAsync(d_depth.p, depth, (size_t)n_staged * 4, hipMemcpyHostToDevice, s)); HIP_OK(hipMemcpyAsync(d_codes.p, codes, n_staged, hipMemcpyHostToDevice, s));
+        ref_zero(R, max_depth, true, s);
+        const CovRefArgs a = ref_args(R, max_depth, d_segs.as<LiftSeg>(), n_seg, d_depth.as<uint32_t>(), d_codes.as<uint8_t>(), n_staged, lds_buckets < 0 ? COV_LDS_BUCKETS : (uint32_t)lds_buckets, c->flags.as<uint32_t>());
+        launch_cov_ref_copies(s, a);
+        launch_cov_ref_finish(s, a);
+        check_flags(c);                                                            // (waits for the kernels; FLAG_LIFT's error where a segment lifts outside its reference record)
+        const RefTables t = ref_tables(R, max_depth, s);
+        uint64_t staged = 0; for (uint64_t i = 0; i < n_staged; ++i) staged += depth[i];
+        ref_identity(t, staged);
+        const RefTab w(n_ref, max_depth); const size_t nf = n_ref;
+        if (ref_depth && R.bases) HIP_OK(hipMemcpyAsync(ref_depth, R.depth.p, (size_t)R.bases * 4, hipMemcpyDeviceToHost, s));
+        if (packed && R.bases) HIP_OK(hipMemcpyAsync(packed, R.packed.p, (size_t)R.bases * 4, hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        if (hist) std::copy(t.hist.begin(), t.hist.begin() + nf * w.row, hist);
+        if (n_n) std::copy(t.n_n.begin(), t.n_n.begin() + nf, n_n);
+        if (absent) std::copy(t.absent.begin(), t.absent.begin() + nf, absent);
+        if (sum) std::copy(t.sum.begin(), t.sum.begin() + nf, sum);
+        if (sum_n) std::copy(t.sum_n.begin(), t.sum_n.begin() + nf, sum_n);
+        if (cn_bases) std::copy(t.cn_bases.begin(), t.cn_bases.begin() + nf * w.nc, cn_bases);
+        if (cn_sum) std::copy(t.cn_sum.begin(), t.cn_sum.begin() + nf * w.nc, cn_sum);
+        if (unlifted) *unlifted = t.unlifted;
+    });
 }
 
 }  // extern "C"

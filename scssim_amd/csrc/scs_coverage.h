@@ -17,6 +17,8 @@ namespace scs {
 #define COV_TILE 4096u                                     // entries of the difference array per workgroup of the end-of-job pass
 #define COV_CHUNK 1024u                                    // tile sums per step of the one-workgroup offset scan
 #define COV_LDS_BUCKETS 4096u                              // a workgroup's LDS histogram holds min(max_depth + 1, this) buckets
+#define COV_REF_CN 16u                                     // on the reference (scs_set_coverage_ref): depth by copy number 0 .. this, the last one copies >= this
+#define COV_REF_MAX_COPIES 65535u                          // ... and the staged bases that may lift to one reference base (16 bits of its packed word)
 
 // What a placed read (truth_place has run) marks: mark(g, +1), mark(g + l, -1) for every maximal run [g, g + l) of genome bases
 // aligned to read bases, g a global genome index.  M runs that only an insertion separates are one run (an I moves nothing on the

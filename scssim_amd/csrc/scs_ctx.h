@@ -64,6 +64,7 @@ struct DevBuf {
     void* p = nullptr; LiveBytes cap;        // cap: usable (mapped) bytes
     DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete; ~DevBuf() { release(); }
     size_t va = 0;                           // reserved address range in bytes (0: plain hipMalloc block)
+    bool plain = false;                      // true: always a plain hipMalloc block, whatever its size (an array of a fixed size has no use for growing in place)
     // equal-sized chunks: on ROCm 7.2 hipMemSetAccess rejects a chunk mapped right behind one of a different size (probed)
     static constexpr size_t kRange = 384ull << 30, kGran = 128ull << 20;
     static size_t virtual_from() {           // SCS_VMM_FROM_MB: tests lower it so that small jobs run on mapped buffers too
@@ -91,7 +92,7 @@ struct DevBuf {
         // must be copied is, mapped tens of GB in the middle of a job whose amplicon count came out 0.01 % above the last one's)
         size_t ncap = va ? bytes + bytes / 32 : std::max(bytes, cap + cap / 2);
         if (va) { map_more(std::min((ncap + kGran - 1) / kGran * kGran, va)); if (bytes > cap) throw ScsError(SCS_EOVERFLOW, "device buffer larger than its address range"); return; }
-        if (ncap > virtual_from() && virtual_ok()) {
+        if (!plain && ncap > virtual_from() && virtual_ok()) {
             void* base = nullptr;
             if (hipMemAddressReserve(&base, kRange, kGran, nullptr, 0) == hipSuccess) {
                 void* old = p; const size_t old_cap = cap;
@@ -205,7 +206,16 @@ struct DepthTrack { uint32_t width = 0; uint64_t bins = 0; bool valid = false; D
 // runs); the difference array of the running yield call, the per-base depths once it has finished (bases + 1 int32, padded to
 // whole tiles, zeroed on the ctx stream at the start of every call; valid: a call with it on has finished); the tables of the
 // last call -- hist[n_rec][max_depth + 1], n_bases, sum, sum_n [n_rec], all uint64 --, the kernels' record starts and tile sums
-struct CovTrack { uint32_t max_depth = 0, n_rec = 0; uint64_t bases = 0; bool valid = false; DevBuf diff, tab, rec, tiles; };
+// (run_depth: the max_depth the array's last end-of-job pass ran with -- max_depth, or 1 for tables kept private when only the
+// profile on the reference asked for the array)
+struct CovTrack { uint32_t max_depth = 0, n_rec = 0, run_depth = 0; uint64_t bases = 0; bool valid = false; DevBuf diff, tab, rec, tiles; };
+// The coverage profile on the reference (scs_set_coverage_ref; scs_coverage.cpp): max_depth (0: off -- no
+// buffer of it exists, no code of it runs); per reference base of the lift table the depth of the last yield call (uint32, padded
+// to whole tiles, zeroed on the ctx stream at the start of every call) and the packed copies | n_copies << 16 (made once per
+// genome and table: `copies` says that they stand); the tables of the last call (uint64: hist[n_ref][max_depth + 1], n_bases,
+// absent, sum, sum_n [n_ref], cn_bases, cn_sum [n_ref][17], unlifted) and the reference record starts; unlifted: the last call's
+// (the two per-base arrays are plain blocks: their size is the reference's, they never grow)
+struct CovRefTrack { uint32_t max_depth = 0, n_ref = 0; uint64_t bases = 0, unlifted = 0; bool valid = false, copies = false; DevBuf depth, packed, tab, rec; CovRefTrack() { depth.plain = packed.plain = true; } };
 enum { TM_ERRSCAN,TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
 struct SinkPipe;             // scs_sink.h
@@ -276,6 +286,9 @@ struct scs_ctx {
     // coverage profile (scs_set_coverage; scs_coverage.cpp)
     CovTrack cov;
     KernelTimer tm_cov_mark{"k_cov_mark"}, tm_cov_finish{"k_cov_finish"};   // the last yield call's per-batch marks and its end-of-job pass (scs_coverage_kernel_time; not of tm[])
+    // coverage profile on the reference (scs_set_coverage_ref; scs_coverage.cpp)
+    CovRefTrack cov_ref;
+    KernelTimer tm_cov_ref_copies{"k_cov_ref_copies"}, tm_cov_ref_finish{"k_cov_ref_finish"};   // the once-per-layout kernel and the end-of-job lift and count (scs_coverage_ref_kernel_time)
     // lift table (scs_lift.cpp): the staged records as stretches of the original reference -- kept by scs_simuvars
     // or read by scs_load_lift, on the host and (d_lift: the segments) on the device; tied to the staged genome: staging another drops it.
     // Depth by reference bin (scs_set_depth_ref; scs_depth.cpp): the bins of the reference records; counters reads, bases, copies of
@@ -353,7 +366,7 @@ struct scs_ctx {
     scs_stats st{};
     KernelTimer tm[TM_COUNT] = {{"k_errs<semi->full>"}, {"k_errs<frag->semi>"}, {"k_reads"}, {"k_attach<semi>"}, {"k_indels"}, {"k_attach<frag>"}, {"k_truth"}, {"k_depth"}};
     // the timers a yield call runs: reset at its start, collected at its end.  A new side output's timer is one more entry here
-    std::array<KernelTimer*, 10> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref, &tm_support_ref_open, &tm_support_ref_gather, &tm_cov_mark, &tm_cov_finish}; }
+    std::array<KernelTimer*, 12> yield_timers() { return {&tm[TM_READS], &tm[TM_INDELS], &tm[TM_TRUTH], &tm[TM_DEPTH], &tm_support, &tm_depth_ref, &tm_support_ref_open, &tm_support_ref_gather, &tm_cov_mark, &tm_cov_finish, &tm_cov_ref_copies, &tm_cov_ref_finish}; }
 
     DevFrags frags_view() const {
         uint8_t* b = df_blob.as<uint8_t>();
@@ -422,6 +435,13 @@ void depth_open(scs_ctx* c, bool on_ref);
 void coverage_check(scs_ctx* c);
 void coverage_open(scs_ctx* c);
 void coverage_finish(scs_ctx* c, uint32_t lds);
+// ... on the reference (scs_set_coverage_ref): coverage_check refuses it too (sharded, or no lift table); coverage_ref_open, after
+// coverage_open: the zeroed reference array and tables, and the packed copies where the genome or the table is new;
+// coverage_ref_finish, after coverage_finish: the staged depths through the table, counted per reference record;
+// coverage_ref_close, once the call's flags are clean: the sum identity (SCS_EOVERFLOW where it does not hold)
+void coverage_ref_open(scs_ctx* c);
+void coverage_ref_finish(scs_ctx* c, uint32_t lds);
+void coverage_ref_close(scs_ctx* c);
 // lift table (scs_lift.cpp): lift_install makes T the ctx's table (host and device), lift_drop forgets it (every call that stages a
 // genome); need_lift refuses (SCS_EINVAL) in fn's name where there is none
 void lift_install(scs_ctx* c, LiftTable&& T);

@@ -300,6 +300,26 @@ uint64_t cov_tiles(uint64_t n_bases);
 void launch_cov_mark(hipStream_t s, const CovArgs& a);
 void launch_cov_finish(hipStream_t s, const CovFinish& f);
 
+// ---- coverage profile on the reference (scs_k_coverage_ref.hip; scs_set_coverage_ref): the staged depths
+// carried through the lift table once, after launch_cov_finish.  ref_off: starts of the reference records (n_ref + 1); ref_depth
+// and packed: one uint32 per reference base each, padded to cov_ref_tiles(n_ref_bases) tiles of COV_TILE; packed = copies |
+// n_copies << 16 (COV_REF_MAX_COPIES: the host refuses a table that could reach beyond it).  launch_cov_ref_copies, once per
+// (genome, table): packed from the table and the genome's codes (>= 4: N).  launch_cov_ref_finish: ref_depth from depth[n_staged]
+// (what launch_cov_finish left where the differences lay), the depths under I segments summed into *unlifted; then the tables
+// per reference record -- hist (n_ref rows of max_depth + 1), n_n / absent / sum / sum_n (n_ref each), cn_bases / cn_sum (n_ref
+// rows of COV_REF_CN + 1); lds as CovFinish's.  FLAG_LIFT: a segment that lifts outside its reference record, or leaves the table
+// (nothing is added for it); FLAG_COVERAGE: depth on a base no staged base lifts to
+struct LiftSeg;
+struct CovRefArgs {
+    const LiftSeg* segs; uint32_t n_seg; const uint64_t* ref_off; uint32_t n_ref; uint64_t n_staged, n_ref_bases;
+    const uint32_t* depth; const uint8_t* codes; uint32_t* ref_depth; uint32_t* packed; uint32_t max_depth, lds;
+    unsigned long long* hist; unsigned long long* n_n; unsigned long long* absent; unsigned long long* sum; unsigned long long* sum_n;
+    unsigned long long* cn_bases; unsigned long long* cn_sum; unsigned long long* unlifted; uint32_t* flags;
+};
+uint64_t cov_ref_tiles(uint64_t n_ref_bases);
+void launch_cov_ref_copies(hipStream_t s, const CovRefArgs& a);
+void launch_cov_ref_finish(hipStream_t s, const CovRefArgs& a);
+
 // ---- lift table (scs_k_lift.hip; scs_lift.h): the staged records as stretches of the original reference.
 // k_depth_lift: the depth track of a batch by REFERENCE bin -- k_depth's placement and LDS table, the bins found through the
 // segment table; bin n_bins collects what has no reference coordinate.  k_lift_copies: per reference bin the haplotype bases

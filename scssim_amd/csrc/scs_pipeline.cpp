@@ -49,9 +49,9 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_DEPTH) m += " depth track (a read with more than 32 indel events, pair flags that are not a strand, or a read placed outside its record)";
         if (f & FLAG_AMP) m += " amplicon table (a lineage that does not fit its parents, view flags that are not a strand, an amplicon outside its record, or a line the two passes size differently)";
         if (f & FLAG_SITE) m += " artefact table (an amplicon that cannot be placed, a slab whose entries differ from their count, site counts that contradict each other, or a line the two passes size differently)";
-        if (f & FLAG_LIFT) m += " depth by reference bin / truth SAM on the reference (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand; artefact table on the reference: an amplicon whose walk leaves the lift table or its record's segments, or a segment that lifts outside its reference record)";
+        if (f & FLAG_LIFT) m += " depth by reference bin / truth SAM on the reference (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand; artefact table on the reference: an amplicon whose walk leaves the lift table or its record's segments, or a segment that lifts outside its reference record; coverage profile on the reference: a segment that lifts outside its reference record, or a staged base the table does not hold)";
         if (f & FLAG_SUPPORT) m += " site support (a read placed outside its record, pair flags that are not a strand, a read with more than 32 indel events, a FASTQ record that is not where the offsets say, or sites that are not in order" + std::string(c->support_ref ? "; on the reference: staged positions that do not ascend, or a reference counter past 2^32 - 1" : "") + ")";
-        if (f & FLAG_COVERAGE) m += " coverage profile (a read placed outside its record, a read with more than 32 indel events, pair flags that are not a strand, a negative running depth, or a depth that is not 0 behind the genome's last base)";
+        if (f & FLAG_COVERAGE) m += " coverage profile (a read placed outside its record, a read with more than 32 indel events, pair flags that are not a strand, a negative running depth, or a depth that is not 0 behind the genome's last base; on the reference: depth on a base no staged base lifts to)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }
@@ -91,7 +91,7 @@ int scs_create(const scs_config* cfg, scs_ctx** out) {
         if (cfg->stream) c->stream.adopt((hipStream_t)cfg->stream); else c->stream.ensure(hipStreamNonBlocking);
         c->key = RngKey{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32)};
         for (KernelTimer& t : c->tm) t.gate = &c->timing_gate;
-        c->tm_support.gate = &c->timing_gate; c->tm_depth_ref.gate = &c->timing_gate; c->tm_support_ref_open.gate = &c->timing_gate; c->tm_support_ref_gather.gate = &c->timing_gate; c->tm_cov_mark.gate = &c->timing_gate; c->tm_cov_finish.gate = &c->timing_gate;
+        c->tm_support.gate = &c->timing_gate; c->tm_depth_ref.gate = &c->timing_gate; c->tm_support_ref_open.gate = &c->timing_gate; c->tm_support_ref_gather.gate = &c->timing_gate; c->tm_cov_mark.gate = &c->timing_gate; c->tm_cov_finish.gate = &c->timing_gate; c->tm_cov_ref_copies.gate = &c->timing_gate; c->tm_cov_ref_finish.gate = &c->timing_gate;
         c->flags.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->flags.p, 0, 256, c->stream));
         c->dsums.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->dsums.p, 0, 256, c->stream));
         c->d_tot.reserve(256, c->stream);

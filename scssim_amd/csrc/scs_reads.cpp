@@ -149,7 +149,7 @@ struct PipeGuard { SinkPipe* p; ~PipeGuard() { if (p) (void)p->finish(); } };
 struct Yield {               // the state of one do_yield call
     scs_ctx* const c; const OutTarget& tg;
     const hipStream_t s = c->stream; hipStream_t ps = s; const int paired = c->cfg.paired != 0; const uint64_t P = c->n_pairs_planned; const uint32_t L = (uint32_t)c->prof.read_length, slot = ((L + 64 + 63) / 64) * 64;
-    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth.width != 0, depth_ref = c->depth_ref.width != 0, support = c->support_on, coverage = c->cov.max_depth != 0; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
+    const bool to_sink = !tg.device && tg.sink, truth = !c->truth_path.empty(), bam = truth && c->truth_bam, tref = truth && c->truth_ref, bgzf = to_sink && tg.bgzf, depth = c->depth.width != 0, depth_ref = c->depth_ref.width != 0, support = c->support_on, coverage = c->cov.max_depth != 0, coverage_ref = c->cov_ref.max_depth != 0, cov_array = coverage || coverage_ref; const std::string tname = bam ? "truth BAM" : tref ? "truth SAM on the reference" : "truth SAM";
     BatchPlan plan; std::vector<uint32_t> bounds; BatchSet bs[2]; ReadsJob job;
     uint64_t tot[2] = {0, 0}, sunk[2] = {0, 0}, bi = 0;                           // sunk: bytes handed to the sink (= the text's, or its BGZF blocks'); bi: batches handed to the sink so far
     bool d2h_rec[2] = {false, false}, free_rec[2] = {false, false}; Ship pending{}; bool have_pending = false;
@@ -224,7 +224,9 @@ struct Yield {               // the state of one do_yield call
     }
     void coverage_open() {
         // this call's difference array and tables, zeroed on the ctx stream, and the kernels' record starts (scs_coverage.cpp)
+        // (the profile on the reference needs the same array: one array and one k_cov_mark launch per batch whichever switches are on)
         scs::coverage_open(c);
+        if (coverage_ref) scs::coverage_ref_open(c);
         ca.rec_off = c->cov.rec.as<uint64_t>(); ca.n_rec = c->cov.n_rec; ca.diff = c->cov.diff.as<int32_t>();
         place_job(ca);
     }
@@ -241,7 +243,7 @@ struct Yield {               // the state of one do_yield call
         if (depth) depth_open();
         if (depth_ref) depth_ref_open();
         if (support) support_open();
-        if (coverage) coverage_open();
+        if (cov_array) coverage_open();
         if (to_sink) {
             if (!c->pipe) c->pipe.reset(new SinkPipe);
             c->copy_stream.ensure(hipStreamNonBlocking); for (int k = 0; k < 2; ++k) { c->ev_made[k].ensure(hipEventDisableTiming); c->ev_d2h[k].ensure(hipEventDisableTiming); }
@@ -415,7 +417,9 @@ struct Yield {               // the state of one do_yield call
     }
     void coverage_finish() {
         // after the last batch: the differences become depths, counted per record (three kernels on the ctx stream, scs_k_coverage.hip)
-        scs::coverage_finish(c, seam_u32("SCS_TEST_COV_LDS", COV_LDS_BUCKETS));   // (read at every call: the legs of one test job differ in it)
+        const uint32_t lds = seam_u32("SCS_TEST_COV_LDS", COV_LDS_BUCKETS);      // (read at every call: the legs of one test job differ in it)
+        scs::coverage_finish(c, lds);
+        if (coverage_ref) scs::coverage_ref_finish(c, lds);                        // the staged depths through the lift table, counted per reference record
     }
     void ship(Ship sh) {                                                           // D2H on the copy stream into a free pinned slot, then to the region's writer
         if (bgzf || (bam && sh.p[2])) HIP_OK(hipEventSynchronize(c->ev_z[sh.dsl]));   // the blocks' totals have arrived
@@ -460,10 +464,11 @@ struct Yield {               // the state of one do_yield call
         if (to_sink) { HIP_OK(hipStreamSynchronize(c->copy_stream)); guard.p = nullptr; const bool ok = c->pipe->finish(); c->pipe->truth_fd = -1; if (!ok) throw ScsError(SCS_EIO, truth ? "sink aborted (or the " + tname + " could not be written)" : std::string("sink aborted")); }
         if (truth) { truth_fd.finish("closing"); c->truth_bytes = truth_fd.total; }   // (BAM: the end-of-file block first)
         mail_wait(c); flags_eval(c);
+        if (coverage_ref) coverage_ref_close(c);                                   // the sum identity: the net under a uint32 wrap of a reference base's depth
         if (c->want_cks && !tg.device && plan.nbatch) { c->cks.assign((size_t)plan.nbatch * 2, 0); HIP_OK(hipMemcpyAsync(c->cks.data(), c->d_cks.p, (size_t)plan.nbatch * 16, hipMemcpyDeviceToHost, s)); HIP_OK(hipStreamSynchronize(s)); }
         const uint64_t pairs_written = P - c->h_rb[2];
         for (KernelTimer* t : c->yield_timers()) t->collect();
-        c->depth.valid = depth; c->support_valid = support; c->depth_ref.valid = depth_ref; c->cov.valid = coverage;
+        c->depth.valid = depth; c->support_valid = support; c->depth_ref.valid = depth_ref; c->cov.valid = coverage; c->cov_ref.valid = coverage_ref;
         c->st.pairs_written = pairs_written; c->st.reads_written = paired ? 2 * pairs_written : pairs_written;
         for (int m = 0; m < 2; ++m) { c->st.fastq_bytes[m] = tot[m]; c->st.sink_bytes[m] = to_sink ? sunk[m] : 0; }
         // 1526 B per created amplicon + per pair (insert size + FASTQ bytes of both records)
@@ -482,7 +487,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     if (c->cfg.verbose) fprintf(stderr, "\n*****Producing reads*****\n");
     c->timing_gate = (c->yield_calls++ % c->timing_every) == 0;
     for (KernelTimer* t : c->yield_timers()) t->reset();
-    c->depth.valid = false; c->support_valid = false; c->depth_ref.valid = false; c->cov.valid = false;
+    c->depth.valid = false; c->support_valid = false; c->depth_ref.valid = false; c->cov.valid = false; c->cov_ref.valid = false;
     depth_yield_check(c);                                  // more than 2^27 bins, no lift table: refused before any GPU work
     // A paired-end job on a model whose [Insert Size Standard Deviation] is 0 has no insert-size alphabet (Profile.cpp:908: built only when
     // stdISize > 0); the reference's first yieldInsertSize then asks its Config for a parameter that does not exist and exit(1)s
@@ -515,7 +520,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
         if (y.depth) y.depth_batch(b);
         if (y.depth_ref) y.depth_ref_batch(b);
         if (y.support) y.support_batch(b);
-        if (y.coverage) y.coverage_batch(b);
+        if (y.cov_array) y.coverage_batch(b);
         if (y.ps != s) { HIP_OK(hipEventRecord(c->ev_free[b.k], s)); y.free_rec[b.k] = true; }   // this batch's buffer set is free for the pre-pass after next
         { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("k_reads launch failed: ") + hipGetErrorString(le)); }
         if (y.to_sink) y.sink_batch(b);                                            // BGZF where asked; then to the region's writer (with BGZF: the batch before)
@@ -523,7 +528,7 @@ void do_yield(scs_ctx* c, const OutTarget& tg, uint64_t* n1_out, uint64_t* n2_ou
     }
     if (y.have_pending) y.ship(y.pending);
     if (y.support) support_close(c);                                               // (the table on the reference: the staged counters summed by reference position)
-    if (y.coverage) y.coverage_finish();                                           // (the per-base depths and their histogram, before the call's last synchronise)
+    if (y.cov_array) y.coverage_finish();                                          // (the per-base depths and their histogram, before the call's last synchronise)
     y.finish(n1_out, n2_out, pairs_out);
 }
 
