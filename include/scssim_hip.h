@@ -411,6 +411,43 @@ int         scs_coverage_ref_finish_probe(scs_ctx* ctx, const uint32_t* depth, c
                                           const uint64_t* hap_lens, uint32_t n_hap, const uint64_t* ref_lens, uint32_t n_ref, uint32_t max_depth, int lds_buckets,
                                           uint32_t* ref_depth, uint32_t* packed, uint64_t* hist, uint64_t* n_n, uint64_t* absent, uint64_t* sum, uint64_t* sum_n,
                                           uint64_t* cn_bases, uint64_t* cn_sum, uint64_t* unlifted);
+/* ---- the per-base arrays as bedGraph: depth and true copy number as files a genome browser and bedtools read ---------------
+ * After a yield call the device holds three per-base uint32 arrays: the staged depths (scs_set_coverage), the reference depths and
+ * the per-base true copy number of the reference (scs_set_coverage_ref: the packed word's lower 16 bits).  Each write call below
+ * encodes one of them on the GPU as plain bedGraph: lines "name\tstart\tend\tvalue\n", 0-based and half-open, no `track` line, no
+ * header; one line per maximal run of equal value inside a record, runs of value 0 included (`bedtools genomecov -bga`), so the
+ * lines of a record tile it exactly -- the first starts at 0, consecutive lines abut, the last ends at the record's length,
+ * neighbouring lines of one record differ in value -- and a run never crosses a record border, even between equal values.
+ * Records in staged (reference) order; N bases carry their depth like any base; values are exact, never clamped by max_depth.
+ * The value is compared and printed under a mask (0xFFFFFFFF for depths, 0xFFFF for copies: neighbours that differ only in the
+ * packed word's upper half are one run).  A path ending in .gz is written in BGZF made on the GPU, ending with BGZF's end-of-file
+ * block.  lines / text_bytes (either may be NULL): the lines written and their uncompressed bytes.
+ * scs_write_coverage_bedgraph: the staged depths under the staged record names; needs a finished yield call with scs_set_coverage
+ * on (else SCS_EINVAL, as scs_write_coverage).  scs_write_coverage_ref_bedgraph: the reference depths under the lift table's
+ * reference names; scs_write_copy_number_ref: the staged bases that lift to each reference base (copy number 0 on every haplotype
+ * is a run of 0); both need scs_set_coverage_ref and the lift table, as scs_write_coverage_ref.
+ * The calls synchronise the ctx stream themselves, only read the arrays and may be repeated after one yield: identical files.
+ * Device memory for text is bounded by a cap (128 MB) that does not depend on the genome: the tiles of the array are cut into
+ * slabs whose text fits it, each slab is sized, scanned, formatted, compressed where asked, copied through pinned memory and
+ * written.  The writer's buffers belong to the ctx: kept for the next write, released with it or when both coverage switches are
+ * off.  Errors: an unwritable path is SCS_EIO before any GPU work and the ctx stays usable; text that would leave its plan
+ * raises a device flag and fails the call (SCS_EOVERFLOW), never a wrong file; a tile (4096 bases) whose text alone exceeds the
+ * cap, or a record name beyond 65535 bytes, is SCS_EINVAL stating the bytes.  One GPU.
+ * scs_coverage_bedgraph_kernel_time: the writer's kernels (plan passes, per slab scan, emit and BGZF) in the last write call,
+ * units = bases; not part of scs_kernel_time's table.
+ * Test seams.  scs_runs_probe (needs the GPU): the same kernels and the same slab loop over a caller's values[n] under mask, records
+ * of rec_lens[n_rec] (adding up to n) named names[n_rec]; text_cap: the cap in bytes (0: the product's); bgzf != 0: BGZF blocks
+ * and the end-of-file block.  out[out_cap] gets the bytes a file would hold, *n_out their number (SCS_EOVERFLOW when out_cap is
+ * too small, *n_out set), *lines the lines, *slabs the slabs written; a cap below one tile's text is SCS_EINVAL and the ctx stays
+ * usable.  scs_runs_line_probe (host only): one line through the formatter the sizing and emit kernels run; *n_out = its bytes
+ * (SCS_EOVERFLOW when cap is too small, *n_out set, out not to be trusted). */
+int         scs_write_coverage_bedgraph(scs_ctx* ctx, const char* path, uint64_t* lines, uint64_t* text_bytes);
+int         scs_write_coverage_ref_bedgraph(scs_ctx* ctx, const char* path, uint64_t* lines, uint64_t* text_bytes);
+int         scs_write_copy_number_ref(scs_ctx* ctx, const char* path, uint64_t* lines, uint64_t* text_bytes);
+int         scs_coverage_bedgraph_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+int         scs_runs_probe(scs_ctx* ctx, const uint32_t* values, uint64_t n, uint32_t mask, const uint64_t* rec_lens, uint32_t n_records, const char* const* names,
+                           uint64_t text_cap, int bgzf, char* out, uint64_t out_cap, uint64_t* n_out, uint64_t* lines, uint64_t* slabs);
+int         scs_runs_line_probe(const char* name, uint64_t start, uint64_t end, uint32_t value, char* out, uint64_t cap, uint64_t* n_out);
 /* ---- lift table and depth by reference bin: the job in the coordinates of the original reference ---------------------------
  * Every other truth product lives in the coordinates of the staged haplotype records.  The lift table maps them to the reference
  * `simuvars` built them from: segments that ascend and tile the staged genome, none straddling two staged records, each `len`

@@ -490,6 +490,46 @@ def coverage_ref_finish_probe(ctx, depth, codes, segs, hap_lens, ref_lens, max_d
     return out
 
 
+def runs_line_probe(name, start, end, value, cap=None):
+    """Host-only: one bedGraph line `name\\tstart\\tend\\tvalue\\n` as bytes, through the formatter the bedGraph writer's sizing and
+    emit kernels run.  cap: room in bytes (None: enough); too little raises ScsError (SCS_EOVERFLOW) whose `needed` is the line's size."""
+    L = load_library()
+    L.scs_runs_line_probe.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    nm = name if isinstance(name, bytes) else name.encode()
+    room = len(nm) + 64 if cap is None else int(cap)
+    buf, n = C.create_string_buffer(max(1, room)), C.c_uint64()
+    rc = L.scs_runs_line_probe(nm, int(start), int(end), int(value), buf, room, C.byref(n))
+    if rc:
+        e = ScsError(rc, "scs_runs_line_probe: the line has %d bytes, room for %d" % (n.value, room))
+        e.needed = n.value
+        raise e
+    return buf.raw[:n.value]
+
+
+def runs_probe(ctx, values, mask, rec_lens, names, text_cap=0, bgzf=False):
+    """Needs the GPU: the bedGraph writer's kernels and slab loop, as the product runs them, over values (uint32[n]) compared and
+    printed under `mask`, records of rec_lens (adding up to n) named `names`, on the GenReads `ctx`.  text_cap: bytes of text a slab
+    may hold (0: the product's); bgzf: BGZF blocks with the end-of-file block.  Returns dict(data=bytes a file would hold, lines=,
+    slabs=).  A cap below one tile's text raises ScsError (SCS_EINVAL) and leaves the ctx usable."""
+    import numpy as np
+    v, ln = np.ascontiguousarray(values, np.uint32), np.ascontiguousarray(rec_lens, np.uint64)
+    nm = [s if isinstance(s, bytes) else s.encode() for s in names]
+    if len(nm) != ln.size:
+        raise ValueError("one name per record")
+    arr = (C.c_char_p * max(1, len(nm)))(*nm)
+    fn = ctx._L.scs_runs_probe
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64] + [C.POINTER(C.c_uint64)] * 3
+    n_out, lines, slabs = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    args = (ctx._ctx, v.ctypes.data, v.size, int(mask), ln.ctypes.data, ln.size, arr, int(text_cap), int(bool(bgzf)))
+    rc = fn(*args, None, 0, C.byref(n_out), C.byref(lines), C.byref(slabs))            # sizes first, then the bytes
+    if rc != SCS_EOVERFLOW or not n_out.value:
+        ctx._ck(rc)
+        return dict(data=b"", lines=lines.value, slabs=slabs.value)
+    buf = np.zeros(n_out.value, np.uint8)
+    ctx._ck(fn(*args, buf.ctypes.data, buf.size, C.byref(n_out), C.byref(lines), C.byref(slabs)))
+    return dict(data=buf[:n_out.value].tobytes(), lines=lines.value, slabs=slabs.value)
+
+
 class LiftTable:
     """A lift table as numpy arrays: per segment hap_off (global staged index), len, ref_pos, ref_rec, kind (0: R, 1: I); the
     reference records' and the staged records' names and lengths."""
@@ -1206,6 +1246,37 @@ class GenReads:
         fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
         self._ck(fn(self._ctx, int(which), C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def _write_bedgraph(self, name, path):
+        fn = getattr(self._L, name)
+        fn.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lines, text = C.c_uint64(), C.c_uint64()
+        self._ck(fn(self._ctx, os.fsencode(path), C.byref(lines), C.byref(text)))
+        return dict(lines=lines.value, text_bytes=text.value)
+
+    def write_coverage_bedgraph(self, path):
+        """The per-base depth of the staged genome after the last yield call (set_coverage on) as bedGraph, encoded on the GPU: one
+        line `name start end depth` per maximal run of equal depth inside a record, depth 0 included (`bedtools genomecov -bga`).
+        A path ending in .gz is written in BGZF.  Returns dict(lines=, text_bytes=) (uncompressed); may be repeated."""
+        return self._write_bedgraph("scs_write_coverage_bedgraph", path)
+
+    def write_coverage_ref_bedgraph(self, path):
+        """The same for the per-base depth of the original reference (set_coverage_ref on, a lift table), under the reference's
+        record names."""
+        return self._write_bedgraph("scs_write_coverage_ref_bedgraph", path)
+
+    def write_copy_number_ref(self, path):
+        """The per-base true copy number of the original reference as bedGraph: per maximal segment the staged bases that lift to
+        each of its bases, 0 where every haplotype lost it (set_coverage_ref on, a lift table)."""
+        return self._write_bedgraph("scs_write_copy_number_ref", path)
+
+    def coverage_bedgraph_kernel_time(self):
+        """Event pairs, milliseconds and units (bases) of the bedGraph writer's kernels in the last write call."""
+        fn = self._L.scs_coverage_bedgraph_kernel_time
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
         return dict(launches=n.value, ms=ms.value, units=u.value)
 
     def amplicon_places(self):

@@ -195,7 +195,7 @@ int scs_set_coverage(scs_ctx* c, uint32_t max_depth) {
         HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's arrays go: nothing may still read them
         T.tab.release(); T.valid = false; T.max_depth = max_depth;
         if (!c->cov_ref.max_depth) { T.diff.release(); T.rec.release(); T.tiles.release(); T.bases = 0; T.n_rec = 0; }   // (the array does not depend on max_depth: it stays while the profile on the reference, which reads it, is on)
-        if (!max_depth && !c->cov_ref.max_depth) for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish}) { t->ev.clear(); t->used = 0; t->reset(); }
+        if (!max_depth && !c->cov_ref.max_depth) { for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish, &c->tm_runs}) { t->ev.clear(); t->used = 0; t->reset(); } c->runs.release(); }   // (the bedGraph writer's buffers go with the last array)
     });
 }
 
@@ -258,6 +258,16 @@ int scs_write_coverage(scs_ctx* c, const char* path) {
     });
 }
 
+int scs_write_coverage_bedgraph(scs_ctx* c, const char* path, uint64_t* lines, uint64_t* text_bytes) {
+    return guarded(c, [&] {
+        const std::string fn = "scs_write_coverage_bedgraph";
+        if (!path || !*path) throw ScsError(SCS_EINVAL, fn + ": no path");
+        ready(c, fn);
+        std::vector<std::string> names; for (const FastaRecord& r : c->recs) names.push_back(r.name);
+        runs_write_file(c, fn, path, c->cov.diff.as<uint32_t>(), 0xFFFFFFFFu, c->cov.bases, record_starts(c), names, lines, text_bytes);
+    });
+}
+
 int scs_coverage_kernel_time(const scs_ctx* c, int which, uint64_t* launches, double* ms, uint64_t* units) {
     if (which != 0 && which != 1) return SCS_EINVAL;
     return kernel_time_of(c, which ? &scs_ctx::tm_cov_finish : &scs_ctx::tm_cov_mark, launches, ms, units);
@@ -276,7 +286,8 @@ int scs_set_coverage_ref(scs_ctx* c, uint32_t max_depth) {
             if (!c->cov.max_depth) {                                               // the staged array was this switch's alone
                 CovTrack& T = c->cov;
                 T.diff.release(); T.tab.release(); T.rec.release(); T.tiles.release(); T.bases = 0; T.n_rec = 0;
-                for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish}) { t->ev.clear(); t->used = 0; t->reset(); }
+                for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish, &c->tm_runs}) { t->ev.clear(); t->used = 0; t->reset(); }
+                c->runs.release();
             }
         }
     });
@@ -355,6 +366,25 @@ int scs_write_coverage_ref(scs_ctx* c, const char* path) {
         }
         if (fclose(o) != 0 || !okw) throw ScsError(SCS_EIO, fn + ": writing " + path + " failed");
     });
+}
+
+// the reference's two per-base arrays as bedGraph: the depths, or (copies) the packed word's lower half
+static void write_ref_bedgraph(scs_ctx* c, const std::string& fn, const char* path, bool copies, uint64_t* lines, uint64_t* text_bytes) {
+    if (!path || !*path) throw ScsError(SCS_EINVAL, fn + ": no path");
+    ref_ready(c, fn); need_lift(c, fn.c_str());
+    const CovRefTrack& R = c->cov_ref; const std::vector<uint64_t>& lens = c->lift.ref_lens;
+    std::vector<uint64_t> roff(lens.size() + 1, 0);
+    for (size_t r = 0; r < lens.size(); ++r) roff[r + 1] = roff[r] + lens[r];
+    if (lens.size() != R.n_ref || roff[lens.size()] != R.bases || c->lift.ref_names.size() != lens.size()) throw ScsError(SCS_EINVAL, fn + ": the lift table is not the one the arrays were made with");
+    runs_write_file(c, fn, path, copies ? R.packed.as<uint32_t>() : R.depth.as<uint32_t>(), copies ? 0xFFFFu : 0xFFFFFFFFu, R.bases, roff, c->lift.ref_names, lines, text_bytes);
+}
+
+int scs_write_coverage_ref_bedgraph(scs_ctx* c, const char* path, uint64_t* lines, uint64_t* text_bytes) {
+    return guarded(c, [&] { write_ref_bedgraph(c, "scs_write_coverage_ref_bedgraph", path, false, lines, text_bytes); });
+}
+
+int scs_write_copy_number_ref(scs_ctx* c, const char* path, uint64_t* lines, uint64_t* text_bytes) {
+    return guarded(c, [&] { write_ref_bedgraph(c, "scs_write_copy_number_ref", path, true, lines, text_bytes); });
 }
 
 int scs_coverage_ref_kernel_time(const scs_ctx* c, int which, uint64_t* launches, double* ms, uint64_t* units) {

@@ -13,6 +13,7 @@
 #include "scs_truth.h"
 #include "scs_depth.h"
 #include "scs_coverage.h"
+#include "scs_runs.h"
 #include "scs_lift.h"
 #include "scs_outfile.h"
 
@@ -216,6 +217,14 @@ struct CovTrack { uint32_t max_depth = 0, n_rec = 0, run_depth = 0; uint64_t bas
 // absent, sum, sum_n [n_ref], cn_bases, cn_sum [n_ref][17], unlifted) and the reference record starts; unlifted: the last call's
 // (the two per-base arrays are plain blocks: their size is the reference's, they never grow)
 struct CovRefTrack { uint32_t max_depth = 0, n_ref = 0; uint64_t bases = 0, unlifted = 0; bool valid = false, copies = false; DevBuf depth, packed, tab, rec; CovRefTrack() { depth.plain = packed.plain = true; } };
+// What the bedGraph writer of the per-base arrays keeps (scs_write_coverage_bedgraph ...; scs_runs.cpp): per
+// tile the first run start, the next one behind it, lines and bytes; a slab's 64-bit offsets, the scan's scratch, its text (at
+// most the text cap, whatever the genome's size), the BGZF lane over it and the pinned block it crosses to the host through.  Made
+// by the first write call, kept for the next one, released with the ctx or when both coverage switches are off
+struct RunsWork {
+    DevBuf first, next, lines, bytes, offs, scan, text, crc; BgzfLane z; Pinned<char> h_text; Pinned<uint32_t> h_n;
+    void release() { for (DevBuf* b : {&first, &next, &lines, &bytes, &offs, &scan, &text, &crc, &z.plan, &z.sizes, &z.offs, &z.out[0], &z.out[1]}) b->release(); h_text.release(); h_n.release(); }
+};
 enum { TM_ERRSCAN,TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
 struct SinkPipe;             // scs_sink.h
@@ -289,6 +298,9 @@ struct scs_ctx {
     // coverage profile on the reference (scs_set_coverage_ref; scs_coverage.cpp)
     CovRefTrack cov_ref;
     KernelTimer tm_cov_ref_copies{"k_cov_ref_copies"}, tm_cov_ref_finish{"k_cov_ref_finish"};   // the once-per-layout kernel and the end-of-job lift and count (scs_coverage_ref_kernel_time)
+    // the bedGraph files of the three per-base arrays above (scs_runs.cpp)
+    RunsWork runs;
+    KernelTimer tm_runs{"k_runs"};                        // the last bedGraph write call's kernels (scs_coverage_bedgraph_kernel_time; not one of tm[])
     // lift table (scs_lift.cpp): the staged records as stretches of the original reference -- kept by scs_simuvars
     // or read by scs_load_lift, on the host and (d_lift: the segments) on the device; tied to the staged genome: staging another drops it.
     // Depth by reference bin (scs_set_depth_ref; scs_depth.cpp): the bins of the reference records; counters reads, bases, copies of
@@ -454,6 +466,10 @@ void support_open(scs_ctx* c);
 void support_close(scs_ctx* c);
 // "site support (scs_set_site_support)", or the reference table's name: what the yield call's refusals open with
 std::string support_name(const scs_ctx* c);
+// the bedGraph writer (scs_runs.cpp): the run-length text of values[n] under mask -- records of the starts roff (n_rec + 1, the
+// last one n) and names name(r) -- to the file at path (a name ending in .gz: BGZF made on the device); who: the entry point's name
+void runs_write_file(scs_ctx* c, const std::string& who, const char* path, const uint32_t* values, uint32_t mask, uint64_t n, const std::vector<uint64_t>& roff,
+                     const std::vector<std::string>& names, uint64_t* lines, uint64_t* text_bytes);
 std::vector<int> gpu_local_cpus(int device);   // scs_sink.cpp
 
 template <class F>

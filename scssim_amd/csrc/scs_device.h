@@ -99,8 +99,8 @@ struct SegMap { uint32_t n; uint32_t lo[ALLOC_SLOTS], cnt[ALLOC_SLOTS]; unsigned
 
 // error flags raised by kernels (never silent): bit 0 error-list cap, 1 error pool, 2 read slot, 3 other, 5 a truth record that cannot be right,
 // 6 the same for the depth track, 7 for the amplicon table, 8 for the artefact table, 9 for the site support counters, 10 for the
-// depth track by reference bin, 11 for the coverage profile
-enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512, FLAG_LIFT = 1024, FLAG_COVERAGE = 2048 };
+// depth track by reference bin, 11 for the coverage profile, 12 for the run-length text of the per-base arrays (the bedGraph files)
+enum DevFlag : uint32_t { FLAG_ERRCAP = 1, FLAG_ERRPOOL = 2, FLAG_READSLOT = 4, FLAG_INTERNAL = 8, FLAG_KEYSPACE = 16, FLAG_TRUTH = 32, FLAG_DEPTH = 64, FLAG_AMP = 128, FLAG_SITE = 256, FLAG_SUPPORT = 512, FLAG_LIFT = 1024, FLAG_COVERAGE = 2048, FLAG_RUNS = 4096 };
 
 // one planned read pair (or SE read) with its amplicon already resolved to an index map into the genome:
 // U[t] = maybe_comp(G[base + dir*t]) patched by the semi's errors (at t = k1 - pos(e), value comp(alt))

@@ -52,6 +52,7 @@ void flags_eval(scs_ctx* c) {
         if (f & FLAG_LIFT) m += " depth by reference bin / truth SAM on the reference (a read placed outside its record, an aligned run that leaves the lift table, a lifted coordinate outside its reference record, a read with more than 32 indel events, or pair flags that are not a strand; artefact table on the reference: an amplicon whose walk leaves the lift table or its record's segments, or a segment that lifts outside its reference record; coverage profile on the reference: a segment that lifts outside its reference record, or a staged base the table does not hold)";
         if (f & FLAG_SUPPORT) m += " site support (a read placed outside its record, pair flags that are not a strand, a read with more than 32 indel events, a FASTQ record that is not where the offsets say, or sites that are not in order" + std::string(c->support_ref ? "; on the reference: staged positions that do not ascend, or a reference counter past 2^32 - 1" : "") + ")";
         if (f & FLAG_COVERAGE) m += " coverage profile (a read placed outside its record, a read with more than 32 indel events, pair flags that are not a strand, a negative running depth, or a depth that is not 0 behind the genome's last base; on the reference: depth on a base no staged base lifts to)";
+        if (f & FLAG_RUNS) m += " bedGraph text (a line or a tile the sizing pass and the emit pass size differently: the text would overflow its plan)";
         throw ScsError(SCS_EOVERFLOW, m);
     }
 }

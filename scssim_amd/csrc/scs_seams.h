@@ -15,6 +15,7 @@
 //   SCS_TEST_SUPPORT_SLOTS  entries of the site support kernel's LDS table (rounded down to a power of two, at most 1024; 4: it overflows into direct adds, 0: no table)
 //   SCS_TEST_LIFT_SLOTS  entries of k_depth_lift's LDS table (depth by reference bin; as SCS_TEST_DEPTH_SLOTS: 4 overflows, 0: no table)
 //   SCS_TEST_COV_LDS  buckets of the LDS histogram of the coverage profile's end-of-job pass (at most 4096; 4: most depths overflow into direct adds, 0: no table, every count goes to memory; read at every yield call; the count kernel of the profile on the reference, k_cov_ref_hist, reads it too)
+//   SCS_TEST_RUNS_TEXT_CAP  bytes of text a slab of the bedGraph writer holds on the device (scs_runs.cpp; 128 MB unset, at least 1: several slabs in a small job; below one tile's text: the call is refused; read at every write call)
 //   SCS_TEST_FASTA_CHUNK  bytes of the raw FASTA per chunk of the device parser, and of a piece of the slice gather (scs_stage.cpp; 64 MB unset, at least 1: chunk borders behind a line end, in a header, between '\r' and '\n', on a '>')
 // (SCS_ATTACH_GROUPS / SCS_ATTACH_G began as tuning seams; tests/test_gpu_attach.py now runs k_attach<false, 2 / 4 / 8 / 16> through them.)
 #pragma once
