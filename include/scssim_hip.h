@@ -448,6 +448,43 @@ int         scs_coverage_bedgraph_kernel_time(const scs_ctx* ctx, uint64_t* laun
 int         scs_runs_probe(scs_ctx* ctx, const uint32_t* values, uint64_t n, uint32_t mask, const uint64_t* rec_lens, uint32_t n_records, const char* const* names,
                            uint64_t text_cap, int bgzf, char* out, uint64_t out_cap, uint64_t* n_out, uint64_t* lines, uint64_t* slabs);
 int         scs_runs_line_probe(const char* name, uint64_t start, uint64_t end, uint32_t value, char* out, uint64_t cap, uint64_t* n_out);
+/* ---- GC bias: the per-base depth as a function of GC content, the curve Picard's CollectGcBiasMetrics draws -----------------
+ * After a yield call with scs_set_coverage on the device holds the staged depths, the genome's codes and the record starts.  The
+ * calls below make one pass over them, on demand, and count sliding windows by their GC content.
+ * Window: W bases, 1 .. 1024.  For every staged record r of length len and every start p with p + W <= len the window is the W
+ * bases [p, p + W) of r: windows slide by one base, never cross a record border, and a record shorter than W has none.
+ * Excluded: a window that holds at least one N base is counted in n_windows[r] and in nothing else.
+ * Bin: a counted window with gc bases of G or C adds to row b = 100 * gc / W (integer division, 0 .. 100): the simulator's own
+ * formula for an amplicon, so row b stands beside gc_means[b] of the loaded profile.  W = 100: b = gc; W < 100: some rows stay
+ * empty.
+ * Tables, per record and one last row `genome` which is the host's sum of the records' rows; all uint64 and exact for every
+ * uint32 depth (a window's sum may pass 2^32): windows[r][b] the counted windows of bin b, depth_sum[r][b] the sum over them of
+ * the sum of depth[g] over the window's W bases, n_windows[r] the excluded windows.  Derived by the host, as doubles:
+ * mean_depth[r][b] = depth_sum / (windows * W); row_mean[r] = sum_b depth_sum / (W * sum_b windows); normalized[r][b] =
+ * mean_depth / row_mean, 0 where row_mean is 0 -- Picard's normalized coverage, on aligned bases instead of read starts.
+ * scs_gc_bias: records + 1 rows (records: scs_coverage_shape), windows and depth_sum row-major with 101 values per row; any
+ * pointer may be NULL.  SCS_EINVAL for a window outside 1 .. 1024 and before a yield call with scs_set_coverage on has finished
+ * (the message names scs_set_coverage; a sharded ctx keeps no array, so its yield call is refused as before); SCS_EOVERFLOW when
+ * cap_rows < records + 1.  It synchronises the ctx stream, may be repeated with any W, and only reads the arrays:
+ * scs_download_coverage and scs_coverage_range answer the same before and after.
+ * scs_write_gc_bias: the table as text written by the host (no .gz):
+ *   "#gc_bias\twindow=W\tstep=1\texcluded=windows_with_N\tbin=100*gc/window"
+ *   "#summary\trecord\twindows\tn_windows\tmean_depth", then "#s\tNAME\t<sum_b windows>\t<n_windows>\t<row_mean>" per record and
+ *   for `genome`
+ *   "#record\tgc\twindows\tdepth_sum\tmean_depth\tnormalized\tmodel", then "NAME\tb\t..." for every b with windows > 0, the
+ *   genome's rows last.  Doubles as %.6f; model = the loaded profile's gc_means[b] as %.6g, `.` when the ctx has no profile.
+ * An unwritable path is SCS_EIO before any GPU work.
+ * scs_gc_bias_kernel_time: the last call's launches, HIP-event milliseconds and units (staged bases); not part of
+ * scs_kernel_time's table.
+ * The table's buffer belongs to the ctx: released with it, when scs_set_coverage goes off and when another genome is staged.
+ * scs_gc_bias_probe (test seam, needs the GPU): the kernel alone, as the product launches it, over depth[n_bases], codes[n_bases]
+ * (0 .. 3 = ACGT, >= 4 = N) and records of rec_lens (adding up to n_bases); lds as scs_coverage_finish_probe's lds_buckets: < 0
+ * the product's choice, 0 no LDS table, every add goes to memory.  n_records rows, no genome row; any output may be NULL. */
+int         scs_gc_bias(scs_ctx* ctx, uint32_t window, uint64_t* windows, uint64_t* depth_sum, uint64_t* n_windows, uint64_t cap_rows);
+int         scs_write_gc_bias(scs_ctx* ctx, const char* path, uint32_t window);
+int         scs_gc_bias_kernel_time(const scs_ctx* ctx, uint64_t* launches, double* ms, uint64_t* units);
+int         scs_gc_bias_probe(scs_ctx* ctx, const uint32_t* depth, const uint8_t* codes, uint64_t n_bases, const uint64_t* rec_lens, uint32_t n_records,
+                              uint32_t window, int lds, uint64_t* windows, uint64_t* depth_sum, uint64_t* n_windows);
 /* ---- lift table and depth by reference bin: the job in the coordinates of the original reference ---------------------------
  * Every other truth product lives in the coordinates of the staged haplotype records.  The lift table maps them to the reference
  * `simuvars` built them from: segments that ascend and tile the staged genome, none straddling two staged records, each `len`

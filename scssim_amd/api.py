@@ -464,6 +464,22 @@ def coverage_finish_probe(ctx, diff, codes, rec_lens, max_depth, lds_buckets=-1)
     return out
 
 
+def gc_bias_probe(ctx, depth, codes, rec_lens, window, lds_buckets=-1):
+    """Needs the GPU: the GC-bias kernel alone, as the product launches it, on the GenReads `ctx`.  depth: uint32[G], codes: uint8[G]
+    (0 .. 3 = ACGT, >= 4 = N), rec_lens adding up to G, window 1 .. 1024; lds_buckets: -1 the product's choice, 0 no LDS table (every
+    add goes to memory).  Returns dict(windows=uint64[records][101], depth_sum=uint64[records][101], n_windows=uint64[records])."""
+    import numpy as np
+    d, cd, ln = np.ascontiguousarray(depth, np.uint32), np.ascontiguousarray(codes, np.uint8), np.ascontiguousarray(rec_lens, np.uint64)
+    G, nr = cd.size, ln.size
+    if d.size != G:
+        raise ValueError("depth and codes have G entries each")
+    out = dict(windows=np.zeros((nr, 101), np.uint64), depth_sum=np.zeros((nr, 101), np.uint64), n_windows=np.zeros(nr, np.uint64))
+    fn = ctx._L.scs_gc_bias_probe
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int] + [C.c_void_p] * 3
+    ctx._ck(fn(ctx._ctx, d.ctypes.data, cd.ctypes.data, G, ln.ctypes.data, nr, int(window), int(lds_buckets), *[out[k].ctypes.data for k in ("windows", "depth_sum", "n_windows")]))
+    return out
+
+
 def coverage_ref_finish_probe(ctx, depth, codes, segs, hap_lens, ref_lens, max_depth, lds_buckets=-1):
     """Needs the GPU: the kernels of the coverage profile on the reference alone, as the product launches them, on the GenReads
     `ctx`.  depth: uint32[G] staged depths, codes: uint8[G] (0 .. 3, 4 = N), segs: (hap_off, len, ref_pos, ref_rec, kind) arrays in
@@ -1274,6 +1290,41 @@ class GenReads:
     def coverage_bedgraph_kernel_time(self):
         """Event pairs, milliseconds and units (bases) of the bedGraph writer's kernels in the last write call."""
         fn = self._L.scs_coverage_bedgraph_kernel_time
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
+        self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def gc_bias(self, window=100, cap_rows=None):
+        """The GC-bias table of the last yield call's per-base depth (set_coverage on), made on the GPU at this call: every window
+        of `window` bases (1 .. 1024) inside a staged record, sliding by one base, is counted under bin 100 * gc / window; a window
+        that holds an N only in n_windows.  dict of numpy arrays with records + 1 rows, the genome's last: windows, depth_sum
+        (uint64[rows][101]), n_windows (uint64[rows]) and, derived here as the file derives them, mean_depth, normalized
+        (float64[rows][101]) and row_mean (float64[rows]).  May be repeated with any window; the arrays are only read.  cap_rows:
+        the rows the call is told there is room for (default: all)."""
+        np = self._np
+        nr, _ = self.coverage_shape()
+        W = int(window)
+        a = dict(windows=np.zeros((nr + 1, 101), np.uint64), depth_sum=np.zeros((nr + 1, 101), np.uint64), n_windows=np.zeros(nr + 1, np.uint64))
+        self._L.scs_gc_bias.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        self._ck(self._L.scs_gc_bias(self._ctx, W & 0xFFFFFFFF, *[a[k].ctypes.data for k in ("windows", "depth_sum", "n_windows")], nr + 1 if cap_rows is None else int(cap_rows)))
+        n, s = a["windows"].astype(np.float64), a["depth_sum"].astype(np.float64)
+        tot_n, tot_s = a["windows"].sum(axis=1).astype(np.float64), a["depth_sum"].sum(axis=1).astype(np.float64)
+        a["mean_depth"] = np.divide(s, n * W, out=np.zeros_like(s), where=n > 0)
+        a["row_mean"] = np.divide(tot_s, W * tot_n, out=np.zeros_like(tot_s), where=tot_n > 0)
+        a["normalized"] = np.divide(a["mean_depth"], a["row_mean"][:, None], out=np.zeros_like(s), where=a["row_mean"][:, None] > 0)
+        return a
+
+    def write_gc_bias(self, path, window=100):
+        """gc_bias(window) as text written by the host: a `#gc_bias` line stating the window, `#s` summary lines per record and for
+        the genome (windows, n_windows, mean depth), then `record gc windows depth_sum mean_depth normalized model` for every bin
+        with windows, the genome's rows last; model is the loaded profile's gc_means[gc]."""
+        self._L.scs_write_gc_bias.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
+        self._ck(self._L.scs_write_gc_bias(self._ctx, os.fsencode(path), int(window) & 0xFFFFFFFF))
+
+    def gc_bias_kernel_time(self):
+        """Event pairs, milliseconds and units (staged bases) of the GC-bias kernel in the last gc_bias / write_gc_bias call."""
+        fn = self._L.scs_gc_bias_kernel_time
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
         self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))

@@ -194,6 +194,7 @@ int scs_set_coverage(scs_ctx* c, uint32_t max_depth) {
         if (max_depth == T.max_depth) return;
         HIP_OK(hipStreamSynchronize(c->stream));                                   // the last call's arrays go: nothing may still read them
         T.tab.release(); T.valid = false; T.max_depth = max_depth;
+        if (!max_depth) { c->gcb.release(); c->tm_gcbias.ev.clear(); c->tm_gcbias.used = 0; c->tm_gcbias.reset(); }   // (the GC-bias table needs this switch: scs_gcbias.cpp)
         if (!c->cov_ref.max_depth) { T.diff.release(); T.rec.release(); T.tiles.release(); T.bases = 0; T.n_rec = 0; }   // (the array does not depend on max_depth: it stays while the profile on the reference, which reads it, is on)
         if (!max_depth && !c->cov_ref.max_depth) { for (KernelTimer* t : {&c->tm_cov_mark, &c->tm_cov_finish, &c->tm_runs}) { t->ev.clear(); t->used = 0; t->reset(); } c->runs.release(); }   // (the bedGraph writer's buffers go with the last array)
     });

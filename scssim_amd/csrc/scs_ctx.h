@@ -225,6 +225,10 @@ struct RunsWork {
     DevBuf first, next, lines, bytes, offs, scan, text, crc; BgzfLane z; Pinned<char> h_text; Pinned<uint32_t> h_n;
     void release() { for (DevBuf* b : {&first, &next, &lines, &bytes, &offs, &scan, &text, &crc, &z.plan, &z.sizes, &z.offs, &z.out[0], &z.out[1]}) b->release(); h_text.release(); h_n.release(); }
 };
+// The GC-bias table's buffer (scs_gc_bias, scs_write_gc_bias; scs_gcbias.cpp): windows and depth_sum, rows
+// of 101 per staged record, and n_windows, all uint64.  Made by the first call, zeroed by every call, released with the ctx, when
+// scs_set_coverage goes off or when another genome is staged
+struct GcBiasWork { DevBuf tab; void release() { tab.release(); } };
 enum { TM_ERRSCAN,TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
 struct SinkPipe;             // scs_sink.h
@@ -295,6 +299,9 @@ struct scs_ctx {
     // coverage profile (scs_set_coverage; scs_coverage.cpp)
     CovTrack cov;
     KernelTimer tm_cov_mark{"k_cov_mark"}, tm_cov_finish{"k_cov_finish"};   // the last yield call's per-batch marks and its end-of-job pass (scs_coverage_kernel_time; not of tm[])
+    // the GC-bias table of cov's depths (scs_gcbias.cpp): made on demand after a yield call
+    GcBiasWork gcb;
+    KernelTimer tm_gcbias{"k_gc_bias"};                   // the last scs_gc_bias / scs_write_gc_bias call's kernel (scs_gc_bias_kernel_time; not one of tm[])
     // coverage profile on the reference (scs_set_coverage_ref; scs_coverage.cpp)
     CovRefTrack cov_ref;
     KernelTimer tm_cov_ref_copies{"k_cov_ref_copies"}, tm_cov_ref_finish{"k_cov_ref_finish"};   // the once-per-layout kernel and the end-of-job lift and count (scs_coverage_ref_kernel_time)
