@@ -1173,10 +1173,7 @@ class GenReads:
 
     def coverage_shape(self):
         """(staged records, max_depth) of the coverage profile."""
-        self._L.scs_coverage_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        n, d = C.c_uint32(), C.c_uint32()
-        self._ck(self._L.scs_coverage_shape(self._ctx, C.byref(n), C.byref(d)))
-        return n.value, d.value
+        return self._shape("scs_coverage_shape")
 
     def coverage(self):
         """The tables of the last yield call as numpy uint64 arrays: dict(hist=[records + 1][max_depth + 1], n_bases=, sum=, sum_n=
@@ -1205,11 +1202,7 @@ class GenReads:
     def coverage_kernel_time(self, which=0):
         """Event pairs, milliseconds and units of the last yield call's coverage passes: which=0 the per-batch marks (units: pairs),
         1 the end-of-job pass (units: staged bases)."""
-        fn = self._L.scs_coverage_kernel_time
-        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(fn(self._ctx, int(which), C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_coverage_kernel_time", which)
 
     def set_coverage_ref(self, max_depth):
         """Coverage profile on the reference: the following yield calls also keep, per base of the reference records of the lift
@@ -1221,10 +1214,7 @@ class GenReads:
 
     def coverage_ref_shape(self):
         """(reference records, max_depth) of the coverage profile on the reference."""
-        self._L.scs_coverage_ref_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        n, d = C.c_uint32(), C.c_uint32()
-        self._ck(self._L.scs_coverage_ref_shape(self._ctx, C.byref(n), C.byref(d)))
-        return n.value, d.value
+        return self._shape("scs_coverage_ref_shape")
 
     def download_coverage_ref(self):
         """The tables of the last yield call on the reference as numpy uint64 arrays: dict(hist=[ref records + 1][max_depth + 1],
@@ -1258,11 +1248,7 @@ class GenReads:
     def coverage_ref_kernel_time(self, which=0):
         """Event pairs, milliseconds and units (staged bases) of the last yield call's passes on the reference: which=0 the
         once-per-layout copies kernel (no launch while the layout stands), 1 the end-of-job lift and count."""
-        fn = self._L.scs_coverage_ref_kernel_time
-        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(fn(self._ctx, int(which), C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_coverage_ref_kernel_time", which)
 
     def _write_bedgraph(self, name, path):
         fn = getattr(self._L, name)
@@ -1289,11 +1275,7 @@ class GenReads:
 
     def coverage_bedgraph_kernel_time(self):
         """Event pairs, milliseconds and units (bases) of the bedGraph writer's kernels in the last write call."""
-        fn = self._L.scs_coverage_bedgraph_kernel_time
-        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_coverage_bedgraph_kernel_time")
 
     def gc_bias(self, window=100, cap_rows=None):
         """The GC-bias table of the last yield call's per-base depth (set_coverage on), made on the GPU at this call: every window
@@ -1324,11 +1306,7 @@ class GenReads:
 
     def gc_bias_kernel_time(self):
         """Event pairs, milliseconds and units (staged bases) of the GC-bias kernel in the last gc_bias / write_gc_bias call."""
-        fn = self._L.scs_gc_bias_kernel_time
-        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-        n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
-        return dict(launches=n.value, ms=ms.value, units=u.value)
+        return self._kernel_time("scs_gc_bias_kernel_time")
 
     def amplicon_places(self):
         """The amplified pool after allocate_reads, one entry per full amplicon in list order (the index the read names print): dict
@@ -1349,12 +1327,20 @@ class GenReads:
         self._ck(self._L.scs_write_amplicons(self._ctx, os.fsencode(path), 1 if bgzf else 0, C.byref(n)))
         return n.value
 
-    def _kernel_time(self, symbol):
+    def _kernel_time(self, symbol, which=None):
         fn = getattr(self._L, symbol)
-        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        lead = [] if which is None else [int(which)]       # the entry points with more than one timer take its index first
+        fn.argtypes = [C.c_void_p] + [C.c_int] * len(lead) + [C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         n, ms, u = C.c_uint64(), C.c_double(), C.c_uint64()
-        self._ck(fn(self._ctx, C.byref(n), C.byref(ms), C.byref(u)))
+        self._ck(fn(self._ctx, *lead, C.byref(n), C.byref(ms), C.byref(u)))
         return dict(launches=n.value, ms=ms.value, units=u.value)
+
+    def _shape(self, symbol):
+        fn = getattr(self._L, symbol)
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        n, d = C.c_uint32(), C.c_uint32()
+        self._ck(fn(self._ctx, C.byref(n), C.byref(d)))
+        return n.value, d.value
 
     def amplicon_kernel_time(self):
         """Event pairs, milliseconds and amplicons of the last write_amplicons call's kernels."""

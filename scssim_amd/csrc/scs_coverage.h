@@ -20,6 +20,12 @@ namespace scs {
 #define COV_REF_CN 16u                                     // on the reference (scs_set_coverage_ref): depth by copy number 0 .. this, the last one copies >= this
 #define COV_REF_MAX_COPIES 65535u                          // ... and the staged bases that may lift to one reference base (16 bits of its packed word)
 
+// the buckets of a workgroup's LDS histogram for a caller's `lds` (the launchers' clamp; 0: every count goes to memory)
+inline uint32_t cov_lds_buckets(uint32_t lds, uint32_t max_depth) {
+    const uint32_t n = lds < max_depth + 1u ? lds : max_depth + 1u;
+    return n < COV_LDS_BUCKETS ? n : COV_LDS_BUCKETS;
+}
+
 // What a placed read (truth_place has run) marks: mark(g, +1), mark(g + l, -1) for every maximal run [g, g + l) of genome bases
 // aligned to read bases, g a global genome index.  M runs that only an insertion separates are one run (an I moves nothing on the
 // genome); a deletion ends a run.  Leading and trailing deletions are truth_cigar_walk's to drop.  Every index lies in

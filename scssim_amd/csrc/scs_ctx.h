@@ -198,36 +198,35 @@ struct KernelTimer {         // HIP events on the ctx stream around the launches
         used = 0;
     }
     void reset() { ms = 0; launches = 0; units = 0; used = 0; }
+    void drop_events() { ev.clear(); used = 0; }         // a call's open events go (a failed wait); the sums stay
+    void drop() { drop_events(); reset(); }              // what the timer's feature made goes with the feature
 };
 // One depth track of a ctx: the bin width (0: off -- no buffer of it exists, no code of it runs), the bins of its records, the
 // counters of the last yield call (planes of `bins` entries, zeroed on the ctx stream at the start of every call; valid: a call with
 // the track on has finished) and the kernel's tables
 struct DepthTrack { uint32_t width = 0; uint64_t bins = 0; bool valid = false; DevBuf cnt, tab; };
-// The coverage profile of a ctx (scs_set_coverage; scs_coverage.cpp): max_depth (0: off -- no buffer of it exists, no code of it
-// runs); the difference array of the running yield call, the per-base depths once it has finished (bases + 1 int32, padded to
-// whole tiles, zeroed on the ctx stream at the start of every call; valid: a call with it on has finished); the tables of the
-// last call -- hist[n_rec][max_depth + 1], n_bases, sum, sum_n [n_rec], all uint64 --, the kernels' record starts and tile sums
-// (run_depth: the max_depth the array's last end-of-job pass ran with -- max_depth, or 1 for tables kept private when only the
-// profile on the reference asked for the array)
+// The coverage profile of a ctx (scs_set_coverage; scs_coverage.cpp): max_depth (0: off); the difference array of the running
+// yield call, the per-base depths once it has finished (bases + 1 int32, padded to whole tiles; valid: a call with it on has
+// finished); the last call's tables (CovTab's layout), the kernels' record starts and tile sums; run_depth: the max_depth the
+// last end-of-job pass ran with (1: tables kept private for the profile on the reference).  Which switch owns which buffer of
+// this struct and the three below: coverage_settle (scs_coverage.cpp)
 struct CovTrack { uint32_t max_depth = 0, n_rec = 0, run_depth = 0; uint64_t bases = 0; bool valid = false; DevBuf diff, tab, rec, tiles; };
-// The coverage profile on the reference (scs_set_coverage_ref; scs_coverage.cpp): max_depth (0: off -- no
-// buffer of it exists, no code of it runs); per reference base of the lift table the depth of the last yield call (uint32, padded
-// to whole tiles, zeroed on the ctx stream at the start of every call) and the packed copies | n_copies << 16 (made once per
-// genome and table: `copies` says that they stand); the tables of the last call (uint64: hist[n_ref][max_depth + 1], n_bases,
-// absent, sum, sum_n [n_ref], cn_bases, cn_sum [n_ref][17], unlifted) and the reference record starts; unlifted: the last call's
-// (the two per-base arrays are plain blocks: their size is the reference's, they never grow)
+// The coverage profile on the reference (scs_set_coverage_ref; scs_coverage.cpp): per reference base of
+// the lift table the last call's depth (uint32, padded to whole tiles) and the packed copies | n_copies << 16 (made once per
+// genome and table: `copies` says that they stand); the last call's tables (CovTab's layout), the reference record starts and
+// unlifted (the two per-base arrays are plain blocks: their size is the reference's, they never grow)
 struct CovRefTrack { uint32_t max_depth = 0, n_ref = 0; uint64_t bases = 0, unlifted = 0; bool valid = false, copies = false; DevBuf depth, packed, tab, rec; CovRefTrack() { depth.plain = packed.plain = true; } };
 // What the bedGraph writer of the per-base arrays keeps (scs_write_coverage_bedgraph ...; scs_runs.cpp): per
 // tile the first run start, the next one behind it, lines and bytes; a slab's 64-bit offsets, the scan's scratch, its text (at
 // most the text cap, whatever the genome's size), the BGZF lane over it and the pinned block it crosses to the host through.  Made
-// by the first write call, kept for the next one, released with the ctx or when both coverage switches are off
+// by the first write call, kept for the next one, released by a change of either coverage switch (coverage_settle)
 struct RunsWork {
     DevBuf first, next, lines, bytes, offs, scan, text, crc; BgzfLane z; Pinned<char> h_text; Pinned<uint32_t> h_n;
     void release() { for (DevBuf* b : {&first, &next, &lines, &bytes, &offs, &scan, &text, &crc, &z.plan, &z.sizes, &z.offs, &z.out[0], &z.out[1]}) b->release(); h_text.release(); h_n.release(); }
 };
 // The GC-bias table's buffer (scs_gc_bias, scs_write_gc_bias; scs_gcbias.cpp): windows and depth_sum, rows
-// of 101 per staged record, and n_windows, all uint64.  Made by the first call, zeroed by every call, released with the ctx, when
-// scs_set_coverage goes off or when another genome is staged
+// of 101 per staged record, and n_windows, all uint64.  Made by the first call, zeroed by every call (coverage_settle,
+// coverage_invalidate)
 struct GcBiasWork { DevBuf tab; void release() { tab.release(); } };
 enum { TM_ERRSCAN,TM_ERRSCAN_F, TM_READS, TM_ATTACH, TM_INDELS, TM_ATTACH_F, TM_TRUTH, TM_DEPTH, TM_COUNT };   // a ctx's timers, in the order scs_kernel_time(which) documents
 
@@ -452,6 +451,7 @@ void depth_open(scs_ctx* c, bool on_ref);
 // coverage_open: the call's zeroed difference array and tables and the kernels' record starts; coverage_finish: the end-of-job
 // pass on the ctx stream (lds: buckets of its LDS histogram)
 void coverage_check(scs_ctx* c);
+void coverage_invalidate(scs_ctx* c, bool genome_changed);   // another genome is staged, or (false) only another lift table: what was made of the old one no longer stands
 void coverage_open(scs_ctx* c);
 void coverage_finish(scs_ctx* c, uint32_t lds);
 // ... on the reference (scs_set_coverage_ref): coverage_check refuses it too (sharded, or no lift table); coverage_ref_open, after

@@ -4,7 +4,6 @@
 // scs_gcbias.h's, the kernel is scs_k_gcbias.hip's.  Nothing here runs unless one of the entry points below is called.
 #include "scs_textout.h"
 #include "scs_gcbias.h"
-#include <cstdarg>
 
 namespace scs {
 namespace {
@@ -34,7 +33,7 @@ GcbTables gcb_run(scs_ctx* c, DevBuf& tab, const uint32_t* depth, uint64_t depth
     std::vector<uint64_t> all(words);
     if (words) HIP_OK(hipMemcpyAsync(all.data(), tab.p, words * 8, hipMemcpyDeviceToHost, s));
     const hipError_t se = hipStreamSynchronize(s);
-    if (se != hipSuccess) { tm.ev.clear(); tm.used = 0; throw ScsError(SCS_EDEVICE, std::string("GC-bias table: ") + hipGetErrorString(se)); }
+    if (se != hipSuccess) { tm.drop_events(); throw ScsError(SCS_EDEVICE, std::string("GC-bias table: ") + hipGetErrorString(se)); }
     tm.collect();
     { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("GC-bias table: the kernel was not launched: ") + hipGetErrorString(le)); }
     const size_t rows = (size_t)nr + (genome ? 1u : 0u);
@@ -51,12 +50,6 @@ GcbTables gcb_run(scs_ctx* c, DevBuf& tab, const uint32_t* depth, uint64_t depth
 GcbTables gcb_of_ctx(scs_ctx* c, uint32_t window) {
     const CovTrack& T = c->cov;
     return gcb_run(c, c->gcb.tab, T.diff.as<uint32_t>(), cov_tiles(T.bases) * COV_TILE, c->genome.as<uint8_t>(), T.bases, T.rec.as<uint64_t>(), T.n_rec, window, 1u, true);
-}
-
-void gcb_printf(std::string& o, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-void gcb_printf(std::string& o, const char* fmt, ...) {
-    char buf[512]; va_list ap; va_start(ap, fmt); const int n = vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (n > 0) o.append(buf, std::min<size_t>((size_t)n, sizeof buf - 1));
 }
 
 }  // namespace
@@ -87,17 +80,17 @@ int scs_write_gc_bias(scs_ctx* c, const char* path, uint32_t window) {
         auto name = [&](uint32_t r) { return r < nr ? c->recs[r].name.c_str() : "genome"; };
         std::vector<GcbRow> rows; for (uint32_t r = 0; r <= nr; ++r) rows.push_back(gcb_row(t.windows.data() + (size_t)r * GCB_BINS, t.depth_sum.data() + (size_t)r * GCB_BINS, window));
         std::string o;
-        gcb_printf(o, "#gc_bias\twindow=%u\tstep=1\texcluded=windows_with_N\tbin=100*gc/window\n", window);
+        text_printf(o, "#gc_bias\twindow=%u\tstep=1\texcluded=windows_with_N\tbin=100*gc/window\n", window);
         o += "#summary\trecord\twindows\tn_windows\tmean_depth\n";
-        for (uint32_t r = 0; r <= nr; ++r) { o += "#s\t"; o += name(r); gcb_printf(o, "\t%llu\t%llu\t%.6f\n", (unsigned long long)rows[r].n, (unsigned long long)t.n_windows[r], rows[r].row_mean); }
+        for (uint32_t r = 0; r <= nr; ++r) { o += "#s\t"; o += name(r); text_printf(o, "\t%llu\t%llu\t%.6f\n", (unsigned long long)rows[r].n, (unsigned long long)t.n_windows[r], rows[r].row_mean); }
         o += "#record\tgc\twindows\tdepth_sum\tmean_depth\tnormalized\tmodel\n";
         for (uint32_t r = 0; r <= nr; ++r)
             for (uint32_t b = 0; b < GCB_BINS; ++b) {
                 const uint64_t w = t.windows[(size_t)r * GCB_BINS + b];
                 if (!w) continue;
                 o += name(r);
-                gcb_printf(o, "\t%u\t%llu\t%llu\t%.6f\t%.6f\t", b, (unsigned long long)w, (unsigned long long)t.depth_sum[(size_t)r * GCB_BINS + b], rows[r].mean[b], rows[r].normalized[b]);
-                if (c->have_profile) gcb_printf(o, "%.6g\n", c->prof.gc_means[b]); else o += ".\n";   // (the value k_weights reads for an amplicon of this bin)
+                text_printf(o, "\t%u\t%llu\t%llu\t%.6f\t%.6f\t", b, (unsigned long long)w, (unsigned long long)t.depth_sum[(size_t)r * GCB_BINS + b], rows[r].mean[b], rows[r].normalized[b]);
+                if (c->have_profile) text_printf(o, "%.6g\n", c->prof.gc_means[b]); else o += ".\n";   // (the value k_weights reads for an amplicon of this bin)
             }
         fd.write(o.data(), o.size());
         fd.finish();
@@ -115,8 +108,7 @@ int scs_gc_bias_probe(scs_ctx* c, const uint32_t* depth, const uint8_t* codes, u
         const std::string fn = "scs_gc_bias_probe";
         if (!depth || !codes || !n_bases || !rec_lens || !n_records) throw ScsError(SCS_EINVAL, fn + ": bad argument");
         gcb_window_ok(fn, window);
-        std::vector<uint64_t> roff(n_records + 1, 0);
-        for (uint32_t r = 0; r < n_records; ++r) roff[r + 1] = roff[r] + rec_lens[r];
+        const std::vector<uint64_t> roff = starts_of(std::vector<uint64_t>(rec_lens, rec_lens + n_records));
         if (roff[n_records] != n_bases) throw ScsError(SCS_EINVAL, fn + ": the records' lengths add up to " + std::to_string(roff[n_records]) + ", the arrays have " + std::to_string(n_bases) + " entries");
         const uint64_t nt = cov_tiles(n_bases);
         if (nt > 0x7FFFFFFFull) throw ScsError(SCS_EINVAL, fn + ": too many tiles");

@@ -58,20 +58,15 @@ __global__ void __launch_bounds__(256) k_cov_tile_sums(const int32_t* __restrict
 // offs[i] = sums[0] + .. + sums[i - 1]: one workgroup, COV_CHUNK sums per step (four per thread), the steps joined by a carry
 __global__ void __launch_bounds__(256) k_cov_tile_offsets(const int32_t* __restrict__ sums, int32_t* __restrict__ offs, uint64_t n) {
     __shared__ uint32_t s_w[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t carry = 0;
     for (uint64_t base = 0; base < n; base += COV_CHUNK) {
         const uint64_t i = base + threadIdx.x * 4u;
         uint32_t v[4], t = 0;
 #pragma unroll
         for (uint32_t e = 0; e < 4u; ++e) { v[e] = i + e < n ? (uint32_t)sums[i + e] : 0u; t += v[e]; }
-        const uint32_t incl = wave_incl_scan(t, (int)lane);
-        if (lane == 63u) s_w[wave] = incl;
+        const uint32_t incl = block_scan_put(t, s_w);
         __syncthreads();
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w) before += s_w[w];
-        const uint32_t tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        uint32_t ex = carry + before + incl - t;
+        uint32_t tot, ex = carry + block_scan_get(incl, t, s_w, tot);
 #pragma unroll
         for (uint32_t e = 0; e < 4u; ++e) if (i + e < n) { offs[i + e] = (int32_t)ex; ex += v[e]; }
         carry += tot;
@@ -82,7 +77,7 @@ __global__ void __launch_bounds__(256) k_cov_tile_offsets(const int32_t* __restr
 __global__ void __launch_bounds__(256) k_cov_scan_hist(CovFinish F) {
     __shared__ uint32_t s_hist[COV_LDS_BUCKETS];
     __shared__ uint32_t s_w[4];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, D = F.max_depth, nl = F.lds;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, D = F.max_depth, nl = F.lds;
     const uint64_t base = (uint64_t)blockIdx.x * COV_TILE, G = F.n_bases;
     for (uint32_t i = tid; i < nl; i += 256u) s_hist[i] = 0u;
     // the record the tile begins in: its bases use the LDS table and the per-thread sums; the others of the tile go to memory
@@ -100,21 +95,16 @@ __global__ void __launch_bounds__(256) k_cov_scan_hist(CovFinish F) {
         const uint64_t i0 = base + j * 1024u + tid * 4u;
         const int4 d = *(const int4*)(F.diff + i0);
         uint32_t p[4]; p[0] = (uint32_t)d.x; p[1] = p[0] + (uint32_t)d.y; p[2] = p[1] + (uint32_t)d.z; p[3] = p[2] + (uint32_t)d.w;
-        const uint32_t incl = wave_incl_scan(p[3], (int)lane);
-        if (lane == 63u) s_w[wave] = incl;
+        const uint32_t incl = block_scan_put(p[3], s_w);
         __syncthreads();
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w) before += s_w[w];
-        const uint32_t ex = carry + before + incl - p[3];
-        carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        uint32_t tot; const uint32_t ex = carry + block_scan_get(incl, p[3], s_w, tot);
+        carry += tot;
         __syncthreads();                                   // (s_w is written again in the next strip)
         int32_t v[4];
 #pragma unroll
         for (uint32_t e = 0; e < 4u; ++e) v[e] = (int32_t)(ex + p[e]);
         *(int4*)(F.diff + i0) = make_int4(v[0], v[1], v[2], v[3]);   // the depths, where their differences lay (non-negative, or the call fails)
-        uint32_t cw = 0;
-        if (i0 + 4u <= G) cw = *(const uint32_t*)(F.codes + i0);
-        else for (uint32_t e = 0; e < 4u; ++e) if (i0 + e < G) cw |= (uint32_t)F.codes[i0 + e] << (8u * e);
+        const uint32_t cw = codes4(F.codes, i0, G);
         uint32_t run_b = 0xFFFFFFFFu, run_n = 0;
 #pragma unroll
         for (uint32_t e = 0; e < 4u; ++e) {
@@ -151,7 +141,7 @@ uint64_t cov_tiles(uint64_t n_bases) { return (n_bases + 1u + COV_TILE - 1u) / C
 void launch_cov_finish(hipStream_t s, const CovFinish& f) {
     const uint64_t nt = cov_tiles(f.n_bases);
     if (f.n_rec == 0 || nt > 0x7FFFFFFFull) { note_launch(hipErrorInvalidValue); return; }
-    CovFinish g = f; g.lds = std::min(std::min(f.lds, f.max_depth + 1u), COV_LDS_BUCKETS);
+    CovFinish g = f; g.lds = cov_lds_buckets(f.lds, f.max_depth);
     hipLaunchKernelGGL(k_cov_tile_sums, dim3((uint32_t)nt), dim3(256), 0, s, (const int32_t*)f.diff, f.tile_sums);
     note_launch(hipGetLastError());
     hipLaunchKernelGGL(k_cov_tile_offsets, dim3(1), dim3(256), 0, s, (const int32_t*)f.tile_sums, f.tile_offs, nt);

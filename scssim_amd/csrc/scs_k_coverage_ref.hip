@@ -159,7 +159,7 @@ void launch_cov_ref_copies(hipStream_t s, const CovRefArgs& a) {
 void launch_cov_ref_finish(hipStream_t s, const CovRefArgs& a) {
     uint64_t st, rt;
     if (!cov_ref_grids(a, st, rt)) { note_launch(hipErrorInvalidValue); return; }
-    CovRefArgs g = a; g.lds = std::min(std::min(a.lds, a.max_depth + 1u), COV_LDS_BUCKETS);
+    CovRefArgs g = a; g.lds = cov_lds_buckets(a.lds, a.max_depth);
     if (st) { hipLaunchKernelGGL(k_cov_ref_lift, dim3((uint32_t)st), dim3(256), 0, s, g); note_launch(hipGetLastError()); }
     if (rt) { hipLaunchKernelGGL(k_cov_ref_hist, dim3((uint32_t)rt), dim3(256), 0, s, g); note_launch(hipGetLastError()); }
 }

@@ -26,12 +26,6 @@ namespace scs {
 #define GCB_STRIP 1024u
 #define GCB_ENTRIES (COV_TILE + GCB_MAX_WINDOW)            // 5120: tile plus the widest halo, rounded up to whole strips
 
-__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long v, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const unsigned long long t = __shfl_up(v, d); if (lane >= d) v += t; }
-    return v;
-}
-
 __global__ void __launch_bounds__(256) k_gc_bias(GcBiasArgs A) {
     __shared__ unsigned long long s_pd[GCB_ENTRIES + 1u];  // s_pd[k] = the depths of the tile's entries before k
     __shared__ uint32_t s_pc[GCB_ENTRIES + 1u];            // ... their G/C bases | their N bases << 16

@@ -169,6 +169,36 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
     return v;
 }
+__device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long long v, int lane) {
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) { const unsigned long long t = __shfl_up(v, d); if (lane >= d) v += t; }
+    return v;
+}
+// One step of a scan over a block of 256 threads (T: uint32_t or unsigned long long), in two halves around the caller's barrier.
+// block_scan_put: the wave's inclusive scan of v, the four wave totals into the caller's s_w[4].  block_scan_get, behind the
+// barrier: the sum of the v of the threads before this one; tot: the block's.  One more barrier before s_w is written again
+template <class T>
+__device__ __forceinline__ T block_scan_put(T v, T* s_w) {
+    const int lane = (int)(threadIdx.x & 63u);
+    T incl;
+    if constexpr (sizeof(T) == 8) incl = wave_incl_scan_u64(v, lane); else incl = wave_incl_scan(v, lane);
+    if (lane == 63) s_w[threadIdx.x >> 6] = incl;
+    return incl;
+}
+template <class T>
+__device__ __forceinline__ T block_scan_get(T incl, T v, const T* s_w, T& tot) {
+    T ex = incl - v;
+    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) ex += s_w[w];
+    tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return ex;
+}
+// the codes of bases i0 .. i0 + 3 as one uint32, base i0 + e in byte e: one load, or byte-wise (0 behind the end) where the array of G ends
+__device__ __forceinline__ uint32_t codes4(const uint8_t* __restrict__ codes, uint64_t i0, uint64_t G) {
+    if (i0 + 4u <= G) return *(const uint32_t*)(codes + i0);
+    uint32_t cw = 0;
+    for (uint32_t e = 0; e < 4u; ++e) if (i0 + e < G) cw |= (uint32_t)codes[i0 + e] << (8u * e);
+    return cw;
+}
 // every thread of the block must call this exactly once (contains __syncthreads)
 __device__ __forceinline__ void block_add_u64(unsigned long long v, unsigned long long* __restrict__ dst) {
     __shared__ unsigned long long s_acc;

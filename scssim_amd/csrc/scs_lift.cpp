@@ -11,7 +11,7 @@ void lift_drop(scs_ctx* c) {
     if (!c->have_lift && !c->d_lift.p) return;
     c->have_lift = false; c->lift.clear(); c->d_lift.release();
     c->depth_ref.valid = false; c->dref_copies = false; c->depth_ref.bins = 0;   // (the reference track's layout was this table's)
-    c->cov_ref.valid = false; c->cov_ref.copies = false;                         // (and so were the coverage profile's reference array and its copies)
+    coverage_invalidate(c, false);                                               // (and so were the coverage profile's reference array and its copies)
 }
 void lift_install(scs_ctx* c, LiftTable&& T) {
     lift_drop(c);

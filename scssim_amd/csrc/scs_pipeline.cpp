@@ -92,7 +92,7 @@ int scs_create(const scs_config* cfg, scs_ctx** out) {
         if (cfg->stream) c->stream.adopt((hipStream_t)cfg->stream); else c->stream.ensure(hipStreamNonBlocking);
         c->key = RngKey{(uint32_t)cfg->seed, (uint32_t)(cfg->seed >> 32)};
         for (KernelTimer& t : c->tm) t.gate = &c->timing_gate;
-        c->tm_support.gate = &c->timing_gate; c->tm_depth_ref.gate = &c->timing_gate; c->tm_support_ref_open.gate = &c->timing_gate; c->tm_support_ref_gather.gate = &c->timing_gate; c->tm_cov_mark.gate = &c->timing_gate; c->tm_cov_finish.gate = &c->timing_gate; c->tm_cov_ref_copies.gate = &c->timing_gate; c->tm_cov_ref_finish.gate = &c->timing_gate;
+        for (KernelTimer* t : c->yield_timers()) t->gate = &c->timing_gate;
         c->flags.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->flags.p, 0, 256, c->stream));
         c->dsums.reserve(256, c->stream); HIP_OK(hipMemsetAsync(c->dsums.p, 0, 256, c->stream));
         c->d_tot.reserve(256, c->stream);

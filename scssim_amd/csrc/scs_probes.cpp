@@ -181,38 +181,6 @@ int scs_coverage_stats_probe(const uint64_t* hist, uint32_t max_depth, uint64_t 
 }
 // the end-of-job pass' tile and the chunk of its tile-offset scan: where the tests aim
 void scs_coverage_tile(uint32_t* tile, uint32_t* chunk) { if (tile) *tile = COV_TILE; if (chunk) *chunk = COV_CHUNK; }
-// device test seam: the end-of-job kernels of the coverage profile alone (launch_cov_finish, scs_k_coverage.hip) over a given
-// difference array diff[n_bases + 1], the bases' codes[n_bases] (0 .. 3, 4: N) and records of rec_lens (they add up to n_bases), on
-// the ctx's stream and flags word; lds_buckets < 0: the product's.  depth[n_bases], hist[n_records][max_depth + 1], n_n / sum /
-// sum_n[n_records]; any output may be NULL.  Differences that are not those of intervals: the flag's error (SCS_EOVERFLOW)
-int scs_coverage_finish_probe(scs_ctx* c, const int32_t* diff, const uint8_t* codes, uint64_t n_bases, const uint64_t* rec_lens, uint32_t n_records, uint32_t max_depth, int lds_buckets,
-                              uint32_t* depth, uint64_t* hist, uint64_t* n_n, uint64_t* sum, uint64_t* sum_n) {
-    return guarded(c, [&] {
-        if (!diff || (n_bases && !codes) || !rec_lens || !n_records || max_depth < 1u || max_depth > COV_MAX_DEPTH) throw ScsError(SCS_EINVAL, "scs_coverage_finish_probe: bad argument");
-        std::vector<uint64_t> roff(n_records + 1, 0);
-        for (uint32_t r = 0; r < n_records; ++r) roff[r + 1] = roff[r] + rec_lens[r];
-        if (roff[n_records] != n_bases) throw ScsError(SCS_EINVAL, "scs_coverage_finish_probe: the records do not add up to n_bases");
-        const uint64_t nt = cov_tiles(n_bases); const size_t nh = (size_t)n_records * ((size_t)max_depth + 1), ntab = nh + 3 * (size_t)n_records;
-        if (nt > 0x7FFFFFFFull) throw ScsError(SCS_EINVAL, "scs_coverage_finish_probe: too many tiles");
-        hipStream_t s = c->stream; DevBuf d_diff, d_codes, d_rec, d_tiles, d_tab;
-        d_diff.reserve((size_t)nt * COV_TILE * 4, s); d_codes.reserve(std::max<size_t>(n_bases, 16), s); d_tiles.reserve((size_t)nt * 8, s); d_tab.reserve(ntab * 8, s);
-        upload(d_rec, roff, s);
-        HIP_OK(hipMemsetAsync(d_diff.p, 0, (size_t)nt * COV_TILE * 4, s)); HIP_OK(hipMemsetAsync(d_tab.p, 0, ntab * 8, s));
-        HIP_OK(hipMemcpyAsync(d_diff.p, diff, (size_t)(n_bases + 1) * 4, hipMemcpyHostToDevice, s));
-        if (n_bases) HIP_OK(hipMemcpyAsync(d_codes.p, codes, n_bases, hipMemcpyHostToDevice, s));
-        unsigned long long* tab = d_tab.as<unsigned long long>();
-        launch_cov_finish(s, CovFinish{d_diff.as<int32_t>(), d_codes.as<uint8_t>(), n_bases, d_rec.as<uint64_t>(), n_records, max_depth, lds_buckets < 0 ? COV_LDS_BUCKETS : (uint32_t)lds_buckets,
-                                       d_tiles.as<int32_t>(), d_tiles.as<int32_t>() + nt, tab, tab + nh, tab + nh + n_records, tab + nh + 2 * (size_t)n_records, c->flags.as<uint32_t>()});
-        check_flags(c);                                                            // (waits for the kernels; the flag's error where the differences are inconsistent)
-        if (depth && n_bases) HIP_OK(hipMemcpyAsync(depth, d_diff.p, (size_t)n_bases * 4, hipMemcpyDeviceToHost, s));
-        if (hist) HIP_OK(hipMemcpyAsync(hist, tab, nh * 8, hipMemcpyDeviceToHost, s));
-        if (n_n) HIP_OK(hipMemcpyAsync(n_n, tab + nh, (size_t)n_records * 8, hipMemcpyDeviceToHost, s));
-        if (sum) HIP_OK(hipMemcpyAsync(sum, tab + nh + n_records, (size_t)n_records * 8, hipMemcpyDeviceToHost, s));
-        if (sum_n) HIP_OK(hipMemcpyAsync(sum_n, tab + nh + 2 * (size_t)n_records, (size_t)n_records * 8, hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-    });
-}
-
 // host-only: one read through the function the site support kernel runs (support_read, scs_support.h) after the truth passes'
 // placement: seq = the FASTQ record's `len` bases, positions = the listed record coordinates, ascending and distinct
 int scs_support_read_probe(int n, int64_t pos0, int reverse, const int32_t* events, int nev, uint64_t rec_len, const char* seq, int len,

@@ -34,7 +34,7 @@ std::vector<RunsSlab> runs_slabs(const std::string& who, const std::vector<uint3
 // ends every way out of a write: the ctx stream drained before anyone touches the buffers again; the timer's open events dropped
 struct RunsCall {
     scs_ctx* c;
-    ~RunsCall() { (void)hipStreamSynchronize(c->stream); c->tm_runs.ev.clear(); c->tm_runs.used = 0; }
+    ~RunsCall() { (void)hipStreamSynchronize(c->stream); c->tm_runs.drop_events(); }
 };
 
 using RunsPut = std::function<void(const char*, size_t)>;

@@ -88,8 +88,8 @@ void stage_genome(scs_ctx* c, const void* d_ascii, const uint64_t* d_lens) {
     index_genome(c, tot);
     HIP_OK(hipStreamSynchronize(c->stream));
     for (auto& r : c->recs) std::vector<uint8_t>().swap(r.code);
-    c->have_genome = true; c->have_frags = false; c->amplified = false; c->allocated = false; c->depth.valid = false; c->cov.valid = false; c->cov_ref.valid = false; c->cov_ref.copies = false;
-    c->gcb.release();                                                              // (the GC-bias table's rows were the last genome's records; the stream is drained)
+    c->have_genome = true; c->have_frags = false; c->amplified = false; c->allocated = false; c->depth.valid = false;
+    coverage_invalidate(c, true);                                                  // (the stream is drained)
     lift_drop(c);                                                                  // (the lift table belonged to the genome staged before)
     c->st.records = c->recs.size(); c->st.genome_bases = tot; c->st.staged_bases = tot;
 }
@@ -290,8 +290,8 @@ bool stage_fasta_slice(scs_ctx* c, const std::string& path) {
     HIP_OK(hipStreamSynchronize(s));
     { const hipError_t le = take_launch_error(); if (le != hipSuccess) throw ScsError(SCS_EDEVICE, std::string("FASTA slice staging: ") + hipGetErrorString(le)); }
     c->sliced = true; c->slice_base = g_lo; c->slice_len = n_slice;
-    c->have_genome = true; c->have_frags = false; c->amplified = false; c->allocated = false; c->depth.valid = false; c->cov.valid = false; c->cov_ref.valid = false; c->cov_ref.copies = false;
-    c->gcb.release();                                                              // (the GC-bias table's rows were the last genome's records; the stream is drained)
+    c->have_genome = true; c->have_frags = false; c->amplified = false; c->allocated = false; c->depth.valid = false;
+    coverage_invalidate(c, true);                                                  // (the stream is drained)
     lift_drop(c);                                                                  // (the lift table belonged to the genome staged before)
     c->st.records = c->recs.size(); c->st.genome_bases = tot; c->st.staged_bases = n_slice;
     return true;

@@ -3,6 +3,7 @@
 // where they lie on the device.  The file itself is scs_outfile.h's.
 #pragma once
 #include "scs_ctx.h"
+#include <cstdarg>
 
 namespace scs {
 
@@ -13,6 +14,20 @@ inline std::vector<uint64_t> record_starts(const scs_ctx* c) {
     const size_t nr = c->recs.size(); std::vector<uint64_t> roff(nr + 1, 0);
     for (size_t r = 0; r < nr; ++r) { roff[r] = c->rec_off[r]; roff[r + 1] = c->rec_off[r] + c->rec_len[r]; }
     return roff;
+}
+
+// the same from any records' lengths
+inline std::vector<uint64_t> starts_of(const std::vector<uint64_t>& lens) {
+    std::vector<uint64_t> roff(lens.size() + 1, 0);
+    for (size_t r = 0; r < lens.size(); ++r) roff[r + 1] = roff[r] + lens[r];
+    return roff;
+}
+
+// printf behind o: a line's numbers (at most 511 bytes a call; names of any length are appended as they are)
+inline void text_printf(std::string& o, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+inline void text_printf(std::string& o, const char* fmt, ...) {
+    char buf[512]; va_list ap; va_start(ap, fmt); const int n = vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    if (n > 0) o.append(buf, std::min<size_t>((size_t)n, sizeof buf - 1));
 }
 
 // the kernels' record table on the device: record starts (n + 1), name offsets (n + 1), names, 16 bytes of slack.  It lies in the

@@ -421,3 +421,69 @@ def test_refusals_and_ownership(sv_ref, models, golden_inputs, tmp_path):
     `valid`; nothing is left once the contexts are destroyed right after a yield."""
     own = dict(prof=models["Illumina_HiSeq2500"], fa=golden_inputs["g1_hiseq2500_pe"], ref=sv_ref, out=str(tmp_path / "own"))
     run_child(_OWN, own, timeout=300, ok=True)
+
+
+# the four states of the two switches, walked along a closed path that takes each of the twelve transitions between them once
+_MATRIX = r'''
+import numpy as np
+import scssim_amd
+from scssim_amd import SCS_EINVAL
+from gpu_child import fails, job_args
+a = job_args()
+g = scssim_amd.GenReads(profile=a["prof"], coverage=2.0, seed=5)
+g.simuvars(a["ref"], a["snp"], a["vars"])
+g.run(collect=False)
+never_on = scssim_amd.live_resources()                        # before the feature was ever switched on
+WALK = [(0, 0), (1, 0), (0, 0), (0, 1), (0, 0), (1, 1), (1, 0), (0, 1), (1, 0), (1, 1), (0, 1), (1, 1), (0, 0)]
+assert len(set(zip(WALK, WALK[1:]))) == 12 and all(p != q for p, q in zip(WALK, WALK[1:]))
+same = lambda x, y: all((np.asarray(x[k]) == np.asarray(y[k])).all() for k in x)
+first, now, drift = {}, (0, 0), []
+for state in WALK:
+    had_ref, came_from = now[1], now
+    if state[0] != now[0]: g.set_coverage(50 if state[0] else 0)
+    if state[1] != now[1]: g.set_coverage_ref(1000 if state[1] else 0)
+    now = state
+    staged, ref = state
+    g.set_seed(5); g.yield_reads(collect=False)
+    seen = {}
+    if staged:
+        g.gc_bias(100); g.write_coverage_bedgraph(a["out"] + ".bg")
+        seen["cov"] = g.coverage(); seen["range"] = dict(d=g.coverage_range(0, 1000, 1250))
+        assert seen["cov"]["hist"].shape == (g.coverage_shape()[0] + 1, 51)
+    else:
+        fails(g.coverage_shape, SCS_EINVAL, "off"); fails(g.coverage, SCS_EINVAL, "off")
+        fails(lambda: g.coverage_range(0, 1000, 1250), SCS_EINVAL, "scs_coverage_range")
+        if ref: g.write_coverage_ref_bedgraph(a["out"] + "_ref.bg")
+    if ref:
+        seen["ref"] = g.download_coverage_ref(); d, cp = g.coverage_ref_range(0, 1000, 1250); seen["ref_range"] = dict(d=d, cp=cp)
+        assert seen["ref"]["hist"].shape == (4, 1001)
+    else:
+        fails(g.coverage_ref_shape, SCS_EINVAL, "off"); fails(g.download_coverage_ref, SCS_EINVAL, "off")
+        fails(lambda: g.coverage_ref_range(0, 1000, 1250), SCS_EINVAL, "scs_coverage_ref_range")
+    live = scssim_amd.live_resources()
+    launches = [g.coverage_kernel_time(0)["launches"], g.coverage_kernel_time(1)["launches"], g.coverage_ref_kernel_time(0)["launches"], g.coverage_ref_kernel_time(1)["launches"]]
+    print(state, "live", live, "launches", launches, flush=True)
+    # the staged array's two passes run for either switch; the copies are made once per layout, which a change of the reference switch forgets
+    assert (launches[0] > 0 and launches[1] == 1) if staged or ref else launches[:2] == [0, 0], (state, launches)
+    assert launches[2:] == ([1 if not had_ref else 0, 1] if ref else [0, 0]), (state, had_ref, launches)
+    if state == (0, 0): assert live == never_on, (never_on, live)
+    if state not in first: first[state] = (live, seen)
+    else:
+        if live != first[state][0]: drift.append((came_from, state, first[state][0], live))   # (asserted behind the walk, so that the walk's other checks run)
+        assert all(same(seen[k], first[state][1][k]) for k in seen) and seen.keys() == first[state][1].keys(), state
+assert len(first) == 4
+g.close()
+assert scssim_amd.live_resources() == (0, 0, 0, 0), scssim_amd.live_resources()
+assert not drift, drift
+print("ok")
+'''
+
+
+def test_the_switch_matrix(sv_ref, models, tmp_path):
+    """6: one ctx on the golden simuvars genome walks the four states of (scs_set_coverage 50, scs_set_coverage_ref 1000) along a
+    closed path that takes each of the twelve transitions once, a yield in every state (gc_bias and a bedGraph where the staged
+    switch is on, the reference bedGraph where only the other one is).  In every state the live resources, the tables of the
+    switches that are on and one 250-base window equal those of the state's first visit; off/off holds what the ctx held before the
+    feature was ever on; an off switch's accessors are refused and its timers read no launch; the copies kernel runs exactly when the
+    reference switch has just come on; nothing is left after close()."""
+    run_child(_MATRIX, dict(prof=models["Illumina_HiSeq2500"], ref=sv_ref, snp=os.path.join(SV, "snp.txt"), vars=os.path.join(SV, "vars.txt"), out=str(tmp_path / "mx")), timeout=300, ok=True)
